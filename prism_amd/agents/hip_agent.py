@@ -11,7 +11,9 @@ Data-parallel: ``torch.distributed`` all-reduce (RCCL over xGMI) of the flat gra
 between the two native calls; clip + Adam then run redundantly on every rank so replicas stay
 bit-identical.
 """
+import contextlib
 import ctypes
+import gc
 import os
 
 import numpy as np
@@ -20,6 +22,22 @@ import torch
 from prism_amd import _native as N
 from prism_amd import dist as pdist
 from prism_amd.util import ref_pickle
+
+
+@contextlib.contextmanager
+def graph_capture(g, **kwargs):
+    """``torch.cuda.graph(g)`` with Python's cyclic garbage collector held off until the capture has ended.  A collection
+    that an allocation triggers inside the capture would run the destructors of unreachable objects there -- a dropped
+    agent is such garbage (its model's load hook refers back to it) and takes hipGraphs, events and pinned buffers with
+    it -- and a HIP call from one of those in the middle of a capture aborts the process."""
+    enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(g, **kwargs):
+            yield
+    finally:
+        if enabled:
+            gc.enable()
 
 
 class HipAdam:
@@ -452,7 +470,7 @@ class HipAgent:
     def _capture(self, buf, d):
         if self.world == 1:
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with graph_capture(g):
                 self._launch_fused(buf, d)
             g.replay()
             return (g,)
@@ -464,7 +482,7 @@ class HipAgent:
             # graphs around an eagerly launched collective, for good.
             g, err = torch.cuda.CUDAGraph(), None
             try:
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                with graph_capture(g, capture_error_mode="thread_local"):
                     self._launch_fused(buf, d)
             except Exception as e:          # noqa: BLE001 -- any capture failure selects the split form
                 err = repr(e)
@@ -482,11 +500,11 @@ class HipAgent:
                           "running two graphs around an eager collective")
             # nothing of the step has run yet (a capture only records): fall through
         g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g1):
+        with graph_capture(g1):
             self._launch_fused(buf, d, "front")
         g1.replay()
         self._allreduce()
-        with torch.cuda.graph(g2):
+        with graph_capture(g2):
             self._launch_fused(buf, d, "back")
         g2.replay()
         return (g1, g2)
@@ -687,7 +705,7 @@ class HipAgent:
                     st["g"] = []
                     for slot in range(4):
                         g = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(g):
+                        with graph_capture(g):
                             launch(slot)
                         st["g"].append(g)
                 st["g"][k].replay()

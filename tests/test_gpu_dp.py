@@ -256,6 +256,7 @@ def test_direct_allreduce_flag_kernels_single_rank_and_graph_replay():
         pytest.skip("needs a GPU")
     import ctypes
     from prism_amd import _native as N
+    from prism_amd.agents.hip_agent import graph_capture
     dev = "cuda:0"
     flat = torch.randn(10_007, device=dev)
     want = flat.clone()
@@ -280,7 +281,7 @@ def test_direct_allreduce_flag_kernels_single_rank_and_graph_replay():
         f = read_flags()
         assert f[N.MAX_PEERS + 1] == 2 and f[0] == 3 * 1 + 3 and f[N.MAX_PEERS] == 0
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+        with graph_capture(g):
             allreduce()
         for _ in range(3):
             g.replay()
