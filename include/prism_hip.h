@@ -241,9 +241,9 @@ typedef struct prism_learner_desc {
      * separate launches by itself when the launch would not be resident at once or no priority writeback rides along
      * (fused_replay unset: nothing to hide behind the barrier).  Results are bit-identical.
      * The residency proof (occupancy of the launched instantiation x CUs of the current device) assumes the process has the
-     * GPU to itself: with other processes' kernels on the device leave it 0 (or set PRISM_NO_FUSED_TAIL=1).  A barrier that
-     * is not through after 100 ms is abandoned: the workgroup sets PRISM_WS_STATUS_BARRIER_TIMEOUT in the workspace's
-     * status word and skips its update instead of spinning for ever. */
+     * GPU to itself: with other processes' kernels on the device leave it 0.  A barrier that is not through after 100 ms
+     * is abandoned: the workgroup sets PRISM_WS_STATUS_BARRIER_TIMEOUT in the workspace's status word and skips its
+     * update instead of spinning for ever. */
     int32_t fuse_tail;
     /* prism_act_forward only.  PRISM_ACT_WEIGHTS_CURRENT: the stream-packed weight copies and LayerNorm helper vectors in
      * the workspace were built from `params` as they are now (an earlier prism_act_forward without this flag ran since the

@@ -700,18 +700,12 @@ inline BwdGeom bwd_geometry(int H, int B, int C, int T, int n_chunks, bool conv)
     g.main_lds = bwd_main_lds(H, B, C, T, n_chunks, conv);
     return g;
 }
-#ifndef BWD_CHUNKS
-#define BWD_CHUNKS 8
-#endif
 
-// DB = true: ONE wave per SIMD (one workgroup per CU, twice the register budget): the workgroup's weight slices
-// live in registers, tiles are double-buffered -- every operand of tile i+1 is requested at the start of tile i --
-// and the wave feeds the matrix pipe on its own (three independent chains, VALU in the MFMA shadows).
-// DB = false: operands roll forward inside one register set (every set is refilled right after its last use), weight
-// slices are read from LDS; width 128: two workgroups per CU share each SIMD, width 256: one (the accumulators
-// alone take 80 registers; two tile sets do not fit).
-template <int H, bool LN, bool DB>
-__global__ __launch_bounds__(256, (H == 128 && !DB) ? 2 : 1) void iqn_bwd_kernel(IqnArgs a) {
+// A tile's operands roll forward inside one register set (each part is refilled for the next tile right after its last
+// use in this one); the weight slices are read from LDS.  Width 128: two workgroups per CU share each SIMD; width 256:
+// one (the accumulators alone take 80 registers).
+template <int H, bool LN>
+__global__ __launch_bounds__(256, H == 128 ? 2 : 1) void iqn_bwd_kernel(IqnArgs a) {
     kernarg_prefetch<sizeof(IqnArgs)>();
     constexpr int NHT = H / 16, NU = H / 64, BWD_ACC = bwd_acc(H);
     constexpr int SLAB_W1 = E_DIM * K_BASIS + E_DIM + (LN ? 2 * E_DIM : 0);     // slab: phi_w | phi_b | [ln1_g | ln1_b] | w1
@@ -852,51 +846,30 @@ __global__ __launch_bounds__(256, (H == 128 && !DB) ? 2 : 1) void iqn_bwd_kernel
                 S.ph[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_ph, vo_ph + 64 * r, so, 0));
         }
     };
-    TileSet S0, S1;
-    S0.mu = S0.c1 = S0.c2 = S1.mu = S1.c1 = S1.c2 = f32x4{0.f, 0.f, 0.f, 0.f};
-    S0.rs = S1.rs = f32x4{1.f, 1.f, 1.f, 1.f};
+    TileSet S0;
+    S0.mu = S0.c1 = S0.c2 = f32x4{0.f, 0.f, 0.f, 0.f};
+    S0.rs = f32x4{1.f, 1.f, 1.f, 1.f};
     if (tiles_per_wave > 0) {
         load_rows_a(S0, 0);
         load_scalars(S0, 0);
         load_rows_b(S0, 0);
     }
     __syncthreads();          // weight slices (and every wave's observation rows) are in LDS
-    f32x4 wphr[4], w1r[NHT];  // DB: this lane's B operands of the phi / dX products, for the whole kernel
-    if (DB) {
-        if (!PHI_SAVED) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) wphr[q] = wphil[q * 64 + lane];
-        }
-#pragma unroll
-        for (int q = 0; q < NHT; ++q) w1r[q] = w1l[q * 64 + lane];
-    }
     PRISM_STAMP(9);
 
-    auto tile = [&](TileSet &S, TileSet &Sn, int ti) __attribute__((always_inline)) {
+    auto tile = [&](TileSet &S, int ti) __attribute__((always_inline)) {
         const int r0 = (tile_begin + ti) * 16;
         const bool more = ti + 1 < tiles_per_wave;
         const int bsm = (r0 + 4 * g) / T;
-        if (DB && more) {          // the whole next tile, a full tile ahead of its first use
-            load_rows_a(Sn, ti + 1);
-            load_scalars(Sn, ti + 1);
-            load_rows_b(Sn, ti + 1);
-        }
         // ---- dX columns (and, width 256, the phi columns): independent MFMA chains interleaved -------------------
         f32x4 aphi = {0.f, 0.f, 0.f, 0.f}, adx = {0.f, 0.f, 0.f, 0.f}, adx2 = {0.f, 0.f, 0.f, 0.f};
         __builtin_amdgcn_sched_barrier(0);
         if (ti < 4) PRISM_LOOP_STAMP(16 + 4 * ti);
 #pragma unroll
         for (int q = 0; q < NHT / 2; ++q) {
-            f32x4 wa, wb, wp = {0.f, 0.f, 0.f, 0.f};
-            if (DB) {
-                wa = w1r[2 * q];
-                wb = w1r[2 * q + 1];
-                if (!PHI_SAVED && q < 4) wp = wphr[q & 3];
-            } else {
-                wa = w1l[(2 * q) * 64 + lane];
-                wb = w1l[(2 * q + 1) * 64 + lane];
-                if (!PHI_SAVED && q < 4) wp = wphil[(q & 3) * 64 + lane];
-            }
+            const f32x4 wa = w1l[(2 * q) * 64 + lane], wb = w1l[(2 * q + 1) * 64 + lane];
+            f32x4 wp = {0.f, 0.f, 0.f, 0.f};
+            if (!PHI_SAVED && q < 4) wp = wphil[(q & 3) * 64 + lane];
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 if (!PHI_SAVED && q < 4) aphi = mfma16(S.ac[PHI_SAVED ? 0 : q & 3][c], wp[c], aphi);
@@ -907,7 +880,7 @@ __global__ __launch_bounds__(256, (H == 128 && !DB) ? 2 : 1) void iqn_bwd_kernel
         }
         __builtin_amdgcn_sched_barrier(0);
         if (ti < 4) PRISM_LOOP_STAMP(17 + 4 * ti);
-        if (!DB && more) load_rows_a(S, ti + 1);  // the row-on-lane registers are free: refill them for the next tile
+        if (more) load_rows_a(S, ti + 1);  // the row-on-lane registers are free: refill them for the next tile
         __builtin_amdgcn_sched_barrier(0);
         // ---- elementwise backward of row group r (column n), then the weight-gradient MFMAs of that group:
         // the VALU work of group r + 1 issues in the shadow of the MFMAs of group r
@@ -943,7 +916,7 @@ __global__ __launch_bounds__(256, (H == 128 && !DB) ? 2 : 1) void iqn_bwd_kernel
         __builtin_amdgcn_sched_barrier(0);
         if (ti < 4) PRISM_LOOP_STAMP(18 + 4 * ti);
         const bool ev_pos = ev > 0.f;
-        if (!DB && more) {
+        if (more) {
             load_rows_b(S, ti + 1);
             load_scalars(S, ti + 1);
         }
@@ -969,14 +942,7 @@ __global__ __launch_bounds__(256, (H == 128 && !DB) ? 2 : 1) void iqn_bwd_kernel
         if (n_mine) s_dcv[ti * 64 + lane] = dcv;
         if (ti < 4) PRISM_LOOP_STAMP(19 + 4 * ti);
     };
-    if (DB) {
-        for (int ti = 0; ti < tiles_per_wave; ti += 2) {
-            tile(S0, S1, ti);
-            if (ti + 1 < tiles_per_wave) tile(S1, S0, ti + 1);
-        }
-    } else {
-        for (int ti = 0; ti < tiles_per_wave; ++ti) tile(S0, S0, ti);
-    }
+    for (int ti = 0; ti < tiles_per_wave; ++ti) tile(S0, ti);
     // ---- conv taps of (sample, channel cs>>2, output position (y0 + (j>>3), j&7)) for every tile of this wave;
     // LDS reads of this wave's own earlier writes need no barrier
     float cacc[BWD_CONV_TAPS], cbias = 0.f;

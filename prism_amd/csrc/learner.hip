@@ -79,18 +79,10 @@ struct Carver {
     }
 };
 
-// backward decomposition: one workgroup per CU with double-buffered tiles (4 row chunks x 64 column slices = 256
-// workgroups), or two workgroups per CU sharing each SIMD (8 row chunks; width 128 only).  Measured on MI355X
-// (configs[2]): 33.4 us vs 30.3 us -- one wave per SIMD cannot keep the matrix pipe fed through its own VALU and
-// hazard bubbles, the shared form is the default; PRISM_BWD_MODE=1 picks the first form for A/B runs.
+// backward decomposition (iqn_bwd_kernel) into row chunks x 64 column slices: width 128, two workgroups per CU share
+// each SIMD (8 row chunks); width 256, one workgroup per CU (4 row chunks)
 static constexpr int MAX_CHUNKS = 16;
-static int bwd_mode() {
-    static const int mode = [] { const char *e = getenv("PRISM_BWD_MODE"); return e ? atoi(e) : 0; }();
-    return mode;
-}
-static bool bwd_double_buffered(int H) { return H == 128 && bwd_mode() != 0; }
-static int bwd_chunks(int H) { return (H == 128 && bwd_mode() == 0) ? 8 : 4; }      // workgroups per CU x 4
-
+static int bwd_chunks(int H) { return H == 128 ? 8 : 4; }      // workgroups per CU x 4
 
 static bool width_ok(int h) { return h == 128 || h == 256; }
 
@@ -116,15 +108,13 @@ static int use_split(const prism_learner_desc *ld) {
 // the 64-column bf16 backward (bwd3_kernels.h) where it applies: bf16 mode, width 128 (the forward then saves ReLU(phi))
 static bool use_bw3(const prism_learner_desc *ld) {
     const prism_model_dims &d = ld->dims;
-    static const bool off = [] { const char *e = getenv("PRISM_NO_BWD3"); return e && atoi(e) != 0; }();
-    return !off && d.use_iqn && use_split(ld) && bw3_ok(d.iqn_width, ld->batch, d.n_tau, true);
+    return d.use_iqn && use_split(ld) && bw3_ok(d.iqn_width, ld->batch, d.n_tau, true);
 }
 
 // ... and its width-256 form (bwd4_kernels.h: pairs of waves share 16 columns, one hidden half each)
 static bool use_bw4(const prism_learner_desc *ld) {
     const prism_model_dims &d = ld->dims;
-    static const bool off = [] { const char *e = getenv("PRISM_NO_BWD4"); return e && atoi(e) != 0; }();
-    return !off && d.use_iqn && use_split(ld) && bw4_ok(d.iqn_width, ld->batch, d.n_tau);
+    return d.use_iqn && use_split(ld) && bw4_ok(d.iqn_width, ld->batch, d.n_tau);
 }
 static int iqn_supported(const prism_model_dims *d, int32_t B) {
     auto pow2_ok = [](int t) { return t == 4 || t == 8 || t == 16 || t == 32 || t == 64; };
@@ -519,6 +509,19 @@ static hipError_t set_max_lds(const void *fn, size_t bytes) {
     return e;
 }
 
+// launch of a kernel with `lds` bytes of dynamic LDS, after the opt-in to `opt_in` bytes (0: `lds`); the caller checks the launch
+static int launch_lds(void (*kernel)(IqnArgs), const char *name, dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+                      IqnArgs a, size_t opt_in = 0) {
+    const hipError_t e = set_max_lds((const void *)kernel, opt_in ? opt_in : lds);
+    if (e != hipSuccess) {
+        set_error("hipFuncSetAttribute(%s): %s", name, hipGetErrorString(e));
+        return PRISM_ERR_HIP;
+    }
+    void *args[] = {&a};
+    (void)hipLaunchKernel((const void *)kernel, grid, block, args, lds, stream);
+    return PRISM_OK;
+}
+
 static int device_cus() {
     static std::mutex mu;
     static std::map<int, int> cache;
@@ -533,15 +536,47 @@ static int device_cus() {
 
 // Forward tiles on four waves (fwd_kernels.h, WAVES = 4: two 256-thread workgroups per CU, the latency-bound phases of one tile
 // beside the weight stream of another): where the launch has at least two tiles per CU and no mixed tile (their loss tail
-// needs all sixteen rows in registers at once).  PRISM_FWD_WAVES=8 / 4 forces a form (A/B runs).
+// needs all sixteen rows in registers at once).
 static bool fwd_four_waves(const IqnArgs &aa, int tiles) {
     if (!aa.split) return false;
     for (int i = 0; i < aa.n_pass; ++i)
         if (aa.pass[i].kind == 2) return false;
-    static const int forced = [] { const char *e = getenv("PRISM_FWD_WAVES"); return e ? atoi(e) : 0; }();
-    if (forced == 8) return false;
-    if (forced == 4) return true;
     return tiles >= 2 * device_cus();
+}
+
+// the forward tiles of every pass: one launch when every tile kind has the same hidden width, else one per kind
+static int launch_fwd_tiles(const IqnArgs &a, hipStream_t stream) {
+    auto launch = [&](const IqnArgs &aa, int H, int tiles) {
+        int rc = PRISM_OK;
+        dispatch_hl(H, aa.ln, [&](auto h, auto l) {
+            constexpr int HH = decltype(h)::value;
+            constexpr bool LL = decltype(l)::value;
+            const size_t lds = fw_lds_floats<HH>() * sizeof(float);
+            if constexpr (HH == 128) {
+                if (fwd_four_waves(aa, tiles)) {
+                    rc = launch_lds(fwd_tile_kernel<HH, LL, true, 4>, "fwd_tile", dim3(tiles), dim3(256),
+                                    fw_lds_floats<HH, 4>() * sizeof(float), stream, aa);
+                    return;
+                }
+            }
+            if (aa.split) rc = launch_lds(fwd_tile_kernel<HH, LL, true>, "fwd_tile", dim3(tiles), dim3(fw_threads(HH)), lds, stream, aa);
+            else rc = launch_lds(fwd_tile_kernel<HH, LL>, "fwd_tile", dim3(tiles), dim3(fw_threads(HH)), lds, stream, aa);
+        });
+        return rc;
+    };
+    int n_iqn = 0, n_q = 0;
+    for (int i = 0; i < a.n_pass; ++i) (a.pass[i].kind == 1 ? n_q : n_iqn) += a.pass[i].n_tiles;
+    if (n_iqn && n_q && a.Hi != a.Hq) {
+        IqnArgs a1 = a, a2 = a;
+        a1.n_pass = a2.n_pass = 0;
+        for (int i = 0; i < a.n_pass; ++i) {
+            if (a.pass[i].kind == 1) a2.pass[a2.n_pass++] = a.pass[i];
+            else a1.pass[a1.n_pass++] = a.pass[i];
+        }
+        const int rc = launch(a1, a.Hi, n_iqn);
+        return rc ? rc : launch(a2, a.Hq, n_q);
+    }
+    return n_iqn + n_q > 0 ? launch(a, n_iqn ? a.Hi : a.Hq, n_iqn + n_q) : PRISM_OK;
 }
 
 // ---- the post launch: gradient slabs / small tensors / conv fold (+ priority writeback block); with `tail` also the
@@ -579,11 +614,8 @@ static bool tail_fused(const prism_learner_desc *ld) {
     if (!ld->fuse_tail || ld->hyper.grad_scale != 1.0f) return false;
     // without a priority writeback riding along there is nothing for the fused launch to hide behind the barrier
     // (measured, uniform replay + one-layer DQN head: 32.7 us fused vs 30.1 us as two launches)
-    static const bool always = [] { const char *e = getenv("PRISM_FUSED_TAIL_ALWAYS"); return e && atoi(e) != 0; }();
     // (an IQN's gradient slabs are enough to hide: additive ablation base, uniform replay, width 256: 95.5 vs 97.3 us per step)
-    if (!always && !writeback_rides(ld) && !ld->dims.use_iqn) return false;
-    static const bool off = [] { const char *e = getenv("PRISM_NO_FUSED_TAIL"); return e && atoi(e) != 0; }();
-    if (off) return false;
+    if (!writeback_rides(ld) && !ld->dims.use_iqn) return false;
     return post_block_count(ld) + 1 <= post_max_resident(post_dense(ld));
 }
 
@@ -624,58 +656,16 @@ extern "C" int prism_learner_fwd_bwd(const prism_learner_desc *ld, prism_stream_
     const int B = ld->batch;
     IqnArgs a;
     fill_iqn_args(ld, a);
-    hipError_t herr = hipSuccess;
 
     if (!ld->embed_done) {
         ProfileScope ps_(K_EMBED, stream);
         hipLaunchKernelGGL(iqn_embed_kernel, dim3(2 * B + front_extra_blocks(extra_dims(a))), dim3(256), 0, stream, a);
         PRISM_CHECK_LAUNCH();
     }
-    // forward tiles: one launch when every tile kind has the same hidden width, else one per kind
     {
-        int n_iqn = 0, n_q = 0;
-        for (int i = 0; i < a.n_pass; ++i) (a.pass[i].kind == 1 ? n_q : n_iqn) += a.pass[i].n_tiles;
-        auto launch = [&](const IqnArgs &aa, int H, int tiles) {
-            dispatch_hl(H, aa.ln, [&](auto h, auto l) {
-                constexpr int HH = decltype(h)::value;
-                constexpr bool LL = decltype(l)::value;
-                const size_t lds = fw_lds_floats<HH>() * sizeof(float);
-                if constexpr (HH == 128) {
-                    if (aa.split && fwd_four_waves(aa, tiles)) {
-                        const size_t lds4 = fw_lds_floats<HH, 4>() * sizeof(float);
-                        herr = set_max_lds((const void *)fwd_tile_kernel<HH, LL, true, 4>, lds4);
-                        if (herr == hipSuccess)
-                            hipLaunchKernelGGL((fwd_tile_kernel<HH, LL, true, 4>), dim3(tiles), dim3(256), lds4, stream, aa);
-                        return;
-                    }
-                }
-                if (aa.split) {
-                    herr = set_max_lds((const void *)fwd_tile_kernel<HH, LL, true>, lds);
-                    if (herr == hipSuccess)
-                        hipLaunchKernelGGL((fwd_tile_kernel<HH, LL, true>), dim3(tiles), dim3(fw_threads(HH)), lds, stream, aa);
-                    return;
-                }
-                herr = set_max_lds((const void *)fwd_tile_kernel<HH, LL>, lds);
-                if (herr == hipSuccess) hipLaunchKernelGGL((fwd_tile_kernel<HH, LL>), dim3(tiles), dim3(fw_threads(HH)), lds, stream, aa);
-            });
-        };
         ProfileScope ps_(K_TILE_FWD, stream);
-        if (n_iqn && n_q && a.Hi != a.Hq) {
-            IqnArgs a1 = a, a2 = a;
-            a1.n_pass = a2.n_pass = 0;
-            for (int i = 0; i < a.n_pass; ++i) {
-                if (a.pass[i].kind == 1) a2.pass[a2.n_pass++] = a.pass[i];
-                else a1.pass[a1.n_pass++] = a.pass[i];
-            }
-            launch(a1, a.Hi, n_iqn);
-            launch(a2, a.Hq, n_q);
-        } else if (n_iqn + n_q > 0) {
-            launch(a, n_iqn ? a.Hi : a.Hq, n_iqn + n_q);
-        }
-        if (herr != hipSuccess) {
-            set_error("hipFuncSetAttribute(fwd_tile): %s", hipGetErrorString(herr));
-            return PRISM_ERR_HIP;
-        }
+        rc = launch_fwd_tiles(a, stream);
+        if (rc) return rc;
         PRISM_CHECK_LAUNCH();
     }
     // losses first (TD errors final), then the backward kernels
@@ -714,32 +704,14 @@ extern "C" int prism_learner_fwd_bwd(const prism_learner_desc *ld, prism_stream_
         ProfileScope ps_(K_BWD, stream);
         const dim3 grid((E_DIM / 64) * BW3_RC);
         const size_t lds = (size_t)bw3_lds_bytes(B, a.T, a.C, a.conv_in_bwd != 0);
-        if (a.ln) {
-            herr = set_max_lds((const void *)iqn_bwd3_kernel<true>, 160 * 1024);
-            if (herr == hipSuccess) hipLaunchKernelGGL((iqn_bwd3_kernel<true>), grid, dim3(512), lds, stream, a);
-        } else {
-            herr = set_max_lds((const void *)iqn_bwd3_kernel<false>, 160 * 1024);
-            if (herr == hipSuccess) hipLaunchKernelGGL((iqn_bwd3_kernel<false>), grid, dim3(512), lds, stream, a);
-        }
-        if (herr != hipSuccess) {
-            set_error("hipFuncSetAttribute(iqn_bwd3): %s", hipGetErrorString(herr));
-            return PRISM_ERR_HIP;
-        }
+        rc = launch_lds(a.ln ? iqn_bwd3_kernel<true> : iqn_bwd3_kernel<false>, "iqn_bwd3", grid, dim3(512), lds, stream, a, 160 * 1024);
+        if (rc) return rc;
         PRISM_CHECK_LAUNCH();
     } else if (ld->dims.use_iqn && use_bw4(ld)) {
         ProfileScope ps_(K_BWD, stream);
         const dim3 grid((E_DIM / 32) * a.n_chunks);
-        if (a.ln) {
-            herr = set_max_lds((const void *)iqn_bwd4_kernel<true>, BW4_LDS_BYTES);
-            if (herr == hipSuccess) hipLaunchKernelGGL((iqn_bwd4_kernel<true>), grid, dim3(512), BW4_LDS_BYTES, stream, a);
-        } else {
-            herr = set_max_lds((const void *)iqn_bwd4_kernel<false>, BW4_LDS_BYTES);
-            if (herr == hipSuccess) hipLaunchKernelGGL((iqn_bwd4_kernel<false>), grid, dim3(512), BW4_LDS_BYTES, stream, a);
-        }
-        if (herr != hipSuccess) {
-            set_error("hipFuncSetAttribute(iqn_bwd4): %s", hipGetErrorString(herr));
-            return PRISM_ERR_HIP;
-        }
+        rc = launch_lds(a.ln ? iqn_bwd4_kernel<true> : iqn_bwd4_kernel<false>, "iqn_bwd4", grid, dim3(512), BW4_LDS_BYTES, stream, a);
+        if (rc) return rc;
         PRISM_CHECK_LAUNCH();
     } else if (ld->dims.use_iqn) {
         if (!bwd_lds_layout_ok(a.Hi, B, a.C, a.T, a.n_chunks, a.conv_in_bwd != 0)) {
@@ -747,64 +719,32 @@ extern "C" int prism_learner_fwd_bwd(const prism_learner_desc *ld, prism_stream_
             return PRISM_ERR_INVALID;
         }
         ProfileScope ps_(K_BWD, stream);
-        const bool db = bwd_double_buffered(a.Hi);
+        const size_t lds = (size_t)bwd_lds_floats(a.Hi, B, a.C, a.T, a.n_chunks, a.conv_in_bwd != 0) * sizeof(float);
         dispatch_hl(a.Hi, a.ln, [&](auto h, auto l) {
-            constexpr int HH = decltype(h)::value;
-            constexpr bool LL = decltype(l)::value;
-            const size_t lds = (size_t)bwd_lds_floats(HH, B, a.C, a.T, a.n_chunks, a.conv_in_bwd != 0) * sizeof(float);
-            const dim3 grid((E_DIM / 16) * a.n_chunks);
-            if constexpr (HH == 128) {
-                if (db) {
-                    herr = set_max_lds((const void *)iqn_bwd_kernel<HH, LL, true>, lds);
-                    if (herr == hipSuccess) hipLaunchKernelGGL((iqn_bwd_kernel<HH, LL, true>), grid, dim3(256), lds, stream, a);
-                    return;
-                }
-            }
-            herr = set_max_lds((const void *)iqn_bwd_kernel<HH, LL, false>, lds);
-            if (herr == hipSuccess) hipLaunchKernelGGL((iqn_bwd_kernel<HH, LL, false>), grid, dim3(256), lds, stream, a);
+            rc = launch_lds(iqn_bwd_kernel<decltype(h)::value, decltype(l)::value>, "iqn_bwd", dim3((E_DIM / 16) * a.n_chunks),
+                            dim3(256), lds, stream, a);
         });
-        if (herr != hipSuccess) {
-            set_error("hipFuncSetAttribute(iqn_bwd): %s", hipGetErrorString(herr));
-            return PRISM_ERR_HIP;
-        }
+        if (rc) return rc;
         PRISM_CHECK_LAUNCH();
     }
     if (ld->dims.n_heads > 0 && ld->dims.head_layers == 2 && a.split && qb2_ok(a.Hq, B, ld->dims.n_heads, ld->dims.head_layers)) {
         ProfileScope ps_(K_Q_BWD, stream);
-        const dim3 grid(qb2_blocks(ld->dims.n_heads, B));
-        if (a.ln) {
-            herr = set_max_lds((const void *)qh_bwd2_kernel<true>, QB2_LDS_BYTES);
-            if (herr == hipSuccess) hipLaunchKernelGGL((qh_bwd2_kernel<true>), grid, dim3(256), QB2_LDS_BYTES, stream, a);
-        } else {
-            herr = set_max_lds((const void *)qh_bwd2_kernel<false>, QB2_LDS_BYTES);
-            if (herr == hipSuccess) hipLaunchKernelGGL((qh_bwd2_kernel<false>), grid, dim3(256), QB2_LDS_BYTES, stream, a);
-        }
-        if (herr != hipSuccess) {
-            set_error("hipFuncSetAttribute(qh_bwd2): %s", hipGetErrorString(herr));
-            return PRISM_ERR_HIP;
-        }
+        rc = launch_lds(a.ln ? qh_bwd2_kernel<true> : qh_bwd2_kernel<false>, "qh_bwd2", dim3(qb2_blocks(ld->dims.n_heads, B)),
+                        dim3(256), QB2_LDS_BYTES, stream, a);
+        if (rc) return rc;
         PRISM_CHECK_LAUNCH();
     } else if (ld->dims.n_heads > 0 && ld->dims.head_layers == 2) {
         ProfileScope ps_(K_Q_BWD, stream);
+        const size_t lds = qb_lds_floats(a.Hq) * sizeof(float);
         dispatch_hl(a.Hq, a.ln, [&](auto h, auto l) {
             constexpr int HH = decltype(h)::value;
             constexpr bool LL = decltype(l)::value;
-            const size_t lds = qb_lds_floats(HH) * sizeof(float);
-            static const bool cols_off = [] { const char *e = getenv("PRISM_QB_COLS"); return e && atoi(e) == 0; }();      // (A/B runs)
-            if (B <= 128 && !cols_off) {      // small batches: a wave per column slice over all rows (qhead_kernels.h, COLS)
-                herr = set_max_lds((const void *)qh_bwd_kernel<HH, LL, true>, lds);
-                if (herr == hipSuccess)
-                    hipLaunchKernelGGL((qh_bwd_kernel<HH, LL, true>), dim3((E_DIM / 64) * ld->dims.n_heads), dim3(256), lds, stream, a);
-                return;
-            }
-            herr = set_max_lds((const void *)qh_bwd_kernel<HH, LL>, lds);
-            if (herr == hipSuccess)
-                hipLaunchKernelGGL((qh_bwd_kernel<HH, LL>), dim3((E_DIM / 16) * ld->dims.n_heads), dim3(256), lds, stream, a);
+            if (B <= 128)      // small batches: a wave per column slice over all rows (qhead_kernels.h, COLS)
+                rc = launch_lds(qh_bwd_kernel<HH, LL, true>, "qh_bwd", dim3((E_DIM / 64) * ld->dims.n_heads), dim3(256), lds, stream, a);
+            else
+                rc = launch_lds(qh_bwd_kernel<HH, LL>, "qh_bwd", dim3((E_DIM / 16) * ld->dims.n_heads), dim3(256), lds, stream, a);
         });
-        if (herr != hipSuccess) {
-            set_error("hipFuncSetAttribute(qh_bwd): %s", hipGetErrorString(herr));
-            return PRISM_ERR_HIP;
-        }
+        if (rc) return rc;
         PRISM_CHECK_LAUNCH();
     }
     if (!tail_fused(ld)) {
@@ -837,7 +777,6 @@ extern "C" int prism_act_forward(const prism_learner_desc *ld, const float *obs,
     hipStream_t stream = (hipStream_t)stream_;
     IqnArgs a;
     fill_iqn_args(ld, a);
-    hipError_t herr = hipSuccess;
     // embed (+ the parameter-only roles): the n observations stand in for both batch halves
     a.cos_tiles = 0;          // (acting tiles draw and evaluate their basis themselves: no learner passes here)
     a.B = n;
@@ -868,7 +807,7 @@ extern "C" int prism_act_forward(const prism_learner_desc *ld, const float *obs,
     a.act_rng = nullptr;
     a.tau_out = nullptr;
     a.local_loss = 0;
-    int np = 0, n_iqn = 0, n_q = 0;
+    int np = 0;
     IqnPass p;
     if (ld->dims.use_iqn) {
         memset(&p, 0, sizeof(p));
@@ -879,7 +818,7 @@ extern "C" int prism_act_forward(const prism_learner_desc *ld, const float *obs,
         p.tau_in = tau_in;
         p.z_out = out_z;
         p.T = n_tau;
-        p.n_tiles = n_iqn = (n * n_tau + 15) / 16;
+        p.n_tiles = (n * n_tau + 15) / 16;
         p.kind = 0;
         p.stream_id = 3;                 // a Philox stream of its own: acting draws never repeat an update's
         a.pass[np++] = p;
@@ -892,49 +831,14 @@ extern "C" int prism_act_forward(const prism_learner_desc *ld, const float *obs,
         p.e = a.ws.e_cur;
         p.z_out = out_q;
         p.T = 1;
-        p.n_tiles = n_q = (n_pad / 16) * ld->dims.n_heads;
+        p.n_tiles = (n_pad / 16) * ld->dims.n_heads;
         p.kind = 1;
         a.pass[np++] = p;
     }
     PRISM_CHECK_ARG(np > 0, "nothing to run");
-    auto launch = [&](const IqnArgs &aa, int H, int tiles) {
-        dispatch_hl(H, aa.ln, [&](auto h, auto l) {
-            constexpr int HH = decltype(h)::value;
-            constexpr bool LL = decltype(l)::value;
-            const size_t lds = fw_lds_floats<HH>() * sizeof(float);
-            if constexpr (HH == 128) {
-                if (aa.split && fwd_four_waves(aa, tiles)) {
-                    const size_t lds4 = fw_lds_floats<HH, 4>() * sizeof(float);
-                    herr = set_max_lds((const void *)fwd_tile_kernel<HH, LL, true, 4>, lds4);
-                    if (herr == hipSuccess)
-                        hipLaunchKernelGGL((fwd_tile_kernel<HH, LL, true, 4>), dim3(tiles), dim3(256), lds4, stream, aa);
-                    return;
-                }
-            }
-            if (aa.split) {
-                herr = set_max_lds((const void *)fwd_tile_kernel<HH, LL, true>, lds);
-                if (herr == hipSuccess)
-                    hipLaunchKernelGGL((fwd_tile_kernel<HH, LL, true>), dim3(tiles), dim3(fw_threads(HH)), lds, stream, aa);
-                return;
-            }
-            herr = set_max_lds((const void *)fwd_tile_kernel<HH, LL>, lds);
-            if (herr == hipSuccess) hipLaunchKernelGGL((fwd_tile_kernel<HH, LL>), dim3(tiles), dim3(fw_threads(HH)), lds, stream, aa);
-        });
-    };
     a.n_pass = np;
-    if (n_iqn && n_q && a.Hi != a.Hq) {
-        IqnArgs a1 = a, a2 = a;
-        a1.n_pass = a2.n_pass = 1;
-        a2.pass[0] = a.pass[1];
-        launch(a1, a.Hi, n_iqn);
-        launch(a2, a.Hq, n_q);
-    } else {
-        launch(a, n_iqn ? a.Hi : a.Hq, n_iqn + n_q);
-    }
-    if (herr != hipSuccess) {
-        set_error("hipFuncSetAttribute(fwd_tile): %s", hipGetErrorString(herr));
-        return PRISM_ERR_HIP;
-    }
+    rc = launch_fwd_tiles(a, stream);
+    if (rc) return rc;
     PRISM_CHECK_LAUNCH();
     return PRISM_OK;
 }
@@ -1096,13 +1000,7 @@ extern "C" int prism_step_back(const prism_learner_desc *ld, const prism_replay_
         rc = launch_post(ld, ia, &t, stream);
         if (rc) return rc;
         if (k.use_per) {          // prioritised replay that is not riding in the learner's launches: its own update
-            const int threads = ld->batch >= 1024 ? 1024 : ((ld->batch + 127) / 128) * 128;
-            if (tree_dense_ok(rp->tree_capacity, ld->batch, threads))
-                hipLaunchKernelGGL(per_update_kernel<true>, dim3(1), dim3(threads), 0, stream, *rp, index, ld->out_td, ld->batch,
-                                   alpha, eps, 1);
-            else
-                hipLaunchKernelGGL(per_update_kernel<false>, dim3(1), dim3(threads), 0, stream, *rp, index, ld->out_td, ld->batch,
-                                   alpha, eps, 1);
+            launch_per_update(*rp, index, ld->out_td, ld->batch, alpha, eps, 1, stream);
             PRISM_CHECK_LAUNCH();
         }
         return PRISM_OK;

@@ -108,15 +108,9 @@ extern "C" int prism_per_update(const prism_replay_desc *rp, const int64_t *inde
     int rc = check_replay(rp, true);
     if (rc) return rc;
     PRISM_CHECK_ARG(batch > 0 && index && priority, "batch/index/priority");
-    const int threads = batch >= 1024 ? 1024 : ((batch + 127) / 128) * 128;
     {
         ProfileScope ps_(K_PER_UPDATE, (hipStream_t)stream);
-        if (tree_dense_ok(rp->tree_capacity, batch, threads))
-            hipLaunchKernelGGL(per_update_kernel<true>, dim3(1), dim3(threads), 0, (hipStream_t)stream, *rp, index, priority, batch,
-                               alpha, eps, take_abs);
-        else
-            hipLaunchKernelGGL(per_update_kernel<false>, dim3(1), dim3(threads), 0, (hipStream_t)stream, *rp, index, priority,
-                               batch, alpha, eps, take_abs);
+        launch_per_update(*rp, index, priority, batch, alpha, eps, take_abs, (hipStream_t)stream);
         PRISM_CHECK_LAUNCH();
     }
     return PRISM_OK;

@@ -596,6 +596,16 @@ static __global__ __launch_bounds__(1024) void per_update_kernel(prism_replay_de
     per_update_block<false, DENSE>(rp, index, priority, n, alpha, eps, take_abs, s_pool);
 }
 
+// host: the priority update of `n` leaves as one workgroup (up to 1024 threads), dense where tree_dense_ok allows
+static inline void launch_per_update(const prism_replay_desc &rp, const int64_t *index, const float *priority, int n,
+                                     float alpha, float eps, int take_abs, hipStream_t stream) {
+    const int threads = n >= 1024 ? 1024 : ((n + 127) / 128) * 128;
+    if (tree_dense_ok(rp.tree_capacity, n, threads))
+        hipLaunchKernelGGL(per_update_kernel<true>, dim3(1), dim3(threads), 0, stream, rp, index, priority, n, alpha, eps, take_abs);
+    else
+        hipLaunchKernelGGL(per_update_kernel<false>, dim3(1), dim3(threads), 0, stream, rp, index, priority, n, alpha, eps, take_abs);
+}
+
 // rows of an insert batch -> ring slots (any number of workgroups)
 static __global__ void replay_store_rows_kernel(prism_replay_desc rp, int n, const int32_t *__restrict__ slots,
                                          const float *__restrict__ obs, const float *__restrict__ succ_obs,

@@ -1,5 +1,6 @@
 """Diagnostic (GPU box): per-tensor gradient error of a golden case against the oracle, every step.
-usage: python tools/dbg_case.py <case> [gemm_mode]      (PRISM_NO_BWD4 / PRISM_NO_BWD3 / PRISM_GEMM select kernels)"""
+usage: python tools/dbg_case.py <case> [gemm_mode]      (PRISM_GEMM, or another build of the library
+       via PRISM_HIP_LIB, selects kernels)"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
