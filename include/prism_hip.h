@@ -203,9 +203,9 @@ typedef struct prism_learner_desc {
     float *params;
     const float *target_params; /* NULL when !has_target                                     */
     float *grads;             /* out: dL/dparams (unclipped, unscaled)                        */
-    float *adam_m;
-    float *adam_v;
-    int64_t *adam_step;       /* [1] device step counter, incremented by prism_learner_clip_adam */
+    float *adam_m;            /* Adam exp_avg    | RMSprop grad_avg   | SGD: unused, still a valid pointer (prism_opt_hyper) */
+    float *adam_v;            /* Adam exp_avg_sq | RMSprop square_avg | SGD: unused, still a valid pointer               */
+    int64_t *adam_step;       /* [1] device step counter, incremented by every optimizer step    */
     /* minibatch (the static batch of timestep_buffer.py:84-104) */
     const float *obs;         /* [B][10][10][C]                                               */
     const float *next_obs;
@@ -313,6 +313,44 @@ int prism_step_front(const prism_learner_desc *ld, const prism_replay_desc *rp, 
 /* prism_learner_clip_adam + prism_per_update(index, |ld->out_td|) in one launch. */
 int prism_step_back(const prism_learner_desc *ld, const prism_replay_desc *rp, const int64_t *index,
                     float alpha, float eps, prism_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The reference's other optimizers (prism/factory/agent_factory.py:40-58): torch.optim.RMSprop(lr, alpha, eps,
+ * centered=True) when use_adam is off and use_rmsprop on, torch.optim.SGD(lr) when both are off -- no momentum and no
+ * weight decay in either.  prism_adam_hyper and prism_learner_desc keep their layout: the optimizer kind and its own
+ * hyper-parameters arrive through the two calls below.  The clip (hyper.max_grad_norm) and hyper.grad_scale still come
+ * from ld->hyper.
+ *   PRISM_OPT_ADAM     exactly prism_learner_clip_adam / prism_step_back: every Adam hyper-parameter is read from
+ *                      ld->hyper, lr / alpha / eps of prism_opt_hyper are ignored; results are bit-identical
+ *   PRISM_OPT_RMSPROP  ld->adam_m holds grad_avg, ld->adam_v holds square_avg (torch's state names), float32 [n_params];
+ *                      torch/optim/rmsprop.py, _single_tensor_rmsprop, operation by operation in float32.  The radicand
+ *                      square_avg - grad_avg^2 is NOT clamped: where rounding leaves it negative the parameter becomes
+ *                      NaN, as in the reference
+ *   PRISM_OPT_SGD      params -= lr * grad; ld->adam_m / ld->adam_v are neither read nor written, but must still be
+ *                      valid 16-byte aligned pointers (the descriptor check is shared)
+ * Every kind advances ld->adam_step by one.  The fused tail is built for Adam only: with another kind ld->fuse_tail
+ * must be 0 (PRISM_ERR_UNSUPPORTED otherwise -- never a silent Adam step), in these calls AND in the
+ * prism_learner_fwd_bwd in front of them, which then reduces the gradient itself.
+ * ------------------------------------------------------------------------------------------ */
+#define PRISM_OPT_ADAM 0
+#define PRISM_OPT_RMSPROP 1
+#define PRISM_OPT_SGD 2
+
+typedef struct prism_opt_hyper {
+    int32_t kind;          /* PRISM_OPT_*                                                     */
+    double lr;             /* config.learning_rate                                            */
+    double alpha;          /* RMSprop: config.rmsprop_alpha (decay of both running averages)  */
+    double eps;            /* RMSprop: config.rmsprop_epsilon, added to the root              */
+} prism_opt_hyper;
+
+/* clip_grad_norm_(max_grad_norm) + optimizer.step() (agent.py:73-74) for the optimizer agent_factory.py:40-58 built:
+ * prism_learner_clip_adam with the per-element update of opt->kind; adam_step += 1. */
+int prism_learner_clip_step(const prism_learner_desc *ld, const prism_opt_hyper *opt, prism_stream_t stream);
+
+/* prism_learner_clip_step + prism_per_update(index, |ld->out_td|) in one launch: prism_step_back for the optimizer
+ * agent_factory.py:40-58 built (the tail of one Learner iteration, prism/learner.py:95-125). */
+int prism_step_back_opt(const prism_learner_desc *ld, const prism_opt_hyper *opt, const prism_replay_desc *rp,
+                        const int64_t *index, float alpha, float eps, prism_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Acting forward -- Agent.forward (prism/agents/agent.py:31-41): CompositeModel.forward(for_action=True)

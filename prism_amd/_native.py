@@ -57,6 +57,13 @@ class AdamHyper(ctypes.Structure):
                [(n, c_f32) for n in ("max_grad_norm", "grad_scale")]
 
 
+OPT_ADAM, OPT_RMSPROP, OPT_SGD = 0, 1, 2
+
+
+class OptHyper(ctypes.Structure):
+    _fields_ = [("kind", c_i32), ("lr", ctypes.c_double), ("alpha", ctypes.c_double), ("eps", ctypes.c_double)]
+
+
 class LearnerDesc(ctypes.Structure):
     _fields_ = [("dims", ModelDims), ("off", ParamOffsets), ("batch", c_i32), ("embed_done", c_i32),
                 ("params", c_vp), ("target_params", c_vp), ("grads", c_vp), ("adam_m", c_vp), ("adam_v", c_vp),
@@ -102,6 +109,8 @@ SIGNATURES = {
     "prism_learner_supported": (ctypes.c_int, [_P(ModelDims), c_i32]),
     "prism_learner_fwd_bwd": (ctypes.c_int, [_P(LearnerDesc), c_vp]),
     "prism_learner_clip_adam": (ctypes.c_int, [_P(LearnerDesc), c_vp]),
+    "prism_learner_clip_step": (ctypes.c_int, [_P(LearnerDesc), _P(OptHyper), c_vp]),
+    "prism_step_back_opt": (ctypes.c_int, [_P(LearnerDesc), _P(OptHyper), _P(ReplayDesc), c_vp, c_f32, c_f32, c_vp]),
     "prism_step_front": (ctypes.c_int, [_P(LearnerDesc), _P(ReplayDesc), c_i64, c_vp, c_u64, c_u64, c_f32, c_vp, c_vp,
                                          c_vp]),
     "prism_step_back": (ctypes.c_int, [_P(LearnerDesc), _P(ReplayDesc), c_vp, c_f32, c_f32, c_vp]),

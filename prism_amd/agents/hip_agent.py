@@ -1,11 +1,11 @@
 """``HipAgent`` — duck-types the reference ``Agent`` (``/root/reference/prism/agents/agent.py``)
 with the TD update running in the hand-written gfx950 kernels behind ``prism_learner_fwd_bwd`` /
-``prism_learner_clip_adam``.
+``prism_learner_clip_adam`` (``prism_learner_clip_step`` for RMSprop / SGD).
 
 Memory model: ONE flat fp32 parameter buffer per network in ``model.parameters()`` order
 (SURVEY.md Appendix B); every ``nn.Parameter`` of the container modules is a view into it, so
 ``state_dict()`` / checkpoints interchange with the reference while the kernels and the RCCL
-all-reduce see a single contiguous buffer.  Adam moments and the gradient are flat buffers too.
+all-reduce see a single contiguous buffer.  Optimizer state and the gradient are flat buffers too.
 
 Data-parallel: ``torch.distributed`` all-reduce (RCCL over xGMI) of the flat gradient sits
 between the two native calls; clip + Adam then run redundantly on every rank so replicas stay
@@ -40,25 +40,83 @@ def graph_capture(g, **kwargs):
             gc.enable()
 
 
-class HipAdam:
-    """Flat Adam state with a ``torch.optim.Adam``-compatible ``state_dict`` (the update itself is
-    the fused kernel).  Mirrors the options of agent_factory.py:44-47."""
+class HipOptimizer:
+    """Flat optimizer state behind a ``torch.optim`` ``state_dict`` (the update itself is the fused kernel): ``exp_avg``
+    style names per kind in the subclasses, ``buffers()`` = the two flat fp32 tensors ``prism_learner_desc.adam_m`` /
+    ``adam_v`` point at, ``step_t`` = the device step counter every kind advances.  One subclass per optimizer
+    agent_factory.py:40-58 builds."""
+    kind = None                   # PRISM_OPT_* (include/prism_hip.h)
+    state_names = ()              # torch's per-parameter state keys held in buffers()[0], buffers()[1]
 
-    def __init__(self, named_params, flat_params, lr, betas, eps):
+    def __init__(self, named_params, flat_params):
         self.names = [n for n, _ in named_params]
         self.shapes = [tuple(p.shape) for _, p in named_params]
         self.numels = [p.numel() for _, p in named_params]
         self.flat_params = flat_params
-        dev = flat_params.device
+        self.step_t = torch.zeros(1, dtype=torch.int64, device=flat_params.device)
+
+    def zero_grad(self, set_to_none=True):
+        pass
+
+    def buffers(self):
+        raise NotImplementedError
+
+    def native_hyper(self):
+        """``prism_opt_hyper`` of the current param group (None: Adam, whose hyper-parameters travel in
+        ``prism_learner_desc.hyper``)."""
+        return None
+
+    def hyper_key(self):
+        """Everything of the param group a captured launch bakes beyond ``prism_learner_desc.hyper`` (the step graph is
+        keyed by it; None: Adam)."""
+        return None
+
+    def state_dict(self):
+        state, off = {}, 0
+        step = float(self.step_t.item())
+        bufs = self.buffers()
+        for i, (n, shp) in enumerate(zip(self.numels, self.shapes)):
+            if step > 0 and self.state_names:
+                st = {"step": torch.tensor(step)}
+                for name, buf in zip(self.state_names, bufs):
+                    st[name] = buf[off:off + n].view(shp).clone()
+                state[i] = st
+            off += n
+        return {"state": state, "param_groups": [dict(g) for g in self.param_groups]}
+
+    def load_state_dict(self, sd, keys=()):
+        off, step = 0, 0
+        bufs = self.buffers()
+        for i, (n, shp) in enumerate(zip(self.numels, self.shapes)):
+            st = sd["state"].get(i)
+            if st is not None and self.state_names:
+                for name, buf in zip(self.state_names, bufs):
+                    buf[off:off + n].copy_(st[name].reshape(-1))
+                step = int(float(st["step"]))
+            off += n
+        if self.state_names:          # (SGD's files carry no step count: the counter stays where it is)
+            self.step_t.fill_(step)
+        if sd.get("param_groups"):
+            g = sd["param_groups"][0]
+            for k in keys:
+                if k in g:
+                    self.param_groups[0][k] = g[k]
+
+
+class HipAdam(HipOptimizer):
+    """``torch.optim.Adam``, options of agent_factory.py:44-47."""
+    kind = N.OPT_ADAM
+
+    def __init__(self, named_params, flat_params, lr, betas, eps):
+        super().__init__(named_params, flat_params)
         self.exp_avg = torch.zeros_like(flat_params)
         self.exp_avg_sq = torch.zeros_like(flat_params)
-        self.step_t = torch.zeros(1, dtype=torch.int64, device=dev)
         self.param_groups = [dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=0, amsgrad=False,
                                   maximize=False, foreach=None, capturable=False, differentiable=False,
                                   fused=None, params=list(range(len(self.names))))]
 
-    def zero_grad(self, set_to_none=True):
-        pass
+    def buffers(self):
+        return self.exp_avg, self.exp_avg_sq
 
     def state_dict(self):
         state, off = {}, 0
@@ -85,6 +143,83 @@ class HipAdam:
             for k in ("lr", "betas", "eps"):
                 if k in g:
                     self.param_groups[0][k] = g[k]
+
+
+def _torch_param_group(opt_cls, n_params, **kw):
+    """The param group the installed ``torch.optim`` class writes for these options (its own key set and defaults), with
+    the parameters numbered as its ``state_dict()`` numbers them."""
+    g = dict(opt_cls([torch.zeros(1)], **kw).param_groups[0])
+    g["params"] = list(range(n_params))
+    return g
+
+
+class HipRMSprop(HipOptimizer):
+    """``torch.optim.RMSprop(lr, alpha, eps, centered=True)`` (agent_factory.py:48-54): per-parameter ``step``,
+    ``square_avg``, ``grad_avg`` in torch's own layout."""
+    kind = N.OPT_RMSPROP
+    state_names = ("square_avg", "grad_avg")
+
+    def __init__(self, named_params, flat_params, lr, alpha, eps):
+        super().__init__(named_params, flat_params)
+        self.grad_avg = torch.zeros_like(flat_params)
+        self.square_avg = torch.zeros_like(flat_params)
+        self.param_groups = [_torch_param_group(torch.optim.RMSprop, len(self.names), lr=lr, alpha=alpha, eps=eps,
+                                                centered=True)]
+
+    def buffers(self):
+        return self.square_avg, self.grad_avg
+
+    def native_hyper(self):
+        g = self.param_groups[0]
+        return N.OptHyper(self.kind, float(g["lr"]), float(g["alpha"]), float(g["eps"]))
+
+    def hyper_key(self):
+        g = self.param_groups[0]
+        return ("rmsprop", g["lr"], g["alpha"], g["eps"])
+
+    def load_state_dict(self, sd):
+        g = (sd.get("param_groups") or [{}])[0]
+        if not g.get("centered", True) or g.get("momentum", 0) or g.get("weight_decay", 0):
+            raise ValueError("prism_amd: RMSprop state with centered=False, momentum or weight decay "
+                             "(the kernel implements the form agent_factory.py:48-54 builds)")
+        super().load_state_dict(sd, keys=("lr", "alpha", "eps"))
+
+
+class HipSGD(HipOptimizer):
+    """``torch.optim.SGD(lr)`` (agent_factory.py:56-58): no per-parameter state.  The two state pointers of the descriptor
+    must still be valid: one 16-byte block serves both."""
+    kind = N.OPT_SGD
+
+    def __init__(self, named_params, flat_params, lr):
+        super().__init__(named_params, flat_params)
+        self._unused = torch.zeros(4, dtype=torch.float32, device=flat_params.device)
+        self.param_groups = [_torch_param_group(torch.optim.SGD, len(self.names), lr=lr)]
+
+    def buffers(self):
+        return self._unused, self._unused
+
+    def native_hyper(self):
+        return N.OptHyper(self.kind, float(self.param_groups[0]["lr"]), 0.0, 0.0)
+
+    def hyper_key(self):
+        return ("sgd", self.param_groups[0]["lr"])
+
+    def load_state_dict(self, sd):
+        g = (sd.get("param_groups") or [{}])[0]
+        if g.get("momentum", 0) or g.get("weight_decay", 0) or g.get("nesterov", False):
+            raise ValueError("prism_amd: SGD state with momentum / weight decay (the kernel implements plain SGD)")
+        super().load_state_dict(sd, keys=("lr",))
+
+
+def build_optimizer(config, named_params, flat_params):
+    """The reference's three-way choice with its precedence (agent_factory.py:40-58): ``use_adam`` wins, then
+    ``use_rmsprop``, else SGD."""
+    if config.use_adam:
+        return HipAdam(named_params, flat_params, config.learning_rate, (config.adam_beta1, config.adam_beta2),
+                       config.adam_epsilon)
+    if config.use_rmsprop:
+        return HipRMSprop(named_params, flat_params, config.learning_rate, config.rmsprop_alpha, config.rmsprop_epsilon)
+    return HipSGD(named_params, flat_params, config.learning_rate)
 
 
 def _flatten_into(model, device):
@@ -228,8 +363,14 @@ class HipAgent:
         self.flat = _flatten_into(model, self.device)
         self.flat_target = _flatten_into(target_model, self.device) if target_model is not None else None
         self.grads = torch.zeros_like(self.flat)
-        self.optimizer = HipAdam(list(model.named_parameters()), self.flat, config.learning_rate,
-                                 (config.adam_beta1, config.adam_beta2), config.adam_epsilon)
+        self.optimizer = build_optimizer(config, list(model.named_parameters()), self.flat)
+        # Adam runs through prism_learner_clip_adam / prism_step_back; the other kinds through prism_learner_clip_step /
+        # prism_step_back_opt (config.optimizer_entry_points = True sends Adam through those too: same kernels, same bits)
+        self._opt_calls = self.optimizer.kind != N.OPT_ADAM or bool(getattr(config, "optimizer_entry_points", False))
+        # (every step passes through _set_hyper and the graph key: Adam's path there is one flag test longer than it was)
+        self._adam = self.optimizer.kind == N.OPT_ADAM
+        self._opt_hyper = N.OptHyper(N.OPT_ADAM, 0.0, 0.0, 0.0) if self._adam and self._opt_calls else None
+        self._opt_key = None          # the other kinds: what a captured launch bakes of their hyper-parameters
         self.dims = model_dims(config, in_channels, n_actions)
         self.off = _offsets(model)
         self.tau_rng = getattr(config, "tau_rng", "philox")
@@ -300,7 +441,12 @@ class HipAgent:
         d.gemm_mode = N.GEMM_MODES[str(getattr(self.config, "gemm_mode", "auto"))]      # "fp32" | "bf16x3" | "auto"
         d.params, d.grads = self.flat.data_ptr(), self.grads.data_ptr()
         d.target_params = self.flat_target.data_ptr() if self.flat_target is not None else None
-        d.adam_m, d.adam_v = self.optimizer.exp_avg.data_ptr(), self.optimizer.exp_avg_sq.data_ptr()
+        if self.optimizer.kind == N.OPT_ADAM:
+            d.adam_m, d.adam_v = self.optimizer.exp_avg.data_ptr(), self.optimizer.exp_avg_sq.data_ptr()
+        elif self.optimizer.kind == N.OPT_RMSPROP:          # (include/prism_hip.h: adam_m = grad_avg, adam_v = square_avg)
+            d.adam_m, d.adam_v = self.optimizer.grad_avg.data_ptr(), self.optimizer.square_avg.data_ptr()
+        else:
+            d.adam_m = d.adam_v = self.optimizer.buffers()[0].data_ptr()
         d.adam_step = self.optimizer.step_t.data_ptr()
         d.tau_out = self.tau_out.data_ptr()
         d.out_dist_loss, d.out_q_loss = self.out_dl.data_ptr(), self.out_ql.data_ptr()
@@ -310,14 +456,28 @@ class HipAgent:
         if self._direct is not None:      # a collective that gives up poisons THIS workspace's status word (no update applied)
             self._direct._desc.poison = self.workspace.data_ptr() + 4 * N.WS_STATUS_WORD
         self.rng_counters = torch.zeros(3, dtype=torch.int64, device=dev)     # {PER draws, tau draws, acting draws}
+        self._rng_ptr = self.rng_counters.data_ptr()
         self._act_graphs, self._act_ptrs, self._act_dev_draws, self._act_packed_at = {}, {}, 0, None
         self._desc, self._B = d, B
         self._graphs = {}
 
     def _set_hyper(self):
         g, h = self.optimizer.param_groups[0], self._desc.hyper
-        h.lr, h.beta1, h.beta2, h.eps = g["lr"], g["betas"][0], g["betas"][1], g["eps"]
+        if self._adam:
+            h.lr, h.beta1, h.beta2, h.eps = g["lr"], g["betas"][0], g["betas"][1], g["eps"]
+        else:
+            h.lr, h.beta1, h.beta2, h.eps = g["lr"], 0.0, 0.0, 0.0          # (the Adam fields are not read for this kind)
+            self._opt_hyper = self.optimizer.native_hyper()
+            self._opt_key = self.optimizer.hyper_key()
         h.max_grad_norm, h.grad_scale = self.max_grad_norm, 1.0 / self.world
+
+    def _clip_step(self, d):
+        """clip_grad_norm_ + optimizer.step() (agent.py:73-74) on the current stream."""
+        L, st = N.lib(), N.current_stream_handle()
+        if self._opt_calls:
+            N.check(L.prism_learner_clip_step(ctypes.byref(d), ctypes.byref(self._opt_hyper), st), "prism_learner_clip_step")
+        else:
+            N.check(L.prism_learner_clip_adam(ctypes.byref(d), st), "prism_learner_clip_adam")
 
     # ------------------------------------------------------------------ reference API
     def update(self, batch, per_weights=1, taus=None):
@@ -379,7 +539,7 @@ class HipAgent:
             N.check(L.prism_learner_fwd_bwd(ctypes.byref(d), N.current_stream_handle()), "prism_learner_fwd_bwd")
             if self.world > 1:
                 self._allreduce()
-            N.check(L.prism_learner_clip_adam(ctypes.byref(d), N.current_stream_handle()), "prism_learner_clip_adam")
+            self._clip_step(d)
         self._keep = keep
         self._static_total_loss = self.scalars[0]
         self._static_distribution_loss = self.out_dl if self.dims.use_iqn else None
@@ -413,7 +573,8 @@ class HipAgent:
         else:
             d.fused_replay = None
         # one GPU, whole step in one go: the gradient reduction rides in prism_step_back's launch (grid barrier)
-        d.fuse_tail = int(part == "all" and self.world == 1 and self.fuse_tail)
+        # (the fused tail is built for Adam only: the other optimizers run the post + back launch pair)
+        d.fuse_tail = int(part == "all" and self.world == 1 and self.fuse_tail and self._adam)
         if part in ("all", "front"):
             d.embed_done = 1
             N.check(L.prism_step_front(ctypes.byref(d), rp, buf._size, None, buf.seed, buf._draws,
@@ -424,8 +585,12 @@ class HipAgent:
         if part == "all" and self.world > 1:
             self._allreduce()
         if part in ("all", "back"):
-            N.check(L.prism_step_back(ctypes.byref(d), rp, N.ptr(buf._index), smp._alpha, smp._eps, st()),
-                    "prism_step_back")
+            if self._opt_calls:
+                N.check(L.prism_step_back_opt(ctypes.byref(d), ctypes.byref(self._opt_hyper), rp, N.ptr(buf._index), smp._alpha,
+                                              smp._eps, st()), "prism_step_back_opt")
+            else:
+                N.check(L.prism_step_back(ctypes.byref(d), rp, N.ptr(buf._index), smp._alpha, smp._eps, st()),
+                        "prism_step_back")
 
     def step_fused(self, buf, eager=False, use_graph=True):
         """Sample + update + priority writeback as four launches on one GPU, five around an all-reduce (prism_step_front, fwd_bwd,
@@ -437,7 +602,7 @@ class HipAgent:
             buf._alloc_batch(buf.buffer._batch_size)
         self.poll_status()
         d = self._bind_fused(buf)
-        d.rng_counters = self.rng_counters.data_ptr()
+        d.rng_counters = self._rng_ptr
         d.offset = self._draw_offset               # device counter + what update() has consumed: never the same draw twice
         graphable = use_graph and not eager and buf._size == buf.capacity
         with torch.cuda.device(self.device):
@@ -446,7 +611,7 @@ class HipAgent:
             else:
                 # a captured graph bakes every by-value launch argument: hyper-parameters, seeds, beta / alpha, offsets
                 h, smp = d.hyper, buf.buffer._sampler
-                key = (id(buf), buf._size, self.world, h.lr, h.beta1, h.beta2, h.eps, h.max_grad_norm, h.grad_scale,
+                key = (id(buf), buf._size, self.world, h.lr, h.beta1, h.beta2, h.eps, h.max_grad_norm, h.grad_scale, self._opt_key,
                        self.seed, buf.seed, smp._beta, smp._alpha, smp._eps, self._draw_offset, buf._draws,
                        self.overlap_writeback)
                 g = self._graphs.get(key)

@@ -1,5 +1,6 @@
-// TD update entry points: get_losses + backward (prism_learner_fwd_bwd), clip_grad_norm_ + Adam
-// (prism_learner_clip_adam), and the fused step front/back (prism_step_front / prism_step_back).
+// TD update entry points: get_losses + backward (prism_learner_fwd_bwd), clip_grad_norm_ + optimizer step
+// (prism_learner_clip_adam; prism_learner_clip_step for RMSprop / SGD), and the fused step front/back (prism_step_front /
+// prism_step_back, prism_step_back_opt).
 // Reference: /root/reference/prism/agents/models/composite_model.py:94-144,
 // prism/agents/agent.py:53-79, prism/learner.py:95-125.
 #include <math.h>
@@ -471,6 +472,28 @@ static void fill_adam_args(const prism_learner_desc *ld, const IqnWs &ws, AdamAr
     a.poison = ld->hyper.grad_scale != 1.0f ? ws.ticket + PRISM_WS_STATUS_WORD : nullptr;
 }
 
+// The optimizer of the new entry points (prism_learner_clip_step / prism_step_back_opt).  Refusals that need no device
+// come first: tests run them on machines without one.
+static int check_opt(const prism_learner_desc *ld, const prism_opt_hyper *opt) {
+    PRISM_CHECK_ARG(ld != nullptr, "null descriptor");
+    PRISM_CHECK_ARG(opt != nullptr, "null optimizer hyper-parameters");
+    PRISM_CHECK_ARG(opt->kind == PRISM_OPT_ADAM || opt->kind == PRISM_OPT_RMSPROP || opt->kind == PRISM_OPT_SGD,
+                    "optimizer kind must be PRISM_OPT_ADAM, PRISM_OPT_RMSPROP or PRISM_OPT_SGD");
+    if (opt->kind != PRISM_OPT_ADAM && ld->fuse_tail != 0) {
+        set_error("%s: the fused tail (fuse_tail != 0) is built for Adam only; pass fuse_tail = 0 with RMSprop / SGD", __func__);
+        return PRISM_ERR_UNSUPPORTED;
+    }
+    return PRISM_OK;
+}
+// (Adam keeps reading ld->hyper: the old and the new entry points then cannot disagree)
+static void apply_opt(const prism_opt_hyper *opt, AdamArgs &a) {
+    if (opt->kind == PRISM_OPT_ADAM) return;
+    a.lr = opt->lr;
+    a.b1 = 0.0;
+    a.b2 = opt->alpha;
+    a.eps = opt->eps;
+}
+
 // (one workgroup per CU -- every workgroup folds the norm partials itself before its first update, a fixed cost per workgroup:
 // measured on c4's 1.5 M parameters, clip + Adam + writeback: 2048 workgroups 25.5 us, 512: 15.5, 256: 13.4, 128: 15.4;
 // subtractive preset, 3.0 M: 33.8 / 20.7 / 18.8 / 23.8)
@@ -888,7 +911,7 @@ static int prepare_norm(const prism_learner_desc *ld, const IqnWs &ws, AdamArgs 
     return PRISM_OK;
 }
 
-extern "C" int prism_learner_clip_adam(const prism_learner_desc *ld, prism_stream_t stream_) {
+static int clip_step(const prism_learner_desc *ld, const prism_opt_hyper *opt, prism_stream_t stream_) {
     int rc = check_learner(ld);
     if (rc) return rc;
     hipStream_t stream = (hipStream_t)stream_;
@@ -896,14 +919,27 @@ extern "C" int prism_learner_clip_adam(const prism_learner_desc *ld, prism_strea
     carve_iqn(&ld->dims, ld->batch, ld->workspace, &ws, nullptr, nullptr);
     AdamArgs a;
     fill_adam_args(ld, ws, a);
+    const int kind = opt ? opt->kind : PRISM_OPT_ADAM;
+    if (opt) apply_opt(opt, a);
     rc = prepare_norm(ld, ws, a, stream);
     if (rc) return rc;
     {
         ProfileScope ps_(K_CLIP_ADAM, stream);
+        if (kind != PRISM_OPT_ADAM) return launch_clip_opt(kind, adam_blocks(a.n), stream, a);          // (opt_step.hip)
         hipLaunchKernelGGL(clip_adam_kernel, dim3(adam_blocks(a.n)), dim3(256), 0, stream, a);
         PRISM_CHECK_LAUNCH();
     }
     return PRISM_OK;
+}
+
+extern "C" int prism_learner_clip_adam(const prism_learner_desc *ld, prism_stream_t stream_) {
+    return clip_step(ld, nullptr, stream_);
+}
+
+extern "C" int prism_learner_clip_step(const prism_learner_desc *ld, const prism_opt_hyper *opt, prism_stream_t stream_) {
+    int rc = check_opt(ld, opt);
+    if (rc) return rc;
+    return clip_step(ld, opt, stream_);
 }
 
 static int check_replay_for_step(const prism_learner_desc *ld, const prism_replay_desc *rp) {
@@ -951,8 +987,8 @@ extern "C" int prism_step_front(const prism_learner_desc *ld, const prism_replay
     return PRISM_OK;
 }
 
-extern "C" int prism_step_back(const prism_learner_desc *ld, const prism_replay_desc *rp, const int64_t *index,
-                               float alpha, float eps, prism_stream_t stream_) {
+static int step_back(const prism_learner_desc *ld, const prism_opt_hyper *opt, const prism_replay_desc *rp, const int64_t *index,
+                     float alpha, float eps, prism_stream_t stream_) {
     int rc = check_learner(ld);
     if (rc) return rc;
     rc = check_replay_for_step(ld, rp);
@@ -963,6 +999,8 @@ extern "C" int prism_step_back(const prism_learner_desc *ld, const prism_replay_
     carve_iqn(&ld->dims, ld->batch, ld->workspace, &ws, nullptr, nullptr);
     AdamArgs a;
     fill_adam_args(ld, ws, a);
+    const int kind = opt ? opt->kind : PRISM_OPT_ADAM;
+    if (opt) apply_opt(opt, a);
     rc = prepare_norm(ld, ws, a, stream);
     if (rc) return rc;
     BackArgs k;
@@ -985,7 +1023,7 @@ extern "C" int prism_step_back(const prism_learner_desc *ld, const prism_replay_
     const int maxT = ld->dims.n_tau > ld->dims.n_tau_next ? ld->dims.n_tau : ld->dims.n_tau_next;
     k.inc_per = (uint64_t)ld->batch;
     k.inc_tau = (uint64_t)3 * maxT * ld->batch;
-    if (tail_fused(ld)) {
+    if (kind == PRISM_OPT_ADAM && tail_fused(ld)) {          // (check_opt refused fuse_tail with the other kinds)
         // single GPU: gradient reduction + clip + Adam + writeback in one launch
         IqnArgs ia;
         fill_iqn_args(ld, ia);
@@ -1007,8 +1045,21 @@ extern "C" int prism_step_back(const prism_learner_desc *ld, const prism_replay_
     }
     {
         ProfileScope ps_(K_BACK, stream);
+        if (kind != PRISM_OPT_ADAM) return launch_step_back_opt(kind, adam_blocks(a.n), stream, a, *rp, k);          // (opt_step.hip)
         hipLaunchKernelGGL(step_back_kernel, dim3(1 + adam_blocks(a.n)), dim3(256), 0, stream, a, *rp, k);
         PRISM_CHECK_LAUNCH();
     }
     return PRISM_OK;
+}
+
+extern "C" int prism_step_back(const prism_learner_desc *ld, const prism_replay_desc *rp, const int64_t *index,
+                               float alpha, float eps, prism_stream_t stream_) {
+    return step_back(ld, nullptr, rp, index, alpha, eps, stream_);
+}
+
+extern "C" int prism_step_back_opt(const prism_learner_desc *ld, const prism_opt_hyper *opt, const prism_replay_desc *rp,
+                                   const int64_t *index, float alpha, float eps, prism_stream_t stream_) {
+    int rc = check_opt(ld, opt);
+    if (rc) return rc;
+    return step_back(ld, opt, rp, index, alpha, eps, stream_);
 }

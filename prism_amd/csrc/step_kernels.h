@@ -7,6 +7,7 @@
 #include "iqn_kernels.h"
 #include "qhead_kernels.h"
 #include "replay_kernels.h"
+#include "opt_kernels.h"
 
 namespace prism {
 
@@ -472,112 +473,7 @@ __device__ __forceinline__ float block_sum_1024(float v, float *s_red) {
     return t;   // valid in thread 0
 }
 
-// ---- global-norm clip + Adam over the flat buffers ---------------------------------------------
-struct AdamArgs {
-    float *p;
-    const float *g;
-    float *m, *v;
-    int64_t n;
-    int64_t *step;
-    const float *normpart;
-    int n_slots;
-    double lr, b1, b2, eps;
-    float max_norm, grad_scale;
-    float *out_scalars;
-    unsigned int *ticket;
-    const unsigned int *poison;    // data parallel: the workspace status word (PRISM_WS_STATUS_COLLECTIVE_TIMEOUT), else NULL
-};
-
-// One NT-thread block of the clip + Adam update (block `blk` of `nblk`).  The operands of the block's first
-// float4 per thread are requested BEFORE the norm is folded: the fold's own loads and two barriers then ride on the
-// same memory round trip.  The fold itself is always the 256-lane form (strided partial sums, LDS tree), whatever NT:
-// every launch shape arrives at the same bits for the norm.
-template <int NT>
-__device__ __forceinline__ void clip_adam_block(const AdamArgs &a, int blk, int nblk) {
-    __shared__ float s_red[256];
-    __shared__ float s_c[4];     // clip coef, -step_size, sqrt(bias_correction2)
-    const int tid = threadIdx.x;
-    // the all-reduce in front of this launch gave up on a peer (direct.hip): the gradient is not a sum over all ranks --
-    // apply NOTHING (uniform over the grid: every block reads the same sticky word; the host raises at its next poll)
-    if (a.poison && (__hip_atomic_load(a.poison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & PRISM_WS_STATUS_COLLECTIVE_TIMEOUT)) return;
-    const int64_t nvec = a.n >> 2;
-    const int64_t i0 = (int64_t)blk * NT + tid;
-    float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), p0 = g0, m0 = g0, v0 = g0;
-    if (i0 < nvec) {
-        g0 = reinterpret_cast<const float4 *>(a.g)[i0];
-        p0 = reinterpret_cast<const float4 *>(a.p)[i0];
-        m0 = reinterpret_cast<const float4 *>(a.m)[i0];
-        v0 = reinterpret_cast<const float4 *>(a.v)[i0];
-    }
-    // every block folds the same partials in the same order -> identical norm everywhere
-    if (tid < 256) {
-        float s = 0.f;
-#pragma unroll 4
-        for (int i = tid; i < a.n_slots; i += 256) s += a.normpart[i];
-        s_red[tid] = s;
-    }
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) s_red[tid] += s_red[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const float total = sqrtf(s_red[0]);
-        float coef = a.max_norm / (total + 1e-6f);   // torch.nn.utils.clip_grad_norm_
-        coef = fminf(coef, 1.0f);
-        // torch.optim.Adam (_single_tensor_adam): bias corrections in float64 from the step count
-        const double t = (double)(a.step[0] + 1);
-        const double bc1 = 1.0 - pow(a.b1, t), bc2 = 1.0 - pow(a.b2, t);
-        s_c[0] = coef;
-        s_c[1] = (float)(-(a.lr / bc1));
-        s_c[2] = (float)sqrt(bc2);
-        if (blk == 0) {
-            a.out_scalars[3] = total;
-            a.out_scalars[5] = coef;
-        }
-    }
-    __syncthreads();
-    const float coef = s_c[0], neg_step = s_c[1], bc2s = s_c[2];
-    const float w1 = (float)(1.0 - a.b1), b2f = (float)a.b2, w2 = (float)(1.0 - a.b2), epsf = (float)a.eps;
-    const float gs = a.grad_scale;
-    auto upd = [&](float g_, float &p, float &m, float &v) {
-        const float g = (g_ * gs) * coef;
-        m = fmaf(w1, g - m, m);                 // exp_avg.lerp_(grad, 1 - beta1)
-        v = v * b2f + (w2 * g) * g;             // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1-beta2)
-        const float denom = sqrtf(v) / bc2s + epsf;
-        p = p + (neg_step * m) / denom;         // param.addcdiv_(exp_avg, denom, value=-step_size)
-    };
-    auto upd4 = [&](int64_t i, const float4 &g, float4 p, float4 m, float4 v) {
-        upd(g.x, p.x, m.x, v.x);
-        upd(g.y, p.y, m.y, v.y);
-        upd(g.z, p.z, m.z, v.z);
-        upd(g.w, p.w, m.w, v.w);
-        stream_store4(reinterpret_cast<float4 *>(a.p) + i, p);
-        stream_store4(reinterpret_cast<float4 *>(a.m) + i, m);
-        stream_store4(reinterpret_cast<float4 *>(a.v) + i, v);
-    };
-    if (i0 < nvec) upd4(i0, g0, p0, m0, v0);
-    for (int64_t i = i0 + (int64_t)nblk * NT; i < nvec; i += (int64_t)nblk * NT)
-        upd4(i, reinterpret_cast<const float4 *>(a.g)[i], reinterpret_cast<float4 *>(a.p)[i],
-             reinterpret_cast<float4 *>(a.m)[i], reinterpret_cast<float4 *>(a.v)[i]);
-    if (blk == 0 && tid < (int)(a.n & 3)) {
-        const int64_t i = (nvec << 2) + tid;
-        float p = a.p[i], m = a.m[i], v = a.v[i];
-        upd(a.g[i], p, m, v);
-        a.p[i] = p;
-        a.m[i] = m;
-        a.v[i] = v;
-    }
-    // the block that finishes last advances the step counter (every block has read it by then)
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned int done = atomicAdd(a.ticket, 1u);
-        if (done == (unsigned)(nblk - 1)) {
-            a.step[0] = a.step[0] + 1;
-            *a.ticket = 0u;
-        }
-    }
-}
+// (the global-norm clip + optimizer step over the flat buffers: opt_kernels.h)
 
 // Grid-wide barrier for a launch whose workgroups are ALL resident at once (the host checks the occupancy of the very
 // instantiation it launches, per device, before it picks a kernel that calls this), in two halves so that the caller can
@@ -1130,21 +1026,5 @@ __global__ __launch_bounds__(1024) void iqn_post_kernel(IqnArgs a, PostWriteback
         PRISM_STAMP(9);
     }
 }
-
-// ------------------------------------------------------------------------------------------
-// back: block 0 = priority writeback (+ RNG counters); blocks [1, 1 + n_adam) = clip + Adam.
-// ------------------------------------------------------------------------------------------
-struct BackArgs {
-    const int64_t *index;
-    const float *priority;
-    int n;
-    float alpha, eps;
-    int take_abs, use_per;
-    const int4 *plan;          // non-NULL: the post kernel prepared this writeback; finish it here
-    const float2 *sib;
-    unsigned int *sib_state;
-    uint64_t *rng;
-    uint64_t inc_per, inc_tau;
-};
 
 }  // namespace prism

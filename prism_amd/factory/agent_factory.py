@@ -1,8 +1,9 @@
 """``build_agent(config, obs_shape, n_actions)`` — mirrors
 ``/root/reference/prism/factory/agent_factory.py:7-61``: online model, optional target model
 (constructed second so it advances the torch RNG exactly as the reference does, then overwritten
-with the online weights), action selectors, Adam.  RMSprop / SGD are not implemented in the fused
-optimizer kernel and fail loudly."""
+with the online weights), action selectors, and the optimizer of the reference's three-way choice
+(agent_factory.py:40-58: ``use_adam`` wins, then ``use_rmsprop``, else SGD), which ``HipAgent`` builds over its
+flat parameter buffer (``hip_agent.build_optimizer``)."""
 from prism_amd.agents import action_selectors
 from prism_amd.agents.hip_agent import HipAgent
 from prism_amd.factory import model_factory
@@ -30,7 +31,5 @@ def build_agent(config, obs_shape, n_actions, process_group=None):
                                                           config.e_greedy_decay_timesteps, config.seed)
     else:
         selector = action_selectors.GreedyActionSelector()
-    if not config.use_adam:
-        raise model_factory.UnsupportedConfig("prism_amd: only Adam is implemented in the fused optimizer kernel")
     return HipAgent(model, selector, eval_selector, target_model, config, obs_shape[-1], n_actions,
                     process_group=process_group)

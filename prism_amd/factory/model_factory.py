@@ -30,8 +30,6 @@ def check_supported(config):
         bad.append("sparse_init_p != 0")
     if config.frame_stack_size != 1:
         bad.append("frame_stack_size != 1")
-    if not config.use_adam:
-        bad.append("optimizer other than Adam")
     if config.use_c51:
         bad.append("use_c51 (empty in the reference too)")
     if not (config.use_iqn or config.use_ids or config.use_dqn):

@@ -112,6 +112,14 @@ CASES = {
     "full_olf": (dict(use_ids=True, use_iqn=True, use_target_network=True, loss_squish_fn_id="obs_look_further"), 16, 2, False),
     "dqn_symlog": (dict(use_ids=False, use_iqn=False, use_dqn=True, use_layer_norm=False, loss_squish_fn_id="symlog"),
                    32, 2, False),
+    # ---- the optimizers beside Adam (agent_factory.py:48-58): centered RMSprop (use_adam off, use_rmsprop on), plain SGD
+    "dqn_c2_rmsprop": (dict(use_ids=False, use_iqn=False, use_dqn=True, use_layer_norm=False, use_adam=False,
+                            use_rmsprop=True), 256, 3, True),
+    "iqn_c3_rmsprop": (dict(use_ids=False, use_iqn=True, use_dqn=False, use_adam=False, use_rmsprop=True), 256, 3, False),
+    "abl_ln_notarget_rmsprop": (dict(base="additive", use_layer_norm=True, use_target_network=False, use_adam=False,
+                                     use_rmsprop=True), 64, 2, False),
+    "full_small_sgd": (dict(use_ids=True, use_iqn=True, use_target_network=True, use_adam=False, use_rmsprop=False),
+                       16, 2, False),
 }
 
 
@@ -379,15 +387,51 @@ def gen_checkpoint():
     print("ref_checkpoint:", sorted(os.listdir(os.path.join(ck, "agent"))))
 
 
+def gen_checkpoint_rmsprop():
+    """The same for the centered-RMSprop optimizer (agent_factory.py:48-54): the DQN model of case dqn_c2 after two
+    updates, with per-tensor sums of the parameters and of the optimizer state torch wrote."""
+    import shutil
+    from prism.config import Config, MINATAR_CONFIG
+    from prism.factory import agent_factory
+    cfg = Config(**MINATAR_CONFIG.__dict__)
+    cfg.device, cfg.use_cuda_graph, cfg.use_e_greedy = "cpu", False, False
+    for k, v in CASES["dqn_c2_rmsprop"][0].items():
+        setattr(cfg, k, v)
+    torch.manual_seed(cfg.seed)
+    with contextlib.redirect_stdout(io.StringIO()):
+        agent = agent_factory.build_agent(cfg, (10, 10, 4), 6)
+    rng = np.random.default_rng(199)
+    for _ in range(2):
+        b = synth_batch(rng, 32)
+        agent.update(to_ref_batch(b), per_weights=torch.from_numpy(b["w"]))
+    ck = os.path.join(OUT, "ref_checkpoint_rmsprop")
+    shutil.rmtree(ck, ignore_errors=True)
+    agent.save(ck)
+    names, s, l2 = tensor_stats(agent.model.state_dict())
+    opt = agent.optimizer.state_dict()
+    n = len(names)
+    np.savez_compressed(os.path.join(OUT, "ref_checkpoint_rmsprop_expected.npz"), param_names=np.array(names), sum=s, l2=l2,
+                        n_updates=agent.n_updates, max_grad_norm=agent.max_grad_norm,
+                        step=float(opt["state"][0]["step"]),
+                        square_avg_sum=np.array([float(opt["state"][i]["square_avg"].double().sum()) for i in range(n)]),
+                        grad_avg_sum=np.array([float(opt["state"][i]["grad_avg"].double().sum()) for i in range(n)]),
+                        group_keys=np.array(sorted(k for k in opt["param_groups"][0] if k != "params")),
+                        lr=opt["param_groups"][0]["lr"], alpha=opt["param_groups"][0]["alpha"],
+                        eps=opt["param_groups"][0]["eps"])
+    print("ref_checkpoint_rmsprop:", sorted(os.listdir(os.path.join(ck, "agent"))))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     _import_reference()
-    which = sys.argv[1:] or (list(CASES) + ["nstep", "config", "checkpoint"])
+    which = sys.argv[1:] or (list(CASES) + ["nstep", "config", "checkpoint", "checkpoint_rmsprop"])
     for name in which:
         if name == "nstep":
             gen_nstep()
         elif name == "checkpoint":
             gen_checkpoint()
+        elif name == "checkpoint_rmsprop":
+            gen_checkpoint_rmsprop()
         elif name == "config":
             gen_config_snapshot()
         else:
