@@ -715,11 +715,21 @@ class HipAgent:
         if taus is None and dm.use_iqn and self.tau_rng == "torch":
             taus = torch.rand([T * n, 1], device=self.device)
         tau = None if taus is None else taus.to(self.device, torch.float32).reshape(-1).contiguous()
-        with torch.cuda.device(self.device):
-            N.check(N.lib().prism_act_forward(ctypes.byref(self._desc), N.ptr(obs), n, T, N.ptr(tau) if tau is not None else None,
-                                              self.seed, self._act_draws, N.ptr(z) if z is not None else None,
-                                              N.ptr(qb) if qb is not None else None, N.current_stream_handle()),
-                    "prism_act_forward")
+        # This call draws at the HOST's acting count.  A fused step leaves the descriptor pointing at the device counters
+        # (step_fused), and with them set prism_act_forward would add rng_counters[2] to the offset and advance it: that word
+        # belongs to the graph path (_forward_graph), which seeds it from _act_draws whenever an eager call has moved the
+        # count on.  The packed weight copies are rebuilt here as well (act_flags = 0).
+        d = self._desc
+        keep = d.rng_counters, d.act_flags
+        d.rng_counters, d.act_flags = None, 0
+        try:
+            with torch.cuda.device(self.device):
+                N.check(N.lib().prism_act_forward(ctypes.byref(d), N.ptr(obs), n, T, N.ptr(tau) if tau is not None else None,
+                                                  self.seed, self._act_draws, N.ptr(z) if z is not None else None,
+                                                  N.ptr(qb) if qb is not None else None, N.current_stream_handle()),
+                        "prism_act_forward")
+        finally:
+            d.rng_counters, d.act_flags = keep
         self._act_draws += T * n
         self._act_raw = (z, qb, n, n_pad, T)
         dist = z[:n * T].view(n, T, A).permute(1, 0, 2) if z is not None else None

@@ -135,6 +135,45 @@ def philox4x32(seed, ctr, stream):
     return np.stack([c0, c1, c2, c3], axis=1).astype(np.uint32)
 
 
+TAU_KEY = 0x54415530          # "TAU0": the quantile-sample streams are keyed TAU_KEY + stream id
+TAU_CUR, TAU_NEXT_ONLINE, TAU_NEXT_TARGET, TAU_ACT = 0, 1, 2, 3
+
+
+def u32_to_unit_float(x):
+    """common.h::u32_to_unit_float: the top 24 bits of a word as a float32 in [0, 1) (every step exact in float32)."""
+    return (np.asarray(x, dtype=np.uint32) >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+
+
+def philox_taus(seed, offset, T, B, sid):
+    """The IQN quantile samples every drawing site must produce (step_kernels.h cos_basis_block, fwd_kernels.h both tile
+    prologues): float32[T * B], tau-major as the reference's ``torch.rand([T * B, 1])`` is read (iqn_model.py:66-68),
+
+        tau[t * B + b] = float32(Philox(seed, offset + t * B + b, TAU_KEY + sid)[0] >> 8) * 2**-24
+
+    sid: 0 current state, 1 next state on the online network, 2 next state on the target network, 3 acting."""
+    r = philox4x32(seed, np.uint64(offset) + np.arange(int(T) * int(B), dtype=np.uint64), TAU_KEY + int(sid))
+    return u32_to_unit_float(r[:, 0])
+
+
+def tau_streams(cfg):
+    """Stream ids an update of this configuration draws, in the order ``taus`` lists them for the oracle
+    (learner.hip fill_iqn_args; iqn_model.py:104,112-126)."""
+    if not cfg.use_iqn:
+        return []
+    sids = [TAU_CUR]
+    if not cfg.use_target_network or cfg.use_double_q_learning:
+        sids.append(TAU_NEXT_ONLINE)
+    if cfg.use_target_network:
+        sids.append(TAU_NEXT_TARGET)
+    return sids
+
+
+def tau_span(cfg, B):
+    """Counters one update consumes of the learner's one counter space, whichever path ran it (hip_agent.py update /
+    step_fused): three streams' worth of max(T, T') * B, whether or not the configuration draws all three."""
+    return 3 * max(cfg.iqn_n_current_state_quantile_samples, cfg.iqn_n_next_state_quantile_samples) * int(B)
+
+
 def philox_per_mass(seed, offset, batch, p_sum):
     """The masses step_front_kernel / per_sample_kernel draw: U(0, p_sum) in float64 (53 random bits, as numpy's
     random_sample), narrowed to fp32 (replay_kernels.h, key "PERM")."""

@@ -155,6 +155,12 @@ def test_philox_taus_are_uniform_and_recorded(dev):
     B, T = int(g["B"]), 8
     cur = t1[0, :T * B].cpu().numpy()
     assert 0.0 <= cur.min() and cur.max() < 1.0 and abs(cur.mean() - 0.5) < 0.03
+    # ... and are, bit for bit, the host's restatement of the two streams this configuration draws (no target network:
+    # current state and next state on the online network) at the first update's counters; stream 2 is drawn by nobody
+    span = H.tau_span(cfg, B)
+    for sid in (H.TAU_CUR, H.TAU_NEXT_ONLINE):
+        np.testing.assert_array_equal(t1[sid, :T * B].cpu().numpy(), H.philox_taus(agent.seed, 0, T, B, sid))
+    assert not t1[H.TAU_NEXT_TARGET].any()
     # replaying the recorded taus through the oracle reproduces the in-kernel-RNG step
     from oracle.learner_ref import LearnerOracle
     cpu_cfg = H.case_config(g)
@@ -165,6 +171,8 @@ def test_philox_taus_are_uniform_and_recorded(dev):
     np.testing.assert_allclose(td1.cpu().numpy(), td_o.numpy(), rtol=0, atol=LOSS_TOL)
     agent.update(hb, per_weights=w.to(dev))
     assert not torch.equal(agent.tau_out, t1)          # fresh draws every step
+    for sid in (H.TAU_CUR, H.TAU_NEXT_ONLINE):         # ... namely the next 3 * max(T, T') * B counters' (tests/test_gpu_rng_streams.py)
+        np.testing.assert_array_equal(agent.tau_out[sid, :T * B].cpu().numpy(), H.philox_taus(agent.seed, span, T, B, sid))
 
 
 def test_unsupported_config_fails_loudly(dev):
