@@ -42,9 +42,9 @@ def graph_capture(g, **kwargs):
 
 class HipOptimizer:
     """Flat optimizer state behind a ``torch.optim`` ``state_dict`` (the update itself is the fused kernel): ``exp_avg``
-    style names per kind in the subclasses, ``buffers()`` = the two flat fp32 tensors ``prism_learner_desc.adam_m`` /
-    ``adam_v`` point at, ``step_t`` = the device step counter every kind advances.  One subclass per optimizer
-    agent_factory.py:40-58 builds."""
+    style names per kind in the subclasses, ``buffers()`` = the flat fp32 tensors that hold them, ``native_buffers()`` = the
+    two ``prism_learner_desc.adam_m`` / ``adam_v`` point at, ``step_t`` = the device step counter every kind advances.  One
+    subclass per optimizer agent_factory.py:40-58 builds."""
     kind = None                   # PRISM_OPT_* (include/prism_hip.h)
     state_names = ()              # torch's per-parameter state keys held in buffers()[0], buffers()[1]
 
@@ -60,6 +60,11 @@ class HipOptimizer:
 
     def buffers(self):
         raise NotImplementedError
+
+    def native_buffers(self):
+        """What ``prism_learner_desc.adam_m`` / ``adam_v`` point at (include/prism_hip.h: first and second moment; both
+        must be valid pointers for every kind)."""
+        return self.buffers()
 
     def native_hyper(self):
         """``prism_opt_hyper`` of the current param group (None: Adam, whose hyper-parameters travel in
@@ -106,6 +111,7 @@ class HipOptimizer:
 class HipAdam(HipOptimizer):
     """``torch.optim.Adam``, options of agent_factory.py:44-47."""
     kind = N.OPT_ADAM
+    state_names = ("exp_avg", "exp_avg_sq")
 
     def __init__(self, named_params, flat_params, lr, betas, eps):
         super().__init__(named_params, flat_params)
@@ -118,31 +124,8 @@ class HipAdam(HipOptimizer):
     def buffers(self):
         return self.exp_avg, self.exp_avg_sq
 
-    def state_dict(self):
-        state, off = {}, 0
-        step = float(self.step_t.item())
-        for i, (n, shp) in enumerate(zip(self.numels, self.shapes)):
-            if step > 0:
-                state[i] = {"step": torch.tensor(step), "exp_avg": self.exp_avg[off:off + n].view(shp).clone(),
-                            "exp_avg_sq": self.exp_avg_sq[off:off + n].view(shp).clone()}
-            off += n
-        return {"state": state, "param_groups": [dict(g) for g in self.param_groups]}
-
     def load_state_dict(self, sd):
-        off, step = 0, 0
-        for i, (n, shp) in enumerate(zip(self.numels, self.shapes)):
-            st = sd["state"].get(i)
-            if st is not None:
-                self.exp_avg[off:off + n].copy_(st["exp_avg"].reshape(-1))
-                self.exp_avg_sq[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
-                step = int(float(st["step"]))
-            off += n
-        self.step_t.fill_(step)
-        if sd.get("param_groups"):
-            g = sd["param_groups"][0]
-            for k in ("lr", "betas", "eps"):
-                if k in g:
-                    self.param_groups[0][k] = g[k]
+        super().load_state_dict(sd, keys=("lr", "betas", "eps"))
 
 
 def _torch_param_group(opt_cls, n_params, **kw):
@@ -168,6 +151,9 @@ class HipRMSprop(HipOptimizer):
 
     def buffers(self):
         return self.square_avg, self.grad_avg
+
+    def native_buffers(self):
+        return self.grad_avg, self.square_avg
 
     def native_hyper(self):
         g = self.param_groups[0]
@@ -367,12 +353,18 @@ class HipAgent:
         # Adam runs through prism_learner_clip_adam / prism_step_back; the other kinds through prism_learner_clip_step /
         # prism_step_back_opt (config.optimizer_entry_points = True sends Adam through those too: same kernels, same bits)
         self._opt_calls = self.optimizer.kind != N.OPT_ADAM or bool(getattr(config, "optimizer_entry_points", False))
-        # (every step passes through _set_hyper and the graph key: Adam's path there is one flag test longer than it was)
-        self._adam = self.optimizer.kind == N.OPT_ADAM
-        self._opt_hyper = N.OptHyper(N.OPT_ADAM, 0.0, 0.0, 0.0) if self._adam and self._opt_calls else None
-        self._opt_key = None          # the other kinds: what a captured launch bakes of their hyper-parameters
+        # what a captured launch bakes of the hyper-parameters beyond prism_learner_desc.hyper.  None IS "the optimizer is
+        # Adam" to the per-step code (_set_hyper, which renews it and _opt_hyper for the other kinds; one attribute to read)
+        self._opt_key = self.optimizer.hyper_key()
+        assert (self._opt_key is None) == (self.optimizer.kind == N.OPT_ADAM)
+        # (Adam through the general entry points: the kind alone, its hyper-parameters stay in prism_learner_desc.hyper)
+        self._opt_hyper = self.optimizer.native_hyper()
+        if self._opt_hyper is None and self._opt_calls:
+            self._opt_hyper = N.OptHyper(N.OPT_ADAM, 0.0, 0.0, 0.0)
         self.dims = model_dims(config, in_channels, n_actions)
         self.off = _offsets(model)
+        # prism_act_forward fills a Q-value array: two-layer heads (forward tiles) or single-Linear heads (a workgroup per row)
+        self._act_q = self.dims.n_heads > 0 and self.dims.head_layers in (1, 2)
         self.tau_rng = getattr(config, "tau_rng", "philox")
         self.overlap_writeback = bool(getattr(config, "overlap_writeback", True))
         self.seed = int(config.seed)
@@ -441,12 +433,7 @@ class HipAgent:
         d.gemm_mode = N.GEMM_MODES[str(getattr(self.config, "gemm_mode", "auto"))]      # "fp32" | "bf16x3" | "auto"
         d.params, d.grads = self.flat.data_ptr(), self.grads.data_ptr()
         d.target_params = self.flat_target.data_ptr() if self.flat_target is not None else None
-        if self.optimizer.kind == N.OPT_ADAM:
-            d.adam_m, d.adam_v = self.optimizer.exp_avg.data_ptr(), self.optimizer.exp_avg_sq.data_ptr()
-        elif self.optimizer.kind == N.OPT_RMSPROP:          # (include/prism_hip.h: adam_m = grad_avg, adam_v = square_avg)
-            d.adam_m, d.adam_v = self.optimizer.grad_avg.data_ptr(), self.optimizer.square_avg.data_ptr()
-        else:
-            d.adam_m = d.adam_v = self.optimizer.buffers()[0].data_ptr()
+        d.adam_m, d.adam_v = [t.data_ptr() for t in self.optimizer.native_buffers()]
         d.adam_step = self.optimizer.step_t.data_ptr()
         d.tau_out = self.tau_out.data_ptr()
         d.out_dist_loss, d.out_q_loss = self.out_dl.data_ptr(), self.out_ql.data_ptr()
@@ -458,12 +445,14 @@ class HipAgent:
         self.rng_counters = torch.zeros(3, dtype=torch.int64, device=dev)     # {PER draws, tau draws, acting draws}
         self._rng_ptr = self.rng_counters.data_ptr()
         self._act_graphs, self._act_ptrs, self._act_dev_draws, self._act_packed_at = {}, {}, 0, None
+        # observations one prism_act_forward takes: what the workspace holds, in whole 16-row tiles for two-layer Q heads
+        self._act_cap = (B // 16) * 16 if self.dims.n_heads > 0 and self.dims.head_layers == 2 else B
         self._desc, self._B = d, B
         self._graphs = {}
 
     def _set_hyper(self):
         g, h = self.optimizer.param_groups[0], self._desc.hyper
-        if self._adam:
+        if self._opt_key is None:
             h.lr, h.beta1, h.beta2, h.eps = g["lr"], g["betas"][0], g["betas"][1], g["eps"]
         else:
             h.lr, h.beta1, h.beta2, h.eps = g["lr"], 0.0, 0.0, 0.0          # (the Adam fields are not read for this kind)
@@ -541,6 +530,10 @@ class HipAgent:
                 self._allreduce()
             self._clip_step(d)
         self._keep = keep
+        return self._step_done()
+
+    def _step_done(self):
+        """What ``update()`` and ``step_fused()`` leave behind for ``log()`` and hand back: the TD errors."""
         self._static_total_loss = self.scalars[0]
         self._static_distribution_loss = self.out_dl if self.dims.use_iqn else None
         self._static_q_loss = self.out_ql if self.dims.n_heads > 0 else None
@@ -574,7 +567,7 @@ class HipAgent:
             d.fused_replay = None
         # one GPU, whole step in one go: the gradient reduction rides in prism_step_back's launch (grid barrier)
         # (the fused tail is built for Adam only: the other optimizers run the post + back launch pair)
-        d.fuse_tail = int(part == "all" and self.world == 1 and self.fuse_tail and self._adam)
+        d.fuse_tail = int(part == "all" and self.world == 1 and self.fuse_tail and self._opt_key is None)
         if part in ("all", "front"):
             d.embed_done = 1
             N.check(L.prism_step_front(ctypes.byref(d), rp, buf._size, None, buf.seed, buf._draws,
@@ -623,14 +616,13 @@ class HipAgent:
                     torch.cuda.current_stream().synchronize()
                     self._graphs[key] = self._capture(buf, d)   # capture, then replay once = this step
                 else:
-                    self._replay(g, buf, d)
+                    g[0].replay()
+                    if len(g) == 2:          # data parallel, two graphs around an eagerly launched collective
+                        self._allreduce()
+                        g[1].replay()
         self._fused_tau += 3 * max(self.dims.n_tau, self.dims.n_tau_next) * self._B
         buf._fused_draws += self._B
-        self._static_total_loss = self.scalars[0]
-        self._static_distribution_loss = self.out_dl if self.dims.use_iqn else None
-        self._static_q_loss = self.out_ql if self.dims.n_heads > 0 else None
-        self.n_updates += 1
-        return self.out_td
+        return self._step_done()
 
     def _capture(self, buf, d):
         if self.world == 1:
@@ -674,15 +666,63 @@ class HipAgent:
         g2.replay()
         return (g1, g2)
 
-    def _replay(self, g, buf, d):
-        if len(g) == 1:
-            g[0].replay()
-        else:
-            g[0].replay()
-            self._allreduce()
-            g[1].replay()
-
     # ------------------------------------------------------------------ acting
+    def _act_T(self):
+        """Quantile samples per action of one acting forward (composite_model.py:57): its draws are ``T * n``."""
+        return int(self.model.distribution_model.n_quantile_samples_per_action) if self.dims.use_iqn else 0
+
+    def _act_buffers(self, n):
+        """``(z, qb, n_pad, T)``: the estimate arrays ``prism_act_forward`` fills for ``n`` observations and the selector
+        kernels read -- quantile values ``z[T*n (padded to whole 16-row tiles), A]`` with IQN, Q values
+        ``qb[heads, n_pad, A]`` with Q heads, None for what the model does not have."""
+        dm, T = self.dims, self._act_T()
+        n_pad = (n + 15) // 16 * 16
+        z = torch.empty(((n * T + 15) // 16 * 16, dm.n_actions), device=self.device) if dm.use_iqn else None
+        qb = torch.empty((dm.n_heads, n_pad, dm.n_actions), device=self.device) if self._act_q else None
+        return z, qb, n_pad, T
+
+    def _act_launch(self, obs, n, T, tau, offset, z, qb, rng_counters, act_flags):
+        """The one ``prism_act_forward`` call, on the current stream.  The caller says who counts the draws, never the
+        descriptor as the last learner step left it: a fused step leaves it pointing at the device counters (step_fused),
+        and with them set ``prism_act_forward`` adds ``rng_counters[2]`` to ``offset`` and advances it.  That word belongs
+        to the graph path (_forward_graph: ``rng_counters`` bound, offset 0), which seeds it from ``_act_draws`` whenever
+        an eager call has moved the count on; the eager call (act_estimates) draws at the HOST's count (``rng_counters``
+        None, offset ``_act_draws``) and has the packed weight copies rebuilt (``act_flags`` 0).  Both fields go back to
+        what they were.  A capture bakes every argument: ``obs``, ``z``, ``qb`` are the capturing slot's own buffers."""
+        d = self._desc
+        keep = d.rng_counters, d.act_flags
+        d.rng_counters, d.act_flags = rng_counters, act_flags
+        try:
+            N.check(N.lib().prism_act_forward(ctypes.byref(d), N.ptr(obs), n, T, N.ptr(tau), self.seed, offset, N.ptr(z),
+                                              N.ptr(qb), N.current_stream_handle()), "prism_act_forward")
+        finally:
+            d.rng_counters, d.act_flags = keep
+
+    def _selector_key(self, sel):
+        """The selector's native kernel and constants: ``("ids", lmbda, epsilon, rho_lower_bound, unsquish id)``,
+        ``("greedy",)``, or None for what has none (sampled IDS, an unsquish function the kernel does not know, IDS on a
+        model without both estimate arrays, any other selector): the selector's torch code on the eager estimates."""
+        from prism_amd.agents.action_selectors import GreedyActionSelector, IDSActionSelector
+        if type(sel) is IDSActionSelector:
+            from prism_amd.agents.squish_functions import unsquish_id
+            usq = unsquish_id(sel.unsquish_function)
+            if sel.random_sample or usq is None or not (self.dims.use_iqn and self._act_q):
+                return None
+            return ("ids", float(sel.lmbda), float(sel.epsilon), float(sel.ids_rho_lower_bound), usq)
+        return ("greedy",) if type(sel) is GreedyActionSelector else None
+
+    def _select_launch(self, skey, z, qb, n, n_pad, T, act, host_act, scores):
+        """The selector kernel of ``skey`` (_selector_key) on the current stream: actions to ``act`` (device) and, where
+        given, to ``host_act`` (pinned host); ``scores``: the ``(n, A)`` information ratios IDS leaves behind."""
+        L, dm = N.lib(), self.dims
+        if skey[0] == "ids":
+            N.check(L.prism_ids_select(N.ptr(z), N.ptr(qb), n, n_pad, T, dm.n_actions, dm.n_heads, skey[1], skey[2], skey[3],
+                                       skey[4], N.ptr(scores), None, N.ptr(act), N.ptr(host_act), N.current_stream_handle()),
+                    "prism_ids_select")
+        else:
+            N.check(L.prism_greedy_select(N.ptr(z), N.ptr(qb), n, n_pad, T, dm.n_actions, dm.n_heads, N.ptr(act), None,
+                                          N.ptr(host_act), N.current_stream_handle()), "prism_greedy_select")
+
     @torch.no_grad()
     def act_estimates(self, obs, taus=None):
         """``(q_estimates, return_distribution)`` as ``CompositeModel.forward(x, for_action=True)`` hands them to the
@@ -692,15 +732,11 @@ class HipAgent:
         samples ``[T*n, 1]`` in the reference's order (parity tests)."""
         from prism_amd.agents.modules import _as_tensor
         obs = _as_tensor(obs, self.device).contiguous()
-        dm = self.dims
-        q_tiles = dm.n_heads > 0 and dm.head_layers == 2
-        q_rows = dm.n_heads > 0 and dm.head_layers == 1
         if self._B is None:
             self._prepare(int(self.config.batch_size))
-        n, B, A = int(obs.shape[0]), self._B, dm.n_actions
-        cap = (B // 16) * 16 if q_tiles else B
+        n, A, cap = int(obs.shape[0]), self.dims.n_actions, self._act_cap
         if cap < 1:
-            raise ValueError(f"acting through the Q-head tiles needs a learner batch of at least 16 (batch {B})")
+            raise ValueError(f"acting through the Q-head tiles needs a learner batch of at least 16 (batch {self._B})")
         if n > cap:          # more observations than the learner's workspace holds at once: in pieces
             parts = [self.act_estimates(obs[i:i + cap], None if taus is None else
                                         taus.view(-1, n)[:, i:i + cap].reshape(-1, 1)) for i in range(0, n, cap)]
@@ -708,28 +744,12 @@ class HipAgent:
             dist = torch.cat([p[1] for p in parts], dim=1) if parts[0][1] is not None else None
             self._act_raw = None          # (describes the last piece only: nobody may select from it)
             return q, dist
-        T = int(self.model.distribution_model.n_quantile_samples_per_action) if dm.use_iqn else 0
-        n_pad = (n + 15) // 16 * 16
-        z = torch.empty(((n * T + 15) // 16 * 16, A), device=self.device) if dm.use_iqn else None
-        qb = torch.empty((dm.n_heads, n_pad, A), device=self.device) if (q_tiles or q_rows) else None
-        if taus is None and dm.use_iqn and self.tau_rng == "torch":
+        z, qb, n_pad, T = self._act_buffers(n)
+        if taus is None and self.dims.use_iqn and self.tau_rng == "torch":
             taus = torch.rand([T * n, 1], device=self.device)
         tau = None if taus is None else taus.to(self.device, torch.float32).reshape(-1).contiguous()
-        # This call draws at the HOST's acting count.  A fused step leaves the descriptor pointing at the device counters
-        # (step_fused), and with them set prism_act_forward would add rng_counters[2] to the offset and advance it: that word
-        # belongs to the graph path (_forward_graph), which seeds it from _act_draws whenever an eager call has moved the
-        # count on.  The packed weight copies are rebuilt here as well (act_flags = 0).
-        d = self._desc
-        keep = d.rng_counters, d.act_flags
-        d.rng_counters, d.act_flags = None, 0
-        try:
-            with torch.cuda.device(self.device):
-                N.check(N.lib().prism_act_forward(ctypes.byref(d), N.ptr(obs), n, T, N.ptr(tau) if tau is not None else None,
-                                                  self.seed, self._act_draws, N.ptr(z) if z is not None else None,
-                                                  N.ptr(qb) if qb is not None else None, N.current_stream_handle()),
-                        "prism_act_forward")
-        finally:
-            d.rng_counters, d.act_flags = keep
+        with torch.cuda.device(self.device):          # at the host's acting count, packed weight copies rebuilt
+            self._act_launch(obs, n, T, tau, self._act_draws, z, qb, rng_counters=None, act_flags=0)
         self._act_draws += T * n
         self._act_raw = (z, qb, n, n_pad, T)
         dist = z[:n * T].view(n, T, A).permute(1, 0, 2) if z is not None else None
@@ -746,7 +766,7 @@ class HipAgent:
         epsilon-greedy selection (``prism_greedy_select``; the coin and the random actions come from the selector's host
         generator exactly as in action_selectors.py:35-45) run natively on the estimate buffers; only sampled IDS
         (``ids_use_random_samples``: ``torch.multinomial`` on torch's generator) reads them with the selector's torch code."""
-        from prism_amd.agents.action_selectors import EGreedyActionSelector, GreedyActionSelector, IDSActionSelector
+        from prism_amd.agents.action_selectors import EGreedyActionSelector
         from prism_amd.agents.modules import _as_tensor
         sel = self.eval_action_selector if self._is_eval else self.action_selector
         obs_in = obs
@@ -757,7 +777,7 @@ class HipAgent:
                 # quantile samples are drawn whether or not the estimates are used.  The estimates are not needed here, the
                 # draws are: consume them, so that every later greedy action sees the stream it would see in the reference
                 if self.dims.use_iqn:
-                    T = int(self.model.distribution_model.n_quantile_samples_per_action)
+                    T = self._act_T()
                     if self.tau_rng == "torch":
                         torch.rand([T * n, 1], device=self.device)
                     else:
@@ -766,7 +786,7 @@ class HipAgent:
             sel = sel.greedy
         if self._B is None:
             self._prepare(int(self.config.batch_size))
-        cap = (self._B // 16) * 16 if (self.dims.n_heads > 0 and self.dims.head_layers == 2) else self._B
+        cap = self._act_cap
         if n <= cap and self.act_graph and self.tau_rng == "philox":
             out = self._forward_graph(obs_in, n, sel)
             if out is not None:
@@ -783,22 +803,11 @@ class HipAgent:
         experience_collector.py:77-78 -- or the pinned staging block for host arrays), the selector and its constants.  The
         quantile draws come from the device counter ``rng_counters[2]`` (include/prism_hip.h), which mirrors ``_act_draws``.
         Returns None for selectors that have no native kernel (the caller runs the eager path)."""
-        from prism_amd.agents.action_selectors import GreedyActionSelector, IDSActionSelector
-        dm = self.dims
-        A = dm.n_actions
-        shape = (n, 10, 10, dm.in_channels)
-        q_tiles = dm.n_heads > 0 and dm.head_layers == 2
-        q_rows = dm.n_heads > 0 and dm.head_layers == 1
-        if type(sel) is IDSActionSelector:
-            from prism_amd.agents.squish_functions import unsquish_id
-            usq = unsquish_id(sel.unsquish_function)
-            if sel.random_sample or usq is None or not (dm.use_iqn and (q_tiles or q_rows)):
-                return None
-            skey = ("ids", float(sel.lmbda), float(sel.epsilon), float(sel.ids_rho_lower_bound), usq)
-        elif type(sel) is GreedyActionSelector:
-            skey = ("greedy",)
-        else:
+        skey = self._selector_key(sel)
+        if skey is None:
             return None
+        dm = self.dims
+        shape = (n, 10, 10, dm.in_channels)
         if torch.is_tensor(obs_in) and obs_in.is_cuda and not (obs_in.dtype == torch.float32 and obs_in.is_contiguous()
                                                                and obs_in.numel() == n * 100 * dm.in_channels):
             obs_in = obs_in.float().contiguous().view(shape)          # (a device tensor in another layout: one eager copy)
@@ -819,15 +828,12 @@ class HipAgent:
         if st is None:
             if len(self._act_graphs) > 32:
                 self._act_graphs.clear()
-            T = int(self.model.distribution_model.n_quantile_samples_per_action) if dm.use_iqn else 0
-            n_pad = (n + 15) // 16 * 16
+            z, qb, n_pad, T = self._act_buffers(n)
             dev = self.device
-            st = dict(T=T, n_pad=n_pad, calls=0, g=None,
+            st = dict(T=T, n_pad=n_pad, z=z, qb=qb, calls=0, g=None,
                       pin_in=[torch.zeros(shape, dtype=torch.float32).pin_memory() for _ in range(4)] if on_host else None,
                       obs=obs_in if mode == "ptr" else (None if on_host else torch.empty(shape, dtype=torch.float32, device=dev)),
-                      z=torch.empty(((n * T + 15) // 16 * 16, A), device=dev) if dm.use_iqn else None,
-                      qb=torch.empty((dm.n_heads, n_pad, A), device=dev) if (q_tiles or q_rows) else None,
-                      scores=torch.empty((n, A), device=dev) if skey[0] == "ids" else None,
+                      scores=torch.empty((n, dm.n_actions), device=dev) if skey[0] == "ids" else None,
                       act=[torch.empty(n, dtype=torch.int64, device=dev) for _ in range(4)],
                       pin_out=[torch.zeros(n, dtype=torch.int64).pin_memory() for _ in range(4)],
                       ev=[torch.cuda.Event() for _ in range(4)])
@@ -851,23 +857,11 @@ class HipAgent:
         def launch(slot):
             # (host arrays: the embed kernel reads the pinned staging block in place -- 400 C bytes per observation over the
             # host link cost less than a copy node in front of it; the selector writes the actions to device AND pinned host)
-            L, d, T = N.lib(), self._desc, st["T"]
-            keep = d.rng_counters, d.act_flags
-            d.rng_counters = self.rng_counters.data_ptr()
-            d.act_flags = N.ACT_WEIGHTS_CURRENT if current else 0
-            try:
-                N.check(L.prism_act_forward(ctypes.byref(d), N.ptr(st["pin_in"][slot] if on_host else st["obs"]), n, T, None, self.seed, 0,
-                                            N.ptr(st["z"]), N.ptr(st["qb"]), N.current_stream_handle()), "prism_act_forward")
-            finally:
-                d.rng_counters, d.act_flags = keep
-            if skey[0] == "ids":
-                N.check(L.prism_ids_select(N.ptr(st["z"]), N.ptr(st["qb"]), n, st["n_pad"], T, A, dm.n_heads, skey[1], skey[2],
-                                           skey[3], skey[4], N.ptr(st["scores"]), None, N.ptr(st["act"][slot]), N.ptr(st["pin_out"][slot]),
-                                           N.current_stream_handle()), "prism_ids_select")
-            else:
-                N.check(L.prism_greedy_select(N.ptr(st["z"]), N.ptr(st["qb"]), n, st["n_pad"], T, A, dm.n_heads,
-                                              N.ptr(st["act"][slot]), None, N.ptr(st["pin_out"][slot]),
-                                              N.current_stream_handle()), "prism_greedy_select")
+            self._act_launch(st["pin_in"][slot] if on_host else st["obs"], n, st["T"], None, 0, st["z"], st["qb"],
+                             rng_counters=self.rng_counters.data_ptr(),
+                             act_flags=N.ACT_WEIGHTS_CURRENT if current else 0)
+            self._select_launch(skey, st["z"], st["qb"], n, st["n_pad"], st["T"], st["act"][slot], st["pin_out"][slot],
+                                st["scores"])
 
         with torch.cuda.device(self.device):
             if st["g"] is None and st["calls"] == 0:
@@ -894,29 +888,19 @@ class HipAgent:
         return _Actions.wrap(st["act"][k], st["pin_out"][k], st["ev"][k])
 
     def _forward_piece(self, obs, sel):
-        from prism_amd.agents.action_selectors import GreedyActionSelector, IDSActionSelector
         self._act_raw = None
         q, dist = self.act_estimates(obs)
+        skey = self._selector_key(sel)
+        if skey is None:
+            return sel.select_action(sel.generate_action_probs(dist, q))
         z, qb, n, n_pad, T = self._act_raw
-        A = self.dims.n_actions
         action = torch.empty(n, dtype=torch.int64, device=self.device)
-        from prism_amd.agents.squish_functions import unsquish_id
-        usq = unsquish_id(sel.unsquish_function) if type(sel) is IDSActionSelector else None
-        if (type(sel) is IDSActionSelector and not sel.random_sample and usq is not None
-                and z is not None and qb is not None):
-            scores = torch.empty((n, A), device=self.device)
-            with torch.cuda.device(self.device):
-                N.check(N.lib().prism_ids_select(N.ptr(z), N.ptr(qb), n, n_pad, T, A, self.dims.n_heads, float(sel.lmbda),
-                                                 float(sel.epsilon), float(sel.ids_rho_lower_bound), usq, N.ptr(scores), None,
-                                                 N.ptr(action), None, N.current_stream_handle()), "prism_ids_select")
+        scores = torch.empty((n, self.dims.n_actions), device=self.device) if skey[0] == "ids" else None
+        with torch.cuda.device(self.device):
+            self._select_launch(skey, z, qb, n, n_pad, T, action, None, scores)
+        if scores is not None:
             self._act_scores = scores
-            return action
-        if type(sel) is GreedyActionSelector:
-            with torch.cuda.device(self.device):
-                N.check(N.lib().prism_greedy_select(N.ptr(z), N.ptr(qb), n, n_pad, T, A, self.dims.n_heads, N.ptr(action),
-                                                    None, None, N.current_stream_handle()), "prism_greedy_select")
-            return action
-        return sel.select_action(sel.generate_action_probs(dist, q))
+        return action
 
     def _params_replaced(self):
         self._param_epoch += 1
