@@ -102,6 +102,32 @@ def jitter_grads(sd, tgt, spec, batch, w, taus, seed, draws=6, ulps=2.4e-7):
     return out
 
 
+def variant_config(device, over):
+    """MinAtar preset as the parity tests on seeded random minibatches run it (tests/test_gpu_variants.py,
+    tests/test_gpu_envelope.py): IQN alone with PER and LayerNorm unless `over` says otherwise."""
+    from prism_amd.config import MINATAR_CONFIG, derive
+    kw = dict(device=device, use_cuda_graph=False, use_e_greedy=False, use_ids=False, use_iqn=True, use_dqn=False,
+              use_per=True, use_layer_norm=True)
+    kw.update(over)
+    return derive(MINATAR_CONFIG, **kw)
+
+
+def random_batch(rng, B, C, A, cfg):
+    """A seeded random minibatch, PER weights and the quantile samples of one update in the reference's draw order."""
+    T, Tn = cfg.iqn_n_current_state_quantile_samples, cfg.iqn_n_next_state_quantile_samples
+    batch = dict(obs=torch.from_numpy((rng.random((B, 10, 10, C)) < 0.15).astype(np.float32)),
+                 next_obs=torch.from_numpy((rng.random((B, 10, 10, C)) < 0.15).astype(np.float32)),
+                 reward=torch.from_numpy(rng.normal(0, 1, B).astype(np.float32)),
+                 nonterminal=torch.from_numpy((rng.random(B) < 0.9).astype(np.float32)),
+                 gamma=torch.from_numpy(np.full(B, 0.99 ** 3, np.float32)),
+                 action=torch.from_numpy(rng.integers(0, A, B).astype(np.int64)))
+    w = torch.from_numpy(rng.uniform(0.2, 1.0, B).astype(np.float32))
+    n_next = 2 if (cfg.use_target_network and cfg.use_double_q_learning) else 1
+    taus = [torch.from_numpy(rng.random((B * T, 1)).astype(np.float32))]
+    taus += [torch.from_numpy(rng.random((B * Tn, 1)).astype(np.float32)) for _ in range(n_next)]
+    return batch, w, taus
+
+
 def checksums(sd):
     s = np.array([float(v.double().sum()) for v in sd.values()])
     l2 = np.array([float(v.double().norm()) for v in sd.values()])

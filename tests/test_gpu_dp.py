@@ -107,7 +107,11 @@ def test_two_ranks_on_identical_data_equal_single_replica():
 
 
 # ---- the direct all-reduce (prism_direct_reduce_scatter / prism_direct_all_gather over peer-mapped buffers)
-def _direct_worker(rank, world, port, q, mode=None):
+# configs[2] / configs[3] parameter counts, a tail-only and an even size
+DIRECT_SIZES = (201_430, 1_544_210, 7, 4096)
+
+
+def _direct_worker(rank, world, port, q, mode=None, sizes=DIRECT_SIZES):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -116,7 +120,7 @@ def _direct_worker(rank, world, port, q, mode=None):
     from prism_amd import dist as pdist
     N_MAX = N.MAX_PEERS
     ok = True
-    for n in (201_430, 1_544_210, 7, 4096):                 # configs[2] / configs[3] parameter counts, a tail-only and an even size
+    for n in sizes:
         g = torch.Generator(device="cuda:0").manual_seed(100 + rank)
         flat = torch.randn(n, device="cuda:0", generator=g)
         want = flat.cpu()
@@ -154,12 +158,12 @@ def _direct_worker(rank, world, port, q, mode=None):
     dist.destroy_process_group()
 
 
-def _run_direct(mode):
+def _run_direct(mode, sizes=DIRECT_SIZES):          # (sizes: tests/test_gpu_envelope.py runs the same check at other lengths)
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_direct_worker, args=(r, 2, port, q, mode)) for r in range(2)]
+    procs = [ctx.Process(target=_direct_worker, args=(r, 2, port, q, mode, sizes)) for r in range(2)]
     for p in procs:
         p.start()
     res = [q.get(timeout=240), q.get(timeout=240)]

@@ -41,27 +41,7 @@ CASES = {
 }
 
 
-def _config(device, over):
-    from prism_amd.config import MINATAR_CONFIG, derive
-    kw = dict(device=device, use_cuda_graph=False, use_e_greedy=False, use_ids=False, use_iqn=True, use_dqn=False,
-              use_per=True, use_layer_norm=True)
-    kw.update(over)
-    return derive(MINATAR_CONFIG, **kw)
-
-
-def _batch(rng, B, C, A, cfg):
-    T, Tn = cfg.iqn_n_current_state_quantile_samples, cfg.iqn_n_next_state_quantile_samples
-    batch = dict(obs=torch.from_numpy((rng.random((B, 10, 10, C)) < 0.15).astype(np.float32)),
-                 next_obs=torch.from_numpy((rng.random((B, 10, 10, C)) < 0.15).astype(np.float32)),
-                 reward=torch.from_numpy(rng.normal(0, 1, B).astype(np.float32)),
-                 nonterminal=torch.from_numpy((rng.random(B) < 0.9).astype(np.float32)),
-                 gamma=torch.from_numpy(np.full(B, 0.99 ** 3, np.float32)),
-                 action=torch.from_numpy(rng.integers(0, A, B).astype(np.int64)))
-    w = torch.from_numpy(rng.uniform(0.2, 1.0, B).astype(np.float32))
-    n_next = 2 if (cfg.use_target_network and cfg.use_double_q_learning) else 1
-    taus = [torch.from_numpy(rng.random((B * T, 1)).astype(np.float32))]
-    taus += [torch.from_numpy(rng.random((B * Tn, 1)).astype(np.float32)) for _ in range(n_next)]
-    return batch, w, taus
+_config, _batch = H.variant_config, H.random_batch          # (shared with tests/test_gpu_envelope.py)
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
