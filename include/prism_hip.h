@@ -380,6 +380,25 @@ int prism_ids_select(const float *z, const float *q, int32_t n, int32_t n_pad, i
                      int32_t n_heads, float lmbda, float epsilon, float rho_lower_bound, int32_t unsquish_fn,
                      float *out_scores, float *out_aux, int64_t *out_action, int64_t *out_action_host, prism_stream_t stream);
 
+/* IDSActionSelector.generate_action_probs + select_action for ids_use_random_samples = True
+ * (prism/agents/action_selectors.py:125-176; :150-152 the probabilities, :175 the draw).  Scores and out_aux: those of
+ * prism_ids_select, bit for bit (one device routine).  Per observation b, fp32 unless stated:
+ *   p_a = min(max(softmax_a(-scores), epsilon), 1)           (max subtracted first; NOT renormalised after the clamp:
+ *                                                             torch.multinomial samples proportionally to its weights)
+ *   u   = u_in[b] (float64, parity input) when u_in is given, else the 53-bit uniform of the first two words of
+ *         Philox4x32-10(seed, c0 + b, "IDSA" = 0x49445341): a stream key apart from "TAU0" + sid, "PERM" and "UNIF"
+ *   c0  = offset when rng_counters is NULL (the caller's acting-draw count at the start of this call's forward), else
+ *         offset + rng_counters[2] - n * n_tau: prism_act_forward, earlier on the same stream or in the same hipGraph,
+ *         has advanced that word by its n * n_tau draws; the word is read, never written.  A forward consumes
+ *         n * n_tau >= n counts, so the ranges [c0, c0 + n) of successive calls cannot overlap.
+ *   action = first a with u * S < p_0 + ... + p_a in float64, index order, S = p_0 + ... + p_(A-1); A - 1 if none.
+ * out_probs (optional) [n][A]: the clamped probabilities; out_action [n]; out_action_host as for prism_ids_select. */
+int prism_ids_sample_select(const float *z, const float *q, int32_t n, int32_t n_pad, int32_t n_tau, int32_t n_actions,
+                            int32_t n_heads, float lmbda, float epsilon, float rho_lower_bound, int32_t unsquish_fn,
+                            const double *u_in, uint64_t seed, uint64_t offset, const uint64_t *rng_counters,
+                            float *out_scores, float *out_aux, float *out_probs, int64_t *out_action,
+                            int64_t *out_action_host, prism_stream_t stream);
+
 /* GreedyActionSelector.generate_action_probs + select_action (prism/agents/action_selectors.py:70-83; also the greedy
  * branch of EGreedyActionSelector, :24-45): action [n] = argmax_a mean(q_estimates[:, a, :]).  q != NULL: mean over the
  * n_heads ensemble estimates prism_act_forward left in out_q; q == NULL: mean over the n_tau quantile estimates in z

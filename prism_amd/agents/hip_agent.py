@@ -700,21 +700,34 @@ class HipAgent:
 
     def _selector_key(self, sel):
         """The selector's native kernel and constants: ``("ids", lmbda, epsilon, rho_lower_bound, unsquish id)``,
-        ``("greedy",)``, or None for what has none (sampled IDS, an unsquish function the kernel does not know, IDS on a
-        model without both estimate arrays, any other selector): the selector's torch code on the eager estimates."""
+        ``("ids_sampled", ...)`` with the same constants for ``ids_use_random_samples`` (the action is a Philox draw of the
+        agent's seed: only where the quantile draws are, ``tau_rng == "philox"``), ``("greedy",)``, or None for what has
+        none (sampled IDS in parity mode -- ``torch.multinomial`` on torch's generator --, an unsquish function the kernel
+        does not know, IDS on a model without both estimate arrays, any other selector): the selector's torch code on the
+        eager estimates."""
         from prism_amd.agents.action_selectors import GreedyActionSelector, IDSActionSelector
         if type(sel) is IDSActionSelector:
             from prism_amd.agents.squish_functions import unsquish_id
             usq = unsquish_id(sel.unsquish_function)
-            if sel.random_sample or usq is None or not (self.dims.use_iqn and self._act_q):
+            if usq is None or not (self.dims.use_iqn and self._act_q) or (sel.random_sample and self.tau_rng != "philox"):
                 return None
-            return ("ids", float(sel.lmbda), float(sel.epsilon), float(sel.ids_rho_lower_bound), usq)
+            return ("ids_sampled" if sel.random_sample else "ids", float(sel.lmbda), float(sel.epsilon),
+                    float(sel.ids_rho_lower_bound), usq)
         return ("greedy",) if type(sel) is GreedyActionSelector else None
 
-    def _select_launch(self, skey, z, qb, n, n_pad, T, act, host_act, scores):
+    def _select_launch(self, skey, z, qb, n, n_pad, T, act, host_act, scores, draw_offset=0, rng_counters=None):
         """The selector kernel of ``skey`` (_selector_key) on the current stream: actions to ``act`` (device) and, where
-        given, to ``host_act`` (pinned host); ``scores``: the ``(n, A)`` information ratios IDS leaves behind."""
+        given, to ``host_act`` (pinned host); ``scores``: the ``(n, A)`` information ratios IDS leaves behind.  Sampled
+        IDS draws observation b at Philox counter c0 + b, c0 the acting count at the START of this call's forward: the
+        eager call hands it over (``draw_offset``), the graph path binds ``rng_counters``, whose word [2] the forward in
+        front of this launch has advanced by n * T (the kernel takes that off again)."""
         L, dm = N.lib(), self.dims
+        if skey[0] == "ids_sampled":
+            N.check(L.prism_ids_sample_select(N.ptr(z), N.ptr(qb), n, n_pad, T, dm.n_actions, dm.n_heads, skey[1], skey[2],
+                                              skey[3], skey[4], None, self.seed, draw_offset, rng_counters, N.ptr(scores), None,
+                                              None, N.ptr(act), N.ptr(host_act), N.current_stream_handle()),
+                    "prism_ids_sample_select")
+            return
         if skey[0] == "ids":
             N.check(L.prism_ids_select(N.ptr(z), N.ptr(qb), n, n_pad, T, dm.n_actions, dm.n_heads, skey[1], skey[2], skey[3],
                                        skey[4], N.ptr(scores), None, N.ptr(act), N.ptr(host_act), N.current_stream_handle()),
@@ -762,10 +775,12 @@ class HipAgent:
 
     @torch.no_grad()
     def forward(self, obs):
-        """Agent.forward (agent.py:31-41).  Deterministic information-directed sampling (``prism_ids_select``), greedy and
-        epsilon-greedy selection (``prism_greedy_select``; the coin and the random actions come from the selector's host
-        generator exactly as in action_selectors.py:35-45) run natively on the estimate buffers; only sampled IDS
-        (``ids_use_random_samples``: ``torch.multinomial`` on torch's generator) reads them with the selector's torch code."""
+        """Agent.forward (agent.py:31-41).  Information-directed sampling, deterministic (``prism_ids_select``) and sampled
+        (``ids_use_random_samples``: ``prism_ids_sample_select``, the action a Philox draw of the agent's seed on its own
+        stream key), greedy and epsilon-greedy selection (``prism_greedy_select``; the coin and the random actions come from
+        the selector's host generator exactly as in action_selectors.py:35-45) run natively on the estimate buffers.  Only in
+        parity mode (``tau_rng == "torch"``) sampled IDS runs the selector's torch code: ``torch.multinomial`` on torch's
+        generator, as the reference draws."""
         from prism_amd.agents.action_selectors import EGreedyActionSelector
         from prism_amd.agents.modules import _as_tensor
         sel = self.eval_action_selector if self._is_eval else self.action_selector
@@ -833,7 +848,7 @@ class HipAgent:
             st = dict(T=T, n_pad=n_pad, z=z, qb=qb, calls=0, g=None,
                       pin_in=[torch.zeros(shape, dtype=torch.float32).pin_memory() for _ in range(4)] if on_host else None,
                       obs=obs_in if mode == "ptr" else (None if on_host else torch.empty(shape, dtype=torch.float32, device=dev)),
-                      scores=torch.empty((n, dm.n_actions), device=dev) if skey[0] == "ids" else None,
+                      scores=torch.empty((n, dm.n_actions), device=dev) if skey[0] in ("ids", "ids_sampled") else None,
                       act=[torch.empty(n, dtype=torch.int64, device=dev) for _ in range(4)],
                       pin_out=[torch.zeros(n, dtype=torch.int64).pin_memory() for _ in range(4)],
                       ev=[torch.cuda.Event() for _ in range(4)])
@@ -861,7 +876,7 @@ class HipAgent:
                              rng_counters=self.rng_counters.data_ptr(),
                              act_flags=N.ACT_WEIGHTS_CURRENT if current else 0)
             self._select_launch(skey, st["z"], st["qb"], n, st["n_pad"], st["T"], st["act"][slot], st["pin_out"][slot],
-                                st["scores"])
+                                st["scores"], rng_counters=self.rng_counters.data_ptr())
 
         with torch.cuda.device(self.device):
             if st["g"] is None and st["calls"] == 0:
@@ -889,15 +904,16 @@ class HipAgent:
 
     def _forward_piece(self, obs, sel):
         self._act_raw = None
+        c0 = self._act_draws          # (the acting count this piece's forward starts from: the sampled selector's counter)
         q, dist = self.act_estimates(obs)
         skey = self._selector_key(sel)
         if skey is None:
             return sel.select_action(sel.generate_action_probs(dist, q))
         z, qb, n, n_pad, T = self._act_raw
         action = torch.empty(n, dtype=torch.int64, device=self.device)
-        scores = torch.empty((n, self.dims.n_actions), device=self.device) if skey[0] == "ids" else None
+        scores = torch.empty((n, self.dims.n_actions), device=self.device) if skey[0] in ("ids", "ids_sampled") else None
         with torch.cuda.device(self.device):
-            self._select_launch(skey, z, qb, n, n_pad, T, action, None, scores)
+            self._select_launch(skey, z, qb, n, n_pad, T, action, None, scores, draw_offset=c0)
         if scores is not None:
             self._act_scores = scores
         return action

@@ -39,12 +39,11 @@ __device__ __forceinline__ const float *act_stage(const float *z, int64_t b, int
     return s_z;
 }
 
-__global__ __launch_bounds__(ACT_THREADS) void ids_score_kernel(IdsArgs k) {
-    extern __shared__ __attribute__((aligned(16))) float s_act[];
-    const int b = blockIdx.x, lane = threadIdx.x;
+// The information ratio of action `lane` of observation b on wave 0 of the workgroup (every lane of the wave calls it; zb:
+// what act_stage returned), written to k.scores / k.aux.  The one statement of the score arithmetic: ids_score_kernel takes
+// its arg-min, ids_sample_kernel (act_sample.hip) turns it into probabilities.
+__device__ __forceinline__ float ids_score_wave(const IdsArgs &k, const float *zb, int b, int lane) {
     const int A = k.A, T = k.T, Hd = k.heads;
-    const float *zb = act_stage(k.z, b, T, A, s_act, k.stage != 0);
-    if (lane >= 64) return;
     // ensemble statistics: lane = action
     float mean = 0.f, spread = 0.f;
     if (lane < A) {
@@ -91,6 +90,17 @@ __global__ __launch_bounds__(ACT_THREADS) void ids_score_kernel(IdsArgs k) {
             x[3 * A + lane] = gain;
         }
     }
+    return score;
+}
+
+#ifndef PRISM_ACT_NO_KERNELS          // (act_sample.hip takes the routines above alone: the kernels below live in learner.hip)
+__global__ __launch_bounds__(ACT_THREADS) void ids_score_kernel(IdsArgs k) {
+    extern __shared__ __attribute__((aligned(16))) float s_act[];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int A = k.A;
+    const float *zb = act_stage(k.z, b, k.T, A, s_act, k.stage != 0);
+    if (lane >= 64) return;
+    const float score = ids_score_wave(k, zb, b, lane);
     // argmin, first minimum wins (torch.argmin)
     int best = 0;
     float bv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(score), 0));
@@ -153,5 +163,7 @@ __global__ __launch_bounds__(ACT_THREADS) void greedy_select_kernel(GreedyArgs k
         if (k.action2) k.action2[b] = best;
     }
 }
+
+#endif  // PRISM_ACT_NO_KERNELS
 
 }  // namespace prism

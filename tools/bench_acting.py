@@ -2,23 +2,26 @@
 host -> actions on the host, per call, for the hipGraph form (default) and the eager launches (config.act_graph = False):
   numpy in      a host array in, .cpu() out (evaluators: sync_agent_evaluator.py:43)
   device in     the reference collector's pattern: one persistent device inference buffer in, .cpu().numpy() out
-                (multiprocessing_experience_collection/experience_collector.py:77-78,127)"""
-import contextlib, io, json, os, sys, time
+                (multiprocessing_experience_collection/experience_collector.py:77-78,127)
+--rows ids      only the ten-head IDS configuration, deterministic and sampled (ids_use_random_samples), hipGraph form
+--sizes 1,16    observation counts;  --reps 300   calls per median;  --tag NAME   prefix of every printed row (two trees
+                measured alternately in one visit)"""
+import argparse, contextlib, io, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from prism_amd.config import baseline_config
 from prism_amd.learner import Learner
 
 
-def measure(cfg_i, graph, reps=400):
-    cfg = baseline_config(cfg_i, device="cuda:0", log_to_wandb=False, act_graph=graph)
+def measure(cfg_i, graph, reps=400, sizes=(1, 4, 16), **over):
+    cfg = baseline_config(cfg_i, device="cuda:0", log_to_wandb=False, act_graph=graph, **over)
     ln = Learner()
     with contextlib.redirect_stdout(io.StringIO()):
         ln.configure(cfg, obs_shape=(10, 10, 4), n_actions=6)
     ag = ln.agent
     rng = np.random.default_rng(0)
     out = {}
-    for n in (1, 4, 16):
+    for n in sizes:
         obs = (rng.random((n, 10, 10, 4)) < 0.1).astype(np.float32)
         dev_buf = torch.zeros((n, 10, 10, 4), device="cuda:0")
         host_t = torch.from_numpy(obs)
@@ -41,11 +44,24 @@ def measure(cfg_i, graph, reps=400):
 
 
 if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", default="all", choices=["all", "ids"])
+    ap.add_argument("--sizes", default="1,4,16")
+    ap.add_argument("--reps", type=int, default=400)
+    ap.add_argument("--tag", default="")
+    args = ap.parse_args()
+    sizes = tuple(int(x) for x in args.sizes.split(","))
+    sampled = dict(ids_use_random_samples=True)
+    rows = [(2, "IQN (greedy on the quantile mean)", {}), (3, "IDS + IQN, ten heads", {}),
+            (3, "IDS + IQN, ten heads, sampled", sampled)]
+    if args.rows == "ids":
+        rows = rows[1:]
     res = {}
-    for cfg_i, name in ((2, "IQN (greedy on the quantile mean)"), (3, "IDS + IQN, ten heads")):
-        for graph in (True, False):
-            r = measure(cfg_i, graph)
-            res[f"configs[{cfg_i}] {'graph' if graph else 'eager'}"] = r
+    for cfg_i, name, over in rows:
+        for graph in ((True,) if args.rows == "ids" else (True, False)):
+            r = measure(cfg_i, graph, args.reps, sizes, **over)
+            res[f"{args.tag}configs[{cfg_i}]{' sampled' if over else ''} {'graph' if graph else 'eager'}"] = r
             for k, v in r.items():
-                print(f"{name:36s} {'hipGraph' if graph else 'eager   '} {k:18s}: {v:7.1f} us per Agent.forward (host -> actions on the host)")
+                print(f"{args.tag}{name:36s} {'hipGraph' if graph else 'eager   '} {k:18s}: {v:7.1f} us per Agent.forward (host -> actions on the host)",
+                      flush=True)
     print(json.dumps(res))
