@@ -19,6 +19,7 @@
 #include "qbwd2_kernels.h"
 #include "bwd3_kernels.h"
 #include "bwd4_kernels.h"
+#include "plan.h"
 
 namespace prism {
 
@@ -68,167 +69,6 @@ __global__ __launch_bounds__(512) void loss_both_kernel(IqnArgs a) {
     else qh_loss_body<H, LN>(a, (int)blockIdx.x - a.B);
 }
 
-// ---- workspace carving -----------------------------------------------------------------------
-struct Carver {
-    char *base;
-    size_t off;
-    explicit Carver(void *b) : base((char *)b), off(0) {}
-    float *f(size_t n) {
-        float *p = base ? (float *)(base + off) : nullptr;
-        off += ((n + 3) / 4) * 16;   // n floats rounded up to 16 bytes
-        return p;
-    }
-};
-
-// backward decomposition (iqn_bwd_kernel) into row chunks x 64 column slices: width 128, two workgroups per CU share
-// each SIMD (8 row chunks); width 256, one workgroup per CU (4 row chunks)
-static constexpr int MAX_CHUNKS = 16;
-static int bwd_chunks(int H) { return H == 128 ? 8 : 4; }      // workgroups per CU x 4
-
-static bool width_ok(int h) { return h == 128 || h == 256; }
-
-// Forward GEMMs: 1 = exact fp32 chain (v_mfma_f32_16x16x4_f32), 2 = three-piece bf16 operands on v_mfma_f32_16x16x32_bf16
-// (fp32 accuracy, common.h).  prism_learner_desc.gemm_mode picks one, 0 = the library default (PRISM_GEMM=fp32|bf16x3
-// overrides it).
-static int default_gemm_mode() {
-    static const int mode = [] {
-        const char *e = getenv("PRISM_GEMM");
-        if (e && !strcmp(e, "fp32")) return 1;
-        if (e && !strcmp(e, "bf16x3")) return 2;
-        return PRISM_GEMM_DEFAULT;
-    }();
-    return mode;
-}
-static int use_split(const prism_learner_desc *ld) {
-    const prism_model_dims &d = ld->dims;
-    const int mode = ld->gemm_mode == PRISM_GEMM_FP32 || ld->gemm_mode == PRISM_GEMM_BF16X3 ? ld->gemm_mode : default_gemm_mode();
-    if (mode != PRISM_GEMM_BF16X3) return 0;
-    return (d.use_iqn || (d.n_heads && d.head_layers == 2)) ? 1 : 0;
-}
-
-// the 64-column bf16 backward (bwd3_kernels.h) where it applies: bf16 mode, width 128 (the forward then saves ReLU(phi))
-static bool use_bw3(const prism_learner_desc *ld) {
-    const prism_model_dims &d = ld->dims;
-    return d.use_iqn && use_split(ld) && bw3_ok(d.iqn_width, ld->batch, d.n_tau, true);
-}
-
-// ... and its width-256 form (bwd4_kernels.h: pairs of waves share 16 columns, one hidden half each)
-static bool use_bw4(const prism_learner_desc *ld) {
-    const prism_model_dims &d = ld->dims;
-    return d.use_iqn && use_split(ld) && bw4_ok(d.iqn_width, ld->batch, d.n_tau);
-}
-static int iqn_supported(const prism_model_dims *d, int32_t B) {
-    auto pow2_ok = [](int t) { return t == 4 || t == 8 || t == 16 || t == 32 || t == 64; };
-    if (!d->use_iqn && d->n_heads == 0) return PRISM_ERR_UNSUPPORTED;
-    if (d->embed_dim != E_DIM) return PRISM_ERR_UNSUPPORTED;
-    if (d->squish_fn < PRISM_SQUISH_NONE || d->squish_fn > PRISM_SQUISH_SYMLOG) return PRISM_ERR_UNSUPPORTED;
-    if (d->use_iqn) {
-        if (d->n_basis != K_BASIS || d->iqn_layers != 1 || !width_ok(d->iqn_width)) return PRISM_ERR_UNSUPPORTED;
-        if (!pow2_ok(d->n_tau) || !pow2_ok(d->n_tau_next)) return PRISM_ERR_UNSUPPORTED;
-        if ((B * d->n_tau) % 16 || (B * d->n_tau_next) % 16) return PRISM_ERR_UNSUPPORTED;
-    }
-    if (d->n_heads != 0) {
-        // ensemble / DQN heads of the form [LN] -> Linear(1024,H) -> ReLU -> [LN] -> Linear(H,A)
-        if (d->head_layers == 1) {
-            // single Linear(1024 -> A) DQN head, with or without LayerNorm, no IQN beside it
-            if (d->n_heads != 1 || d->use_iqn) return PRISM_ERR_UNSUPPORTED;
-        } else {
-            if (d->n_heads < 0 || d->n_heads > Q_MAX_HEADS || d->head_layers != 2 || !width_ok(d->head_width))
-                return PRISM_ERR_UNSUPPORTED;
-            if (B % 16) return PRISM_ERR_UNSUPPORTED;
-        }
-    }
-    if (B < 1 || B > SMALL_MAX_B) return PRISM_ERR_UNSUPPORTED;
-    if (d->n_actions < 1 || d->n_actions > 16 || d->in_channels < 1 || d->in_channels > 10) return PRISM_ERR_UNSUPPORTED;
-    return PRISM_OK;
-}
-
-static int iqn_width(const prism_model_dims &d) { return d.use_iqn ? d.iqn_width : 128; }
-static int head_width(const prism_model_dims &d) { return d.n_heads && d.head_layers == 2 ? d.head_width : 128; }
-
-// the IQN loss finishes inside the forward tiles (kind 2) when current- and next-state rows of a sample run
-// through the SAME weights (no target network) and a 16-row tile holds whole samples (2 T <= 16)
-static int local_loss(const prism_model_dims &d) {
-    return d.use_iqn && !d.has_target && d.n_tau_next == d.n_tau && d.n_tau <= 8 ? 1 : 0;
-}
-
-static size_t carve_iqn(const prism_model_dims *d, int B, void *base, IqnWs *ws, float **tau_buf, float **dl_buf) {
-    Carver c(base);
-    const size_t R = (size_t)B * d->n_tau, Rn = (size_t)B * d->n_tau_next, A = d->n_actions;
-    const size_t maxT = d->n_tau > d->n_tau_next ? d->n_tau : d->n_tau_next;
-    const size_t Hi = iqn_width(*d), Hq = head_width(*d);
-    const int ln = d->use_layer_norm;
-    IqnWs w;
-    w.ticket = (unsigned int *)c.f(8);     // first 32 bytes: the self-resetting tickets (zeroed once by the caller)
-    w.e_cur = c.f((size_t)B * E_DIM);
-    w.e_next = c.f((size_t)B * E_DIM);
-    w.uv = c.f(2 * UV_ROWS * Hi);
-    w.wpk[0] = c.f(iqn_pack_split_floats((int)Hi));      // (the larger of the two layouts: fp32 stream order / bf16 pieces)
-    w.wpk[1] = c.f(iqn_pack_split_floats((int)Hi));
-    w.cosb = c.f(R * K_BASIS);
-    w.cospk = (unsigned int *)c.f((size_t)((R + 2 * Rn + 15) / 16 + 3) * CP_TILE);
-    w.phis = c.f(((R + 15) / 16) * 16 * (size_t)E_DIM);
-    w.mu1 = c.f(R);
-    w.rstd1 = c.f(R);
-    w.pre1 = c.f(R * Hi);
-    w.xhat2 = c.f(R * Hi);
-    w.rstd2 = c.f(R);
-    w.zcur = c.f(R * A);
-    w.zon = c.f(Rn * A);
-    w.ztg = c.f(Rn * A);
-    w.dq = c.f(R);
-    w.c1 = c.f(R);
-    w.c2 = c.f(R);
-    w.dpre1 = c.f(R * Hi);
-    w.Sb = c.f((size_t)B * Hi);
-    w.Pb = c.f((size_t)B * Hi);
-    w.Db = c.f(B);
-    w.lossw = c.f(B);
-    w.de_iqn = c.f((size_t)B * E_DIM);
-    w.slabs = c.f((size_t)MAX_CHUNKS * iqn_slab_floats((int)Hi, ln));
-    {
-        const size_t post_rows = (size_t)((B + 3) / 4) * CONV_ROW;      // (post_conv_blocks(B, C) <= this)
-        const size_t bwd_rows = (size_t)(E_DIM / 16) * MAX_CHUNKS * BWD_CONV_ROW;
-        const size_t dqn_rows = d->head_layers == 1 && d->n_heads ? (size_t)B * CONV_ROW : 0;   // one row per sample
-        const size_t m = post_rows > bwd_rows ? post_rows : bwd_rows;
-        w.convpart = c.f(m > dqn_rows ? m : dqn_rows);
-    }
-    w.normpart = c.f(NORM_SLOTS);
-    w.sib = c.f((size_t)TREE_MAX_LEVELS * B * 2);
-    w.wb_plan = c.f((size_t)B * 4);
-    {
-        const size_t Hd = d->n_heads, RQ = Hd * (size_t)B;
-        w.q_mu1 = c.f(RQ);
-        w.q_rstd1 = c.f(RQ);
-        w.q_pre1 = c.f(RQ * Hq);
-        w.q_xhat2 = c.f(RQ * Hq);
-        w.q_rstd2 = c.f(RQ);
-        w.zq_cur = c.f(RQ * A);
-        w.zq_on = c.f(RQ * A);
-        w.zq_tg = c.f(RQ * A);
-        w.q_dq = c.f(RQ);
-        w.q_c1 = c.f(RQ);
-        w.q_c2 = c.f(RQ);
-        w.q_dpre1 = c.f(RQ * Hq);
-        w.q_pp = (unsigned short *)c.f(RQ * Hq * 3 / 2);
-        w.q_xp = (unsigned short *)c.f((size_t)B * E_DIM * 3 / 2);
-        w.q_lossw = c.f(B);
-        w.q_uv = c.f(2 * Hd * UV_ROWS * Hq);
-        w.q_kappa = c.f(Q_MAX_HEADS * Q_NORM_PARTS);
-        w.q_wpk[0] = c.f(Hd * (size_t)q_pack_split_floats((int)Hq));
-        w.q_wpk[1] = c.f(d->has_target ? Hd * (size_t)q_pack_split_floats((int)Hq) : 0);
-        w.de_q = c.f(Hd * (size_t)B * E_DIM);      // (one slot for the single-Linear DQN head)
-        w.q_slabs = c.f(Hd * (size_t)q_slab_floats((int)Hq, ln));
-    }
-    float *tb = c.f(3 * maxT * B);
-    float *db = c.f(2 * (size_t)B);       // per-sample dl | ql when the caller binds no output arrays (the post launch reads both)
-    if (ws) *ws = w;
-    if (tau_buf) *tau_buf = tb;
-    if (dl_buf) *dl_buf = db;
-    return c.off;
-}
-
-
 }  // namespace prism
 
 using namespace prism;
@@ -240,12 +80,13 @@ extern "C" int prism_learner_supported(const prism_model_dims *dims, int32_t bat
 
 extern "C" size_t prism_learner_workspace_bytes(const prism_model_dims *dims, int32_t batch) {
     if (!dims || iqn_supported(dims, batch) != PRISM_OK) return 0;
-    return carve_iqn(dims, batch, nullptr, nullptr, nullptr, nullptr);
+    return make_plan(*dims, batch).ws_bytes;
 }
 
+// The ONE envelope check, plan and carve of a call: every entry point starts here and hands `pl` on.
 // `need_batch`: the minibatch arrays and outputs of an update must be bound (not for the acting forward, which may well
 // run before the first update)
-static int check_learner(const prism_learner_desc *ld, bool need_batch = true) {
+static int check_learner(const prism_learner_desc *ld, LearnerPlan &pl, bool need_batch = true) {
     PRISM_CHECK_ARG(ld != nullptr, "null descriptor");
     if (iqn_supported(&ld->dims, ld->batch) != PRISM_OK) {
         set_error("prism_learner: model dims / batch not covered by the HIP kernels "
@@ -253,10 +94,11 @@ static int check_learner(const prism_learner_desc *ld, bool need_batch = true) {
                   "Q heads: one layer, or two layers of width 128/256 with B %% 16 == 0)");
         return PRISM_ERR_UNSUPPORTED;
     }
+    pl = make_plan(ld->dims, ld->batch, ld->gemm_mode, ld->workspace, ld->fused_replay, ld->fused_index, ld->fuse_tail,
+                   ld->hyper.grad_scale);
     PRISM_CHECK_ARG(ld->params && ld->grads && ld->adam_m && ld->adam_v && ld->adam_step, "null parameter buffers");
     PRISM_CHECK_ARG(!ld->dims.has_target || ld->target_params, "has_target without target_params");
-    PRISM_CHECK_ARG(ld->workspace && ld->workspace_bytes >= prism_learner_workspace_bytes(&ld->dims, ld->batch),
-                    "workspace too small");
+    PRISM_CHECK_ARG(ld->workspace && ld->workspace_bytes >= pl.ws_bytes, "workspace too small");
     PRISM_CHECK_ARG(((uintptr_t)ld->workspace & 15) == 0, "workspace must be 16-byte aligned");
     PRISM_CHECK_ARG((((uintptr_t)ld->params | (uintptr_t)ld->grads | (uintptr_t)ld->adam_m | (uintptr_t)ld->adam_v) & 15) == 0,
                     "parameter / gradient / Adam buffers must be 16-byte aligned");
@@ -277,61 +119,57 @@ static int check_learner(const prism_learner_desc *ld, bool need_batch = true) {
     return PRISM_OK;
 }
 
-// fused writeback in two halves: preparation beside the gradient reduction (post launch), level walk
-// beside clip + Adam (back launch, 256-thread workgroups: one leaf per thread)
-static bool split_writeback(const prism_learner_desc *ld) { return ld->batch <= 256; }
-
-static int bwd_row_chunks(const prism_learner_desc *ld) {
-    const prism_model_dims &d = ld->dims;
-    if (use_bw3(ld)) return BW3_RC;
-    if (use_bw4(ld)) return bw4_chunks(ld->batch, d.n_tau);
-    return bwd_chunks(iqn_width(d));
+// One forward pass over `n_tiles` 16-row tiles.  kind 0: IQN quantile rows, 1: Q-head rows, 2: mixed tiles of whole samples
+// (T current-state + T next-state rows; e2 / tau2 / z2 are the next-state half).  `set`: 0 online, 1 target weights (and
+// their packed copies / u|v tables).  The tau draws are tied to `sid` (IqnPass.stream_id) in the reference's draw order
+// (iqn_model.py:104,112-126).  Needs a.params / target_params / ws / Hi / Hq / n_heads.
+static IqnPass make_pass(const IqnArgs &a, int kind, int set, const float *e, const float *tau, float *z, int T, int n_tiles,
+                         int save, int sid, const float *e2 = nullptr, const float *tau2 = nullptr, float *z2 = nullptr) {
+    IqnPass p;
+    memset(&p, 0, sizeof(p));
+    p.params = set ? a.target_params : a.params;
+    p.wpk = kind == 1 ? a.ws.q_wpk[set] : a.ws.wpk[set];
+    p.uv = kind == 1 ? a.ws.q_uv + (size_t)set * a.n_heads * UV_ROWS * a.Hq : a.ws.uv + (size_t)set * UV_ROWS * a.Hi;
+    p.e = e;
+    p.e2 = e2;
+    p.tau_in = tau;
+    p.tau_in2 = tau2;
+    p.z_out = z;
+    p.z_out2 = z2;
+    p.T = T;
+    p.n_tiles = n_tiles;
+    p.save = save;
+    p.stream_id = sid;
+    p.kind = kind;
+    return p;
 }
 
-static bool conv_in_bwd(const prism_learner_desc *ld) {
-    const prism_model_dims &d = ld->dims;
-    if (use_bw3(ld)) return bw3_conv_ok(d.use_iqn, d.n_heads, d.propagate_grad, d.n_tau, d.in_channels, ld->batch);
-    if (use_bw4(ld)) return false;
-    return bwd_conv_ok(d.use_iqn, d.n_heads, d.propagate_grad, d.n_tau, d.in_channels, ld->batch, bwd_chunks(iqn_width(d)),
-                       iqn_width(d));
-}
-
-static int post_block_count(const prism_learner_desc *ld) {
-    const prism_model_dims &d = ld->dims;
-    if (d.head_layers == 1 && d.n_heads) return post_blocks_dqn1(d.in_channels);
-    return post_blocks(ld->batch, d.in_channels, d.use_iqn, d.n_heads, conv_in_bwd(ld), iqn_slab_floats(iqn_width(d), d.use_layer_norm),
-                       q_slab_floats(head_width(d), d.use_layer_norm), iqn_width(d), head_width(d),
-                       bwd_row_chunks(ld));
-}
-
-static void fill_iqn_args(const prism_learner_desc *ld, IqnArgs &a) {
+// the kernel arguments of an update: the plan's decisions, the descriptor's pointers, the learner's pass list
+static void fill_iqn_args(const prism_learner_desc *ld, const LearnerPlan &pl, IqnArgs &a) {
     const prism_model_dims &d = ld->dims;
     const int B = ld->batch;
     memset(&a, 0, sizeof(a));
-    float *tau_buf = nullptr, *dl_buf = nullptr;
-    carve_iqn(&d, B, ld->workspace, &a.ws, &tau_buf, &dl_buf);
+    a.ws = pl.ws;
     a.B = B;
     a.Bt = B;
     a.A = d.n_actions;
     a.C = d.in_channels;
     a.T = d.n_tau;
     a.Tn = d.n_tau_next;
-    a.Hi = iqn_width(d);
-    a.Hq = head_width(d);
+    a.Hi = pl.Hi;
+    a.Hq = pl.Hq;
     a.ln = d.use_layer_norm;
-    a.slab = iqn_slab_floats(a.Hi, a.ln);
-    a.q_slab = q_slab_floats(a.Hq, a.ln);
-    a.n_chunks = bwd_row_chunks(ld);
+    a.slab = pl.slab;
+    a.q_slab = pl.q_slab;
+    a.n_chunks = pl.n_chunks;
     a.has_target = d.has_target;
     a.double_q = d.double_q;
     a.propagate_grad = d.propagate_grad;
     a.squish = d.squish_fn;
-    a.split = use_split(ld);
-    // the Q heads' input-side backward as two shared-operand GEMMs on the bf16 pipe (qbwd2_kernels.h) where it applies
-    a.q_de_slots = d.n_heads;
-    if (a.split && qb2_ok(a.Hq, B, d.n_heads, d.head_layers)) a.q_de_slots = 2;
-    a.conv_in_bwd = conv_in_bwd(ld);
-    a.conv_rows = use_bw3(ld) ? 1 : 4;
+    a.split = pl.split;
+    a.q_de_slots = pl.q_de_slots;
+    a.conv_in_bwd = pl.conv_in_bwd;
+    a.conv_rows = pl.conv_rows;
     a.bg = bwd_geometry(a.Hi, a.B, a.C, a.T, a.n_chunks, a.conv_in_bwd != 0);
     a.huber_k = d.huber_k;
     a.dist_w = d.dist_loss_weight;
@@ -356,94 +194,42 @@ static void fill_iqn_args(const prism_learner_desc *ld, IqnArgs &a) {
     a.seed = ld->seed;
     a.offset = ld->offset;
     a.rng = ld->rng_counters;
-    a.tau_out = ld->tau_out ? ld->tau_out : tau_buf;
-    a.maxT = d.n_tau > d.n_tau_next ? d.n_tau : d.n_tau_next;
-    a.out_dl = ld->out_dist_loss ? ld->out_dist_loss : dl_buf;
-    a.out_ql = ld->out_q_loss ? ld->out_q_loss : dl_buf + B;
+    a.tau_out = ld->tau_out ? ld->tau_out : pl.tau_buf;
+    a.maxT = pl.maxT;
+    a.out_dl = ld->out_dist_loss ? ld->out_dist_loss : pl.dl_buf;
+    a.out_ql = ld->out_q_loss ? ld->out_q_loss : pl.dl_buf + B;
     a.out_td = ld->out_td;
     a.out_scalars = ld->out_scalars;
     a.grads = ld->grads;
-    // passes; the tau draws are tied to stream_id in the reference's draw order (iqn_model.py:104,112-126)
+    a.local_loss = pl.local_loss;
+    // passes: current state | next state on the online weights (no target network, or double Q) | next state on the target's
     int np = 0;
-    const float *uv0 = a.ws.uv, *uv1 = a.ws.uv + UV_ROWS * a.Hi;
+    const bool online_next = !d.has_target || d.double_q;
+    if (pl.local_loss) {
+        a.pass[np++] = make_pass(a, 2, 0, a.ws.e_cur, ld->tau_cur, a.ws.zcur, d.n_tau, B * 2 * d.n_tau / 16, 1, 0, a.ws.e_next,
+                                 ld->tau_next_online, a.ws.zon);
+    } else if (d.use_iqn) {
+        const int nt = B * d.n_tau_next / 16;
+        a.pass[np++] = make_pass(a, 0, 0, a.ws.e_cur, ld->tau_cur, a.ws.zcur, d.n_tau, B * d.n_tau / 16, 1, 0);
+        if (online_next) a.pass[np++] = make_pass(a, 0, 0, a.ws.e_next, ld->tau_next_online, a.ws.zon, d.n_tau_next, nt, 0, 1);
+        if (d.has_target) a.pass[np++] = make_pass(a, 0, 1, a.ws.e_next, ld->tau_next_target, a.ws.ztg, d.n_tau_next, nt, 0, 2);
+    }
     if (d.use_iqn) {
-        a.local_loss = local_loss(d);
-        if (a.local_loss) {
-            // one pass of mixed tiles: each holds whole samples (T current-state + T next-state rows)
-            IqnPass p;
-            memset(&p, 0, sizeof(p));
-            p.params = ld->params;
-            p.wpk = a.ws.wpk[0];
-            p.uv = uv0;
-            p.e = a.ws.e_cur;
-            p.e2 = a.ws.e_next;
-            p.tau_in = ld->tau_cur;
-            p.tau_in2 = ld->tau_next_online;
-            p.z_out = a.ws.zcur;
-            p.z_out2 = a.ws.zon;
-            p.T = d.n_tau;
-            p.n_tiles = B * 2 * d.n_tau / 16;
-            p.save = 1;
-            p.stream_id = 0;
-            p.kind = 2;
-            a.pass[np++] = p;
-            a.ws.ztg = a.ws.zon;
-        } else {
-            auto iqn_pass = [&](const float *params, int set, const float *e, const float *tau, float *z, int T, int save,
-                                int sid) {
-                IqnPass p;
-                memset(&p, 0, sizeof(p));
-                p.params = params;
-                p.wpk = a.ws.wpk[set];
-                p.uv = set ? uv1 : uv0;
-                p.e = e;
-                p.tau_in = tau;
-                p.z_out = z;
-                p.T = T;
-                p.n_tiles = B * T / 16;
-                p.save = save;
-                p.stream_id = sid;
-                p.kind = 0;
-                return p;
-            };
-            a.pass[np++] = iqn_pass(ld->params, 0, a.ws.e_cur, ld->tau_cur, a.ws.zcur, d.n_tau, 1, 0);
-            if (!d.has_target || d.double_q)
-                a.pass[np++] = iqn_pass(ld->params, 0, a.ws.e_next, ld->tau_next_online, a.ws.zon, d.n_tau_next, 0, 1);
-            if (d.has_target)
-                a.pass[np++] = iqn_pass(ld->target_params, 1, a.ws.e_next, ld->tau_next_target, a.ws.ztg, d.n_tau_next, 0, 2);
-            if (!d.has_target) a.ws.ztg = a.ws.zon;            // bootstrap from self
-            else if (!d.double_q) a.ws.zon = a.ws.ztg;         // DQN-style: target picks the action too
-        }
+        if (!d.has_target) a.ws.ztg = a.ws.zon;            // bootstrap from self
+        else if (!d.double_q) a.ws.zon = a.ws.ztg;         // DQN-style: target picks the action too
     }
     if (d.n_heads > 0 && d.head_layers == 2) {
         // Q-head tiles: (B/16) x heads per pass; same online/target selection (q_ensemble.py:62-68)
         const int nt = (B / 16) * d.n_heads;
-        const float *quv0 = a.ws.q_uv, *quv1 = a.ws.q_uv + (size_t)d.n_heads * UV_ROWS * a.Hq;
-        auto q_pass = [&](const float *params, int set, const float *e, float *z, int save, int sid) {
-            IqnPass p;
-            memset(&p, 0, sizeof(p));
-            p.params = params;
-            p.wpk = a.ws.q_wpk[set];
-            p.uv = set ? quv1 : quv0;
-            p.e = e;
-            p.z_out = z;
-            p.T = 1;
-            p.n_tiles = nt;
-            p.save = save;
-            p.stream_id = sid;
-            p.kind = 1;
-            return p;
-        };
-        a.pass[np++] = q_pass(ld->params, 0, a.ws.e_cur, a.ws.zq_cur, 1, 0);
-        if (!d.has_target || d.double_q) a.pass[np++] = q_pass(ld->params, 0, a.ws.e_next, a.ws.zq_on, 0, 1);
-        if (d.has_target) a.pass[np++] = q_pass(ld->target_params, 1, a.ws.e_next, a.ws.zq_tg, 0, 2);
+        a.pass[np++] = make_pass(a, 1, 0, a.ws.e_cur, nullptr, a.ws.zq_cur, 1, nt, 1, 0);
+        if (online_next) a.pass[np++] = make_pass(a, 1, 0, a.ws.e_next, nullptr, a.ws.zq_on, 1, nt, 0, 1);
+        if (d.has_target) a.pass[np++] = make_pass(a, 1, 1, a.ws.e_next, nullptr, a.ws.zq_tg, 1, nt, 0, 2);
         if (!d.has_target) a.ws.zq_tg = a.ws.zq_on;
         else if (!d.double_q) a.ws.zq_on = a.ws.zq_tg;
     }
     a.n_pass = np;
     // the IQN tiles' quantile samples + cos basis come prepared from the embed / front launch (bf16 mode: the prologue they
     // replace is the split forward's)
-    a.cos_tiles = 0;
     if (a.split)
         for (int i = 0; i < np; ++i)
             if (a.pass[i].kind != 1) {
@@ -604,6 +390,15 @@ static int launch_fwd_tiles(const IqnArgs &a, hipStream_t stream) {
 
 // ---- the post launch: gradient slabs / small tensors / conv fold (+ priority writeback block); with `tail` also the
 // clip + Adam update behind a grid barrier (single GPU) ------------------------------------------------------------
+// its instantiation: the fused tail (always the full writer) with the dense tree top or without | preparing a writeback
+// the back launch finishes (`planned`) | the full writer, dense or not (also: no writeback at all)
+using PostKernel = void (*)(IqnArgs, PostWriteback, TailArgs);
+static PostKernel post_kernel(bool tail, bool planned, bool dense) {
+    if (tail) return dense ? iqn_post_kernel<true, true, true> : iqn_post_kernel<true, true, false>;
+    if (planned) return iqn_post_kernel<false, false, false>;
+    return dense ? iqn_post_kernel<true, false, true> : iqn_post_kernel<true, false, false>;
+}
+
 // workgroups of the fused-tail instantiation `dense` that fit the CURRENT device at once (per device: processes that
 // drive several GPUs, and per instantiation: the two forms differ in registers)
 static int post_max_resident(bool dense) {
@@ -616,45 +411,29 @@ static int post_max_resident(bool dense) {
     if (it != cache.end()) return it->second;
     int cus = 0, per = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    const hipError_t e = dense ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, iqn_post_kernel<true, true, true>, 1024, 0)
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, iqn_post_kernel<true, true, false>, 1024, 0);
-    if (e != hipSuccess) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, post_kernel(true, false, dense), 1024, 0) != hipSuccess) return 0;
     return cache[{dev, dense}] = cus * per;
 }
 
-static bool writeback_rides(const prism_learner_desc *ld) { return ld->fused_replay && ld->fused_replay->tree && ld->fused_index; }
-// the writeback block of the post launch recomputes the top of the tree whole when it may (tree_dense_finish)
-static bool post_dense(const prism_learner_desc *ld) {
-    // the full writer's live threads: 2 x the batch rounded up to waves (iqn_post_kernel)
-    const int wb_live = ld->batch <= UPD_MAX ? std::min(1024, 2 * ((ld->batch + 63) & ~63)) : 1024;
-    return writeback_rides(ld) && tree_dense_ok(ld->fused_replay->tree_capacity, ld->batch, wb_live);
-}
-
 // The fused tail needs every workgroup of the launch resident at once (it has a grid barrier; the device must not be
-// shared with other processes' kernels -- the barrier gives up after GRID_WAIT_TICKS and flags it, step_kernels.h) and
-// nothing between the gradient and the optimizer step (no all-reduce: grad_scale 1).
-static bool tail_fused(const prism_learner_desc *ld) {
-    if (!ld->fuse_tail || ld->hyper.grad_scale != 1.0f) return false;
-    // without a priority writeback riding along there is nothing for the fused launch to hide behind the barrier
-    // (measured, uniform replay + one-layer DQN head: 32.7 us fused vs 30.1 us as two launches)
-    // (an IQN's gradient slabs are enough to hide: additive ablation base, uniform replay, width 256: 95.5 vs 97.3 us per step)
-    if (!writeback_rides(ld) && !ld->dims.use_iqn) return false;
-    return post_block_count(ld) + 1 <= post_max_resident(post_dense(ld));
-}
+// shared with other processes' kernels -- the barrier gives up after GRID_WAIT_TICKS and flags it, step_kernels.h): the
+// plan says whether it is wanted, the device whether it fits.
+static bool tail_fused(const LearnerPlan &pl) { return pl.tail_wanted && pl.post_blocks + 1 <= post_max_resident(pl.post_dense); }
 
-static int launch_post(const prism_learner_desc *ld, const IqnArgs &a, const TailArgs *tail, hipStream_t stream) {
+// (`ld`: the writeback's pointers and exponents; every decision is the plan's)
+static int launch_post(const prism_learner_desc *ld, const LearnerPlan &pl, const IqnArgs &a, const TailArgs *tail, hipStream_t stream) {
     ProfileScope ps_(tail ? K_TAIL : K_POST, stream);
-    int nb = post_block_count(ld);
+    int nb = pl.post_blocks;
     PostWriteback wb;
     memset(&wb, 0, sizeof(wb));
-    if (writeback_rides(ld)) {
+    if (pl.writeback_rides) {
         // TD errors are final: the priority writeback rides along as one more block of this launch
         wb.enabled = 1;
         wb.rp = *ld->fused_replay;
         wb.index = ld->fused_index;
         wb.sib = reinterpret_cast<const float2 *>(a.ws.sib);
         wb.sib_state = a.ws.ticket + 3;
-        wb.plan = (!tail && split_writeback(ld)) ? reinterpret_cast<int4 *>(a.ws.wb_plan) : nullptr;
+        wb.plan = (!tail && pl.split_writeback) ? reinterpret_cast<int4 *>(a.ws.wb_plan) : nullptr;
         wb.alpha = ld->fused_alpha;
         wb.eps = ld->fused_eps;
         wb.block = nb;
@@ -662,23 +441,22 @@ static int launch_post(const prism_learner_desc *ld, const IqnArgs &a, const Tai
     }
     TailArgs none;
     memset(&none, 0, sizeof(none));
-    const bool dense = post_dense(ld);
-    if (tail && dense) hipLaunchKernelGGL((iqn_post_kernel<true, true, true>), dim3(nb), dim3(1024), 0, stream, a, wb, *tail);
-    else if (tail) hipLaunchKernelGGL((iqn_post_kernel<true, true, false>), dim3(nb), dim3(1024), 0, stream, a, wb, *tail);
-    else if (wb.plan) hipLaunchKernelGGL((iqn_post_kernel<false, false, false>), dim3(nb), dim3(1024), 0, stream, a, wb, none);
-    else if (dense) hipLaunchKernelGGL((iqn_post_kernel<true, false, true>), dim3(nb), dim3(1024), 0, stream, a, wb, none);
-    else hipLaunchKernelGGL((iqn_post_kernel<true, false, false>), dim3(nb), dim3(1024), 0, stream, a, wb, none);
+    hipLaunchKernelGGL(post_kernel(tail != nullptr, wb.plan != nullptr, pl.post_dense), dim3(nb), dim3(1024), 0, stream, a, wb,
+                       tail ? *tail : none);
     PRISM_CHECK_LAUNCH();
     return PRISM_OK;
 }
 
+// get_losses + backward as its launch sequence: embed, forward tiles, loss, Q loss, backward, Q backward, post -- each in
+// the form the plan names.  Losses first (TD errors final), then the backward kernels.
 extern "C" int prism_learner_fwd_bwd(const prism_learner_desc *ld, prism_stream_t stream_) {
-    int rc = check_learner(ld);
+    LearnerPlan pl;
+    int rc = check_learner(ld, pl);
     if (rc) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    const int B = ld->batch;
+    const int B = ld->batch, heads = ld->dims.n_heads;
     IqnArgs a;
-    fill_iqn_args(ld, a);
+    fill_iqn_args(ld, pl, a);
 
     if (!ld->embed_done) {
         ProfileScope ps_(K_EMBED, stream);
@@ -691,20 +469,16 @@ extern "C" int prism_learner_fwd_bwd(const prism_learner_desc *ld, prism_stream_
         if (rc) return rc;
         PRISM_CHECK_LAUNCH();
     }
-    // losses first (TD errors final), then the backward kernels
-    const bool merged_loss = ld->dims.use_iqn && !a.local_loss && ld->dims.n_heads > 0 && ld->dims.head_layers == 2 && a.Hi == a.Hq &&
-                             loss_waves(a.T) == LOSS_WAVES;
-    if (merged_loss) {
+    if (pl.merged_loss) {
         ProfileScope ps_(K_LOSS, stream);
         dispatch_hl(a.Hi, a.ln, [&](auto h, auto l) {
             hipLaunchKernelGGL((loss_both_kernel<decltype(h)::value, decltype(l)::value>), dim3(2 * B), dim3(512), 0, stream, a);
         });
         PRISM_CHECK_LAUNCH();
-    }
-    if (ld->dims.use_iqn && !a.local_loss && !merged_loss) {
+    } else if (ld->dims.use_iqn && !pl.local_loss) {
         ProfileScope ps_(K_LOSS, stream);
         dispatch_hl(a.Hi, a.ln, [&](auto h, auto l) {
-            if (loss_waves(a.T) == 16)
+            if (pl.loss_waves == 16)
                 hipLaunchKernelGGL((iqn_loss_kernel<decltype(h)::value, decltype(l)::value, 16>), dim3(B), dim3(64 * 16), 0, stream, a);
             else
                 hipLaunchKernelGGL((iqn_loss_kernel<decltype(h)::value, decltype(l)::value, LOSS_WAVES>), dim3(B),
@@ -712,7 +486,7 @@ extern "C" int prism_learner_fwd_bwd(const prism_learner_desc *ld, prism_stream_
         });
         PRISM_CHECK_LAUNCH();
     }
-    if (ld->dims.n_heads > 0 && !merged_loss) {
+    if (heads > 0 && !pl.merged_loss) {
         ProfileScope ps_(K_Q_FWD, stream);
         if (ld->dims.head_layers == 1) {
             hipLaunchKernelGGL(dqn_loss_kernel, dim3(B), dim3(256), 0, stream, a);
@@ -723,55 +497,54 @@ extern "C" int prism_learner_fwd_bwd(const prism_learner_desc *ld, prism_stream_
         }
         PRISM_CHECK_LAUNCH();
     }
-    if (ld->dims.use_iqn && use_bw3(ld)) {
-        ProfileScope ps_(K_BWD, stream);
-        const dim3 grid((E_DIM / 64) * BW3_RC);
-        const size_t lds = (size_t)bw3_lds_bytes(B, a.T, a.C, a.conv_in_bwd != 0);
-        rc = launch_lds(a.ln ? iqn_bwd3_kernel<true> : iqn_bwd3_kernel<false>, "iqn_bwd3", grid, dim3(512), lds, stream, a, 160 * 1024);
-        if (rc) return rc;
-        PRISM_CHECK_LAUNCH();
-    } else if (ld->dims.use_iqn && use_bw4(ld)) {
-        ProfileScope ps_(K_BWD, stream);
-        const dim3 grid((E_DIM / 32) * a.n_chunks);
-        rc = launch_lds(a.ln ? iqn_bwd4_kernel<true> : iqn_bwd4_kernel<false>, "iqn_bwd4", grid, dim3(512), BW4_LDS_BYTES, stream, a);
-        if (rc) return rc;
-        PRISM_CHECK_LAUNCH();
-    } else if (ld->dims.use_iqn) {
-        if (!bwd_lds_layout_ok(a.Hi, B, a.C, a.T, a.n_chunks, a.conv_in_bwd != 0)) {
+    if (pl.bwd != BWD_NONE) {
+        const bool conv = a.conv_in_bwd != 0;
+        if (pl.bwd == BWD_FP32 && !bwd_lds_layout_ok(a.Hi, B, a.C, a.T, a.n_chunks, conv)) {
             set_error("prism_learner_fwd_bwd: internal: LDS layout of the backward kernel overlaps for this shape");
             return PRISM_ERR_INVALID;
         }
         ProfileScope ps_(K_BWD, stream);
-        const size_t lds = (size_t)bwd_lds_floats(a.Hi, B, a.C, a.T, a.n_chunks, a.conv_in_bwd != 0) * sizeof(float);
-        dispatch_hl(a.Hi, a.ln, [&](auto h, auto l) {
-            rc = launch_lds(iqn_bwd_kernel<decltype(h)::value, decltype(l)::value>, "iqn_bwd", dim3((E_DIM / 16) * a.n_chunks),
-                            dim3(256), lds, stream, a);
-        });
+        switch (pl.bwd) {
+        case BWD_BW3:
+            rc = launch_lds(a.ln ? iqn_bwd3_kernel<true> : iqn_bwd3_kernel<false>, "iqn_bwd3", dim3((E_DIM / 64) * BW3_RC), dim3(512),
+                            (size_t)bw3_lds_bytes(B, a.T, a.C, conv), stream, a, 160 * 1024);
+            break;
+        case BWD_BW4:
+            rc = launch_lds(a.ln ? iqn_bwd4_kernel<true> : iqn_bwd4_kernel<false>, "iqn_bwd4", dim3((E_DIM / 32) * a.n_chunks), dim3(512),
+                            BW4_LDS_BYTES, stream, a);
+            break;
+        default:
+            dispatch_hl(a.Hi, a.ln, [&](auto h, auto l) {
+                rc = launch_lds(iqn_bwd_kernel<decltype(h)::value, decltype(l)::value>, "iqn_bwd", dim3((E_DIM / 16) * a.n_chunks),
+                                dim3(256), (size_t)bwd_lds_floats(a.Hi, B, a.C, a.T, a.n_chunks, conv) * sizeof(float), stream, a);
+            });
+        }
         if (rc) return rc;
         PRISM_CHECK_LAUNCH();
     }
-    if (ld->dims.n_heads > 0 && ld->dims.head_layers == 2 && a.split && qb2_ok(a.Hq, B, ld->dims.n_heads, ld->dims.head_layers)) {
-        ProfileScope ps_(K_Q_BWD, stream);
-        rc = launch_lds(a.ln ? qh_bwd2_kernel<true> : qh_bwd2_kernel<false>, "qh_bwd2", dim3(qb2_blocks(ld->dims.n_heads, B)),
-                        dim3(256), QB2_LDS_BYTES, stream, a);
-        if (rc) return rc;
-        PRISM_CHECK_LAUNCH();
-    } else if (ld->dims.n_heads > 0 && ld->dims.head_layers == 2) {
+    if (pl.q_bwd != QB_NONE) {
         ProfileScope ps_(K_Q_BWD, stream);
         const size_t lds = qb_lds_floats(a.Hq) * sizeof(float);
-        dispatch_hl(a.Hq, a.ln, [&](auto h, auto l) {
-            constexpr int HH = decltype(h)::value;
-            constexpr bool LL = decltype(l)::value;
-            if (B <= 128)      // small batches: a wave per column slice over all rows (qhead_kernels.h, COLS)
-                rc = launch_lds(qh_bwd_kernel<HH, LL, true>, "qh_bwd", dim3((E_DIM / 64) * ld->dims.n_heads), dim3(256), lds, stream, a);
-            else
-                rc = launch_lds(qh_bwd_kernel<HH, LL>, "qh_bwd", dim3((E_DIM / 16) * ld->dims.n_heads), dim3(256), lds, stream, a);
-        });
+        switch (pl.q_bwd) {
+        case QB_QB2:
+            rc = launch_lds(a.ln ? qh_bwd2_kernel<true> : qh_bwd2_kernel<false>, "qh_bwd2", dim3(qb2_blocks(heads, B)), dim3(256),
+                            QB2_LDS_BYTES, stream, a);
+            break;
+        default:
+            dispatch_hl(a.Hq, a.ln, [&](auto h, auto l) {
+                constexpr int HH = decltype(h)::value;
+                constexpr bool LL = decltype(l)::value;
+                if (pl.q_bwd == QB_COLS)      // (qhead_kernels.h, COLS)
+                    rc = launch_lds(qh_bwd_kernel<HH, LL, true>, "qh_bwd", dim3((E_DIM / 64) * heads), dim3(256), lds, stream, a);
+                else
+                    rc = launch_lds(qh_bwd_kernel<HH, LL>, "qh_bwd", dim3((E_DIM / 16) * heads), dim3(256), lds, stream, a);
+            });
+        }
         if (rc) return rc;
         PRISM_CHECK_LAUNCH();
     }
-    if (!tail_fused(ld)) {
-        rc = launch_post(ld, a, nullptr, stream);
+    if (!tail_fused(pl)) {
+        rc = launch_post(ld, pl, a, nullptr, stream);
         if (rc) return rc;
     }
     if (ld->dbg_z) {
@@ -789,18 +562,21 @@ extern "C" int prism_learner_fwd_bwd(const prism_learner_desc *ld, prism_stream_
 extern "C" int prism_act_forward(const prism_learner_desc *ld, const float *obs, int32_t n, int32_t n_tau,
                                  const float *tau_in, uint64_t seed, uint64_t offset, float *out_z, float *out_q,
                                  prism_stream_t stream_) {
-    int rc = check_learner(ld, false);
+    LearnerPlan pl;
+    int rc = check_learner(ld, pl, false);
     if (rc) return rc;
+    const int heads = ld->dims.n_heads;
+    const bool heads2 = heads > 0 && ld->dims.head_layers == 2;
     PRISM_CHECK_ARG(obs != nullptr && n >= 1 && n <= ld->batch, "n must be in [1, batch]");
     const int n_pad = (n + 15) / 16 * 16;
-    PRISM_CHECK_ARG(n_pad <= ld->batch || ld->dims.n_heads == 0 || ld->dims.head_layers != 2,
-                    "Q-head tiles need the workspace of a batch >= 16-padded n");
+    PRISM_CHECK_ARG(n_pad <= ld->batch || !heads2, "Q-head tiles need the workspace of a batch >= 16-padded n");
     PRISM_CHECK_ARG(!ld->dims.use_iqn || (n_tau >= 1 && out_z), "quantile samples per action / output buffer");
-    PRISM_CHECK_ARG(!(ld->dims.n_heads && ld->dims.head_layers == 2) || out_q, "Q output buffer");
+    PRISM_CHECK_ARG(!heads2 || out_q, "Q output buffer");
     hipStream_t stream = (hipStream_t)stream_;
+    // the learner's arguments with the acting call's overrides, each stated once: here for the embed launch (+ the
+    // parameter-only roles), where the n observations stand in for both batch halves ...
     IqnArgs a;
-    fill_iqn_args(ld, a);
-    // embed (+ the parameter-only roles): the n observations stand in for both batch halves
+    fill_iqn_args(ld, pl, a);
     a.cos_tiles = 0;          // (acting tiles draw and evaluate their basis themselves: no learner passes here)
     a.B = n;
     a.obs = a.next_obs = obs;
@@ -815,13 +591,14 @@ extern "C" int prism_act_forward(const prism_learner_desc *ld, const float *obs,
     const int extra = (ld->act_flags & PRISM_ACT_WEIGHTS_CURRENT) ? 0 : front_extra_blocks(extra_dims(a));
     hipLaunchKernelGGL(iqn_embed_kernel, dim3((extra ? 2 * n : n) + extra), dim3(256), 0, stream, a);
     PRISM_CHECK_LAUNCH();
-    if (ld->dims.n_heads > 0 && ld->dims.head_layers == 1) {
+    if (heads > 0 && ld->dims.head_layers == 1) {
         // single-Linear DQN head: one workgroup per observation on the embeddings just written
         PRISM_CHECK_ARG(out_q != nullptr, "Q output buffer");
         hipLaunchKernelGGL(dqn1_act_kernel, dim3(n), dim3(256), 0, stream, a, out_q);
         PRISM_CHECK_LAUNCH();
         return PRISM_OK;
     }
+    // ... and here for the tiles: rows padded to whole tiles, the caller's Philox position, no loss
     a.B = n_pad;
     a.Bt = n;
     a.seed = seed;
@@ -830,36 +607,11 @@ extern "C" int prism_act_forward(const prism_learner_desc *ld, const float *obs,
     a.act_rng = nullptr;
     a.tau_out = nullptr;
     a.local_loss = 0;
-    int np = 0;
-    IqnPass p;
-    if (ld->dims.use_iqn) {
-        memset(&p, 0, sizeof(p));
-        p.params = ld->params;
-        p.wpk = a.ws.wpk[0];
-        p.uv = a.ws.uv;
-        p.e = a.ws.e_cur;
-        p.tau_in = tau_in;
-        p.z_out = out_z;
-        p.T = n_tau;
-        p.n_tiles = (n * n_tau + 15) / 16;
-        p.kind = 0;
-        p.stream_id = 3;                 // a Philox stream of its own: acting draws never repeat an update's
-        a.pass[np++] = p;
-    }
-    if (ld->dims.n_heads > 0 && ld->dims.head_layers == 2) {
-        memset(&p, 0, sizeof(p));
-        p.params = ld->params;
-        p.wpk = a.ws.q_wpk[0];
-        p.uv = a.ws.q_uv;
-        p.e = a.ws.e_cur;
-        p.z_out = out_q;
-        p.T = 1;
-        p.n_tiles = (n_pad / 16) * ld->dims.n_heads;
-        p.kind = 1;
-        a.pass[np++] = p;
-    }
-    PRISM_CHECK_ARG(np > 0, "nothing to run");
-    a.n_pass = np;
+    a.n_pass = 0;
+    // (stream_id 3: a Philox stream of its own -- acting draws never repeat an update's)
+    if (ld->dims.use_iqn) a.pass[a.n_pass++] = make_pass(a, 0, 0, a.ws.e_cur, tau_in, out_z, n_tau, (n * n_tau + 15) / 16, 0, 3);
+    if (heads2) a.pass[a.n_pass++] = make_pass(a, 1, 0, a.ws.e_cur, nullptr, out_q, 1, (n_pad / 16) * heads, 0, 0);
+    PRISM_CHECK_ARG(a.n_pass > 0, "nothing to run");
     rc = launch_fwd_tiles(a, stream);
     if (rc) return rc;
     PRISM_CHECK_LAUNCH();
@@ -897,14 +649,13 @@ extern "C" int prism_greedy_select(const float *z, const float *q, int32_t n, in
 }
 
 // grid-norm partial slots valid for the Adam kernels: either what post left, or a fresh pass
-static int prepare_norm(const prism_learner_desc *ld, const IqnWs &ws, AdamArgs &a, hipStream_t stream) {
-    if (ld->hyper.grad_scale == 1.0f) {
-        a.n_slots = post_block_count(ld);
+static int prepare_norm(const LearnerPlan &pl, AdamArgs &a, hipStream_t stream) {
+    if (a.grad_scale == 1.0f) {
+        a.n_slots = pl.post_blocks;
     } else {
         // data parallel: the gradient was all-reduced after the backward; recompute the partials
         const int nb = 256;
-        hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nb), dim3(256), 0, stream, ld->grads, a.n, a.grad_scale,
-                           ws.normpart);
+        hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nb), dim3(256), 0, stream, a.g, a.n, a.grad_scale, pl.ws.normpart);
         PRISM_CHECK_LAUNCH();
         a.n_slots = nb;
     }
@@ -912,16 +663,15 @@ static int prepare_norm(const prism_learner_desc *ld, const IqnWs &ws, AdamArgs 
 }
 
 static int clip_step(const prism_learner_desc *ld, const prism_opt_hyper *opt, prism_stream_t stream_) {
-    int rc = check_learner(ld);
+    LearnerPlan pl;
+    int rc = check_learner(ld, pl);
     if (rc) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    IqnWs ws;
-    carve_iqn(&ld->dims, ld->batch, ld->workspace, &ws, nullptr, nullptr);
     AdamArgs a;
-    fill_adam_args(ld, ws, a);
+    fill_adam_args(ld, pl.ws, a);
     const int kind = opt ? opt->kind : PRISM_OPT_ADAM;
     if (opt) apply_opt(opt, a);
-    rc = prepare_norm(ld, ws, a, stream);
+    rc = prepare_norm(pl, a, stream);
     if (rc) return rc;
     {
         ProfileScope ps_(K_CLIP_ADAM, stream);
@@ -953,7 +703,8 @@ static int check_replay_for_step(const prism_learner_desc *ld, const prism_repla
 extern "C" int prism_step_front(const prism_learner_desc *ld, const prism_replay_desc *rp, int64_t size,
                                 const float *mass, uint64_t seed, uint64_t offset, float beta, int64_t *out_index,
                                 float *out_weight, prism_stream_t stream_) {
-    int rc = check_learner(ld);
+    LearnerPlan pl;
+    int rc = check_learner(ld, pl);
     if (rc) return rc;
     rc = check_replay_for_step(ld, rp);
     if (rc) return rc;
@@ -961,7 +712,7 @@ extern "C" int prism_step_front(const prism_learner_desc *ld, const prism_replay
     PRISM_CHECK_ARG(out_index && (rp->tree == nullptr || out_weight), "null outputs");
     hipStream_t stream = (hipStream_t)stream_;
     IqnArgs a;
-    fill_iqn_args(ld, a);
+    fill_iqn_args(ld, pl, a);
     FrontArgs f;
     f.size = size;
     f.mass = mass;
@@ -989,19 +740,18 @@ extern "C" int prism_step_front(const prism_learner_desc *ld, const prism_replay
 
 static int step_back(const prism_learner_desc *ld, const prism_opt_hyper *opt, const prism_replay_desc *rp, const int64_t *index,
                      float alpha, float eps, prism_stream_t stream_) {
-    int rc = check_learner(ld);
+    LearnerPlan pl;
+    int rc = check_learner(ld, pl);
     if (rc) return rc;
     rc = check_replay_for_step(ld, rp);
     if (rc) return rc;
     PRISM_CHECK_ARG(index != nullptr, "null index");
     hipStream_t stream = (hipStream_t)stream_;
-    IqnWs ws;
-    carve_iqn(&ld->dims, ld->batch, ld->workspace, &ws, nullptr, nullptr);
     AdamArgs a;
-    fill_adam_args(ld, ws, a);
+    fill_adam_args(ld, pl.ws, a);
     const int kind = opt ? opt->kind : PRISM_OPT_ADAM;
     if (opt) apply_opt(opt, a);
-    rc = prepare_norm(ld, ws, a, stream);
+    rc = prepare_norm(pl, a, stream);
     if (rc) return rc;
     BackArgs k;
     k.index = index;
@@ -1010,32 +760,33 @@ static int step_back(const prism_learner_desc *ld, const prism_opt_hyper *opt, c
     k.alpha = alpha;
     k.eps = eps;
     k.take_abs = 1;
-    k.use_per = rp->tree != nullptr && !ld->fused_replay;   // already written back beside the backward pass
+    // fused_replay set: the writeback belongs to the learner's launches (post, finished below where it is split).  That holds
+    // for fused_replay with a NULL fused_index too, where nothing rides along: then nobody writes priorities back.
+    k.use_per = rp->tree != nullptr && !ld->fused_replay;
     k.plan = nullptr;
     k.sib = nullptr;
     k.sib_state = nullptr;
-    if (ld->fused_replay && ld->fused_replay->tree && ld->fused_index && split_writeback(ld)) {
-        k.plan = reinterpret_cast<const int4 *>(ws.wb_plan);
-        k.sib = reinterpret_cast<const float2 *>(ws.sib);
-        k.sib_state = ws.ticket + 3;
+    if (pl.writeback_rides && pl.split_writeback) {
+        k.plan = reinterpret_cast<const int4 *>(pl.ws.wb_plan);
+        k.sib = reinterpret_cast<const float2 *>(pl.ws.sib);
+        k.sib_state = pl.ws.ticket + 3;
     }
     k.rng = ld->rng_counters;
-    const int maxT = ld->dims.n_tau > ld->dims.n_tau_next ? ld->dims.n_tau : ld->dims.n_tau_next;
     k.inc_per = (uint64_t)ld->batch;
-    k.inc_tau = (uint64_t)3 * maxT * ld->batch;
-    if (kind == PRISM_OPT_ADAM && tail_fused(ld)) {          // (check_opt refused fuse_tail with the other kinds)
+    k.inc_tau = (uint64_t)3 * pl.maxT * ld->batch;
+    if (kind == PRISM_OPT_ADAM && tail_fused(pl)) {          // (check_opt refused fuse_tail with the other kinds)
         // single GPU: gradient reduction + clip + Adam + writeback in one launch
         IqnArgs ia;
-        fill_iqn_args(ld, ia);
+        fill_iqn_args(ld, pl, ia);
         TailArgs t;
         t.adam = a;
-        t.barrier = reinterpret_cast<unsigned long long *>(ws.ticket + 4);
-        t.status = ws.ticket + PRISM_WS_STATUS_WORD;
+        t.barrier = reinterpret_cast<unsigned long long *>(pl.ws.ticket + 4);
+        t.status = pl.ws.ticket + PRISM_WS_STATUS_WORD;
         t.host_status = ld->host_status;
         t.rng = k.rng;
         t.inc_per = k.inc_per;
         t.inc_tau = k.inc_tau;
-        rc = launch_post(ld, ia, &t, stream);
+        rc = launch_post(ld, pl, ia, &t, stream);
         if (rc) return rc;
         if (k.use_per) {          // prioritised replay that is not riding in the learner's launches: its own update
             launch_per_update(*rp, index, ld->out_td, ld->batch, alpha, eps, 1, stream);

@@ -68,6 +68,110 @@ def test_argument_checks_without_device(lib):
     assert lib.prism_learner_supported(ctypes.byref(dims), 255) == -3                # B*T not a multiple of 16
 
 
+def _fake_learner_desc(lib, cfg_index=2, batch=32):
+    """A descriptor every check accepts, over buffers that do not exist (16-byte-aligned made-up addresses): each case of the
+    test below breaks ONE condition of it, so the call is refused before anything touches a device."""
+    from prism_amd import _native as N
+    from prism_amd.agents.hip_agent import model_dims
+    from prism_amd.config import baseline_config
+    ld = N.LearnerDesc()
+    ld.dims = model_dims(baseline_config(cfg_index), 4, 6)
+    for f, _ in N.ParamOffsets._fields_:
+        setattr(ld.off, f, 0)
+    ld.off.n_params = 1 << 20
+    ld.batch = batch
+    addr = 0x10000000
+    for f in ("params", "grads", "adam_m", "adam_v", "adam_step", "obs", "next_obs", "reward", "nonterminal", "gamma", "action",
+              "out_td", "out_scalars", "workspace"):
+        setattr(ld, f, addr)
+        addr += 0x1000000
+    if ld.dims.has_target:
+        ld.target_params = addr
+    ld.workspace_bytes = lib.prism_learner_workspace_bytes(ctypes.byref(ld.dims), batch)
+    assert ld.workspace_bytes > 0
+    ld.hyper.lr, ld.hyper.beta1, ld.hyper.beta2, ld.hyper.eps = 1e-3, 0.9, 0.999, 1e-8
+    ld.hyper.max_grad_norm, ld.hyper.grad_scale = 10.0, 1.0
+    rp = N.ReplayDesc()
+    rp.capacity, rp.tree_capacity, rp.obs_elems, rp.n_step = 4096, 4096, 100 * ld.dims.in_channels, 3
+    return ld, rp
+
+
+def _set(**fields):
+    def edit(ld, rp, opt):
+        for k, v in fields.items():
+            obj, _, name = k.rpartition("__")
+            setattr({"": ld, "dims": ld.dims, "off": ld.off, "rp": rp, "opt": opt}[obj], name, v)
+    return edit
+
+
+# (entry point, configuration, the one edit, return code, text): c3 = IQN alone, c4 = IQN + ten two-layer heads (the two
+# Q-head offset checks need a model with heads).  "learner" = prism_learner_fwd_bwd, "opt" = prism_learner_clip_step,
+# "back" / "back_opt" / "front" = prism_step_back / prism_step_back_opt / prism_step_front.
+REFUSALS = [
+    ("learner", 2, None, -1, b"check_learner: null descriptor"),
+    ("learner", 2, _set(dims__embed_dim=512), -3, b"model dims / batch not covered by the HIP kernels (need E=1024; IQN: K=64"),
+    ("learner", 2, _set(batch=33), -3, b"not covered by the HIP kernels"),
+    ("learner", 2, _set(params=None), -1, b"check_learner: null parameter buffers"),
+    ("learner", 2, _set(adam_step=None), -1, b"check_learner: null parameter buffers"),
+    ("learner", 2, _set(dims__has_target=1), -1, b"check_learner: has_target without target_params"),
+    ("learner", 2, lambda ld, rp, opt: setattr(ld, "workspace_bytes", ld.workspace_bytes - 1), -1, b"check_learner: workspace too small"),
+    ("learner", 2, _set(workspace=None), -1, b"check_learner: workspace too small"),
+    ("learner", 2, lambda ld, rp, opt: setattr(ld, "workspace", ld.workspace + 8), -1, b"check_learner: workspace must be 16-byte aligned"),
+    ("learner", 2, lambda ld, rp, opt: setattr(ld, "grads", ld.grads + 4), -1,
+     b"check_learner: parameter / gradient / Adam buffers must be 16-byte aligned"),
+    ("learner", 2, _set(off__n_params=0), -1, b"check_learner: n_params / phi_w offset alignment"),
+    ("learner", 2, _set(off__phi_w=2), -1, b"check_learner: n_params / phi_w offset alignment"),
+    ("learner", 2, _set(off__iqn_w1=-1), -1, b"check_learner: IQN parameter offsets missing"),
+    ("learner", 2, _set(off__iqn_ln2_g=-1), -1, b"check_learner: IQN parameter offsets missing"),
+    ("learner", 3, _set(off__head_base=-1), -1, b"check_learner: Q-head parameter offsets missing"),
+    ("learner", 3, _set(off__h_w2=-1), -1, b"check_learner: two-layer Q-head parameter offsets missing"),
+    ("learner", 2, _set(obs=None), -1, b"check_learner: null batch arrays"),
+    ("learner", 2, _set(action=None), -1, b"check_learner: null batch arrays"),
+    ("learner", 2, _set(out_td=None), -1, b"check_learner: null outputs"),
+    ("learner", 2, _set(out_scalars=None), -1, b"check_learner: null outputs"),
+    ("clip_adam", 2, _set(grads=None), -1, b"check_learner: null parameter buffers"),
+    ("opt", 2, None, -1, b"check_opt: null descriptor"),
+    ("opt", 2, "null opt", -1, b"check_opt: null optimizer hyper-parameters"),
+    ("opt", 2, _set(opt__kind=3), -1, b"check_opt: optimizer kind must be PRISM_OPT_ADAM, PRISM_OPT_RMSPROP or PRISM_OPT_SGD"),
+    ("opt", 2, _set(opt__kind=1, fuse_tail=1), -3,
+     b"check_opt: the fused tail (fuse_tail != 0) is built for Adam only; pass fuse_tail = 0 with RMSprop / SGD"),
+    ("back_opt", 2, _set(opt__kind=2, fuse_tail=1), -3, b"built for Adam only"),
+    ("opt", 2, _set(opt__kind=1, out_td=None), -1, b"check_learner: null outputs"),
+    ("back", 2, "null rp", -1, b"check_replay_for_step: null replay descriptor"),
+    ("front", 2, "null rp", -1, b"check_replay_for_step: null replay descriptor"),
+    ("back", 2, _set(rp__obs_elems=300), -1, b"check_replay_for_step: replay obs_elems must equal 10*10*C"),
+    ("front", 2, _set(rp__obs_elems=401), -1, b"check_replay_for_step: replay obs_elems must equal 10*10*C"),
+    ("back", 2, _set(rp__n_step=0), -1, b"check_replay_for_step: n_step out of range"),
+    ("back_opt", 2, _set(rp__n_step=16), -1, b"check_replay_for_step: n_step out of range"),
+    ("back", 2, _set(workspace_bytes=16), -1, b"check_learner: workspace too small"),
+    ("back", 2, "null index", -1, b"step_back: null index"),
+]
+
+
+@pytest.mark.parametrize("case", range(len(REFUSALS)))
+def test_learner_refusals_without_device(lib, case):
+    """Every refusal of check_learner, check_opt and check_replay_for_step that needs no device: return code and text.  Each
+    call fails a check, so no HIP call is reached."""
+    from prism_amd import _native as N
+    entry, cfg_index, edit, want_rc, want_text = REFUSALS[case]
+    ld, rp = _fake_learner_desc(lib, cfg_index)
+    opt = N.OptHyper(kind=N.OPT_ADAM, lr=1e-3, alpha=0.99, eps=1e-8)
+    if callable(edit):
+        edit(ld, rp, opt)
+    p_ld = None if edit is None else ctypes.byref(ld)
+    p_opt = None if edit == "null opt" else ctypes.byref(opt)
+    p_rp = None if edit == "null rp" else ctypes.byref(rp)
+    index = None if edit == "null index" else 0x40000000
+    rc = {"learner": lambda: lib.prism_learner_fwd_bwd(p_ld, None),
+          "clip_adam": lambda: lib.prism_learner_clip_adam(p_ld, None),
+          "opt": lambda: lib.prism_learner_clip_step(p_ld, p_opt, None),
+          "back": lambda: lib.prism_step_back(p_ld, p_rp, index, 0.5, 1e-6, None),
+          "back_opt": lambda: lib.prism_step_back_opt(p_ld, p_opt, p_rp, index, 0.5, 1e-6, None),
+          "front": lambda: lib.prism_step_front(p_ld, p_rp, 100, None, 1, 0, 0.4, index, index, None)}[entry]()
+    assert rc == want_rc, (rc, lib.prism_last_error())
+    assert want_text in lib.prism_last_error(), lib.prism_last_error()
+
+
 def test_product_never_imports_oracle_and_has_no_cpu_path():
     import subprocess
     import sys
