@@ -51,6 +51,11 @@ extern "C" {
 #define PRISM_WS_STATUS_COLLECTIVE_TIMEOUT 2u /* a direct all-reduce wait gave up (prism_direct_desc.poison): clip + Adam are skipped */
 #define PRISM_STATUS_NONPOSITIVE_PSUM 1
 #define PRISM_STATUS_NONPOSITIVE_PMIN 2
+#define PRISM_STATUS_INGEST_DUP_STREAM 4   /* prism_replay_ingest: a stream id repeated in one call or outside the table */
+
+/* prism_replay_ingest obs_kind */
+#define PRISM_OBS_F32 0
+#define PRISM_OBS_U8 1     /* uint8 / bool observations, widened to fp32 on the device */
 
 typedef void *prism_stream_t;
 
@@ -99,6 +104,31 @@ int prism_replay_init(const prism_replay_desc *rp, prism_stream_t stream);
 int prism_replay_insert(const prism_replay_desc *rp, int32_t n, const int32_t *slots,
                         const float *obs, const float *succ_obs, const float *reward,
                         const int32_t *action, const uint8_t *flags, const int32_t *prev_slot,
+                        float alpha, float eps, prism_stream_t stream);
+
+/* One step of a vectorised collector: n transitions of n DISTINCT environment streams, applied in
+ * order i = 0..n-1 with exactly the result of n one-row prism_replay_insert calls -- in one launch and
+ * without the host resolving any predecessor (the per-row bookkeeping of
+ * multiprocessing_experience_collection/collector_process_interface.py:154-169 + TimestepBuffer.extend).
+ *   slot of row i      (first_slot + i) % capacity; `serial0` = rows ever written to this ring since
+ *                      init / empty / bulk load, serial0 % capacity == first_slot, 1 <= n <= capacity.
+ *   obs, next_obs      [n][obs_elems], fp32 (obs_kind PRISM_OBS_F32) or uint8 (PRISM_OBS_U8).
+ *   flags              DONE if done[i], TRUNC if truncated[i], HAS_NEXT if truncated[i] or not done[i];
+ *                      the successor row is next_obs[i] when HAS_NEXT, zeros otherwise.
+ *   stream_ids         stream of row i, in [0, n_streams); NULL: row i is stream i (needs n <= n_streams).
+ *   stream_tab         [n_streams] int64, device, owned by the caller, -1 = no open row: the write serial
+ *                      w of the stream's open row.  Row i links back to slot w % capacity iff
+ *                      0 < serial0 + i - w < capacity (a slot is reused exactly every `capacity` writes);
+ *                      afterwards the entry is serial0 + i if not done[i] and not truncated[i], else -1.
+ *                      1 <= n_streams <= 65536.
+ * Overwritten slots detach their old neighbours and every written slot gets the default priority, as
+ * prism_replay_insert.  A stream id that repeats within the call (or lies outside the table) cannot be
+ * refused by a call that never reads device memory on the host: its rows are stored UNLINKED, the
+ * stream is closed and the sticky bit PRISM_STATUS_INGEST_DUP_STREAM is set in rp->status. */
+int prism_replay_ingest(const prism_replay_desc *rp, int32_t n, int64_t first_slot, int64_t serial0,
+                        const void *obs, const void *next_obs, int32_t obs_kind, const float *reward,
+                        const int32_t *action, const uint8_t *done, const uint8_t *truncated,
+                        const int32_t *stream_ids, int64_t *stream_tab, int32_t n_streams,
                         float alpha, float eps, prism_stream_t stream);
 
 /* PrioritizedSampler.sample (called at timestep_buffer.py:37): p_sum/p_min = query(0,size);

@@ -14,7 +14,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "prism_hip.h")
 PRISM_OK, PRISM_ERR_INVALID, PRISM_ERR_HIP, PRISM_ERR_UNSUPPORTED = 0, -1, -2, -3
 PRISM_MAX_NSTEP = 15
 FLAG_DONE, FLAG_TRUNC, FLAG_HAS_NEXT = 1, 2, 4
-STATUS_NONPOSITIVE_PSUM, STATUS_NONPOSITIVE_PMIN = 1, 2
+STATUS_NONPOSITIVE_PSUM, STATUS_NONPOSITIVE_PMIN, STATUS_INGEST_DUP_STREAM = 1, 2, 4
+OBS_F32, OBS_U8 = 0, 1
+INGEST_MAX_STREAMS = 65536
 WS_STATUS_WORD, WS_STATUS_BARRIER_TIMEOUT, WS_STATUS_COLLECTIVE_TIMEOUT = 7, 1, 2
 GEMM_MODES = {"auto": 0, "fp32": 1, "bf16x3": 2}
 ACT_WEIGHTS_CURRENT = 1
@@ -97,6 +99,8 @@ SIGNATURES = {
     "prism_replay_init": (ctypes.c_int, [_P(ReplayDesc), c_vp]),
     "prism_replay_insert": (ctypes.c_int, [_P(ReplayDesc), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                             c_f32, c_f32, c_vp]),
+    "prism_replay_ingest": (ctypes.c_int, [_P(ReplayDesc), c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                            c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_vp]),
     "prism_per_sample": (ctypes.c_int, [_P(ReplayDesc), c_i64, c_i32, c_vp, c_u64, c_u64, c_f32, c_vp, c_vp,
                                          c_vp]),
     "prism_uniform_sample": (ctypes.c_int, [c_i64, c_i32, c_u64, c_u64, c_vp, c_vp]),

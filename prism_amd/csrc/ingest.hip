@@ -1,0 +1,64 @@
+// Host entry point of the vectorised producer seam (C ABI in include/prism_hip.h).
+#include "ingest_kernels.h"
+
+using namespace prism;
+
+static int check_ingest_ring(const prism_replay_desc *rp) {
+    PRISM_CHECK_ARG(rp != nullptr, "null descriptor");
+    PRISM_CHECK_ARG(rp->capacity > 0 && rp->capacity < (1ll << 31), "capacity out of range");
+    int64_t cap = 1;
+    while (cap <= rp->capacity) cap <<= 1;
+    PRISM_CHECK_ARG(rp->tree_capacity == cap, "tree_capacity must be the smallest power of two > capacity");
+    PRISM_CHECK_ARG(!rp->tree || cap <= (1ll << TREE_MAX_LEVELS), "prioritized capacity above 2^24 - 1 rows");
+    PRISM_CHECK_ARG(rp->obs_elems > 0, "obs_elems");
+    PRISM_CHECK_ARG(rp->obs && rp->succ_obs && rp->reward && rp->action && rp->flags && rp->link && rp->back,
+                    "null ring array");
+    PRISM_CHECK_ARG(rp->per_state && rp->status, "null per_state/status");
+    PRISM_CHECK_ARG((reinterpret_cast<uintptr_t>(rp->tree) & 15) == 0, "tree must be 16-byte aligned");
+    return PRISM_OK;
+}
+
+extern "C" int prism_replay_ingest(const prism_replay_desc *rp, int32_t n, int64_t first_slot, int64_t serial0,
+                                   const void *obs, const void *next_obs, int32_t obs_kind, const float *reward,
+                                   const int32_t *action, const uint8_t *done, const uint8_t *truncated,
+                                   const int32_t *stream_ids, int64_t *stream_tab, int32_t n_streams, float alpha,
+                                   float eps, prism_stream_t stream) {
+    int rc = check_ingest_ring(rp);
+    if (rc) return rc;
+    PRISM_CHECK_ARG(n >= 1 && n <= rp->capacity, "n must be in [1, capacity]");
+    PRISM_CHECK_ARG(n_streams >= 1 && n_streams <= INGEST_MAX_STREAMS, "n_streams must be in [1, 65536]");
+    PRISM_CHECK_ARG(obs_kind == PRISM_OBS_F32 || obs_kind == PRISM_OBS_U8,
+                    "obs_kind must be PRISM_OBS_F32 or PRISM_OBS_U8");
+    PRISM_CHECK_ARG(first_slot >= 0 && first_slot < rp->capacity, "first_slot must be in [0, capacity)");
+    PRISM_CHECK_ARG(serial0 >= 0 && serial0 % rp->capacity == first_slot,
+                    "serial0 must be >= 0 and serial0 % capacity == first_slot");
+    PRISM_CHECK_ARG(obs && next_obs && reward && action && done && truncated, "null transition array");
+    PRISM_CHECK_ARG(stream_tab != nullptr, "null stream_tab");
+    PRISM_CHECK_ARG(stream_ids != nullptr || n <= n_streams, "stream_ids NULL (row i is stream i) needs n <= n_streams");
+    IngestArgs a;
+    a.n = n;
+    a.n_streams = n_streams;
+    a.obs_kind = obs_kind;
+    const uintptr_t src = reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(next_obs);
+    const uintptr_t dst = reinterpret_cast<uintptr_t>(rp->obs) | reinterpret_cast<uintptr_t>(rp->succ_obs);
+    a.vec = (rp->obs_elems & 3) == 0 && (dst & 15) == 0 && (src & (obs_kind == PRISM_OBS_F32 ? 15 : 3)) == 0;
+    a.first_slot = first_slot;
+    a.serial0 = serial0;
+    a.obs = obs;
+    a.next_obs = next_obs;
+    a.reward = reward;
+    a.action = action;
+    a.done = done;
+    a.truncated = truncated;
+    a.stream_ids = stream_ids;
+    a.stream_tab = stream_tab;
+    a.alpha = alpha;
+    a.eps = eps;
+    const int threads = n >= 1024 ? 1024 : ((n + 127) / 128) * 128;
+    const int per_wg = threads / INGEST_ROW_THREADS;
+    int row_wgs = (n + per_wg - 1) / per_wg;
+    if (row_wgs > INGEST_MAX_ROW_WGS) row_wgs = INGEST_MAX_ROW_WGS;
+    hipLaunchKernelGGL(replay_ingest_kernel, dim3(1 + row_wgs), dim3(threads), 0, (hipStream_t)stream, *rp, a);
+    PRISM_CHECK_LAUNCH();
+    return PRISM_OK;
+}

@@ -1,0 +1,222 @@
+// Device code of the vectorised producer seam: one step of N environment streams -> ring rows, links and default
+// priorities in ONE launch (prism_replay_ingest, include/prism_hip.h).  Row semantics as the reference's collector
+// derives them (/root/reference/multiprocessing_experience_collection/collector_process_interface.py:154-169) and as
+// HipReplayBuffer.extend() restates them row by row; the block routines come from replay_kernels.h.
+//
+// Roles by workgroup, no data shared between them (so no cross-workgroup wait):
+//   workgroup 0        plan (predecessor of every row from the stream table) + link + default priority
+//   workgroups 1 ..    row store: copy / widen the observations, reward, action, flags
+// The stream table holds, per stream, the WRITE SERIAL of the stream's open row (or -1).  A ring slot is reused exactly
+// every `capacity` writes, so "the open row is still in the ring" is `serial0 + i - w < capacity` and its slot is
+// `w % capacity`: no per-slot owner array, no host dict.
+#pragma once
+#include "replay_kernels.h"
+
+namespace prism {
+
+constexpr int INGEST_MAX_STREAMS = 65536;
+constexpr int INGEST_ROW_THREADS = 128;             // threads that share one row in the row-store role
+constexpr int INGEST_MAX_ROW_WGS = 2048;
+// LDS of the plan workgroup: two bitmaps over the stream ids (seen in this call / seen twice), dead before the tree
+// writer takes the pool over (a workgroup barrier separates the two).
+constexpr unsigned IG_PLAN = 8u;
+constexpr LdsRegion IG_SEEN{0, INGEST_MAX_STREAMS / 8, IG_PLAN};
+constexpr LdsRegion IG_DUP{INGEST_MAX_STREAMS / 8, INGEST_MAX_STREAMS / 8, IG_PLAN};
+constexpr LdsRegion IG_REGIONS[] = {TW_SORTED, TW_VAL, TW_PART, TW_KEYS, TW_REC, TW_DENSE, IG_SEEN, IG_DUP};
+static_assert(lds_layout_ok(IG_REGIONS, TREE_WRITE_LDS_BYTES), "ingest: the bitmaps do not fit the tree writer's pool");
+
+struct IngestArgs {
+    int32_t n, n_streams, obs_kind, vec;            // vec: 16-byte (fp32) / 4-byte (uint8) row accesses are aligned
+    int64_t first_slot, serial0;
+    const void *obs, *next_obs;                     // [n][obs_elems] fp32 (obs_kind 0) or uint8 (obs_kind 1)
+    const float *reward;
+    const int32_t *action;
+    const uint8_t *done, *truncated;
+    const int32_t *stream_ids;                      // NULL: row i belongs to stream i
+    int64_t *stream_tab;                            // [n_streams]
+    float alpha, eps;
+};
+
+static __global__ __launch_bounds__(1024) void replay_ingest_kernel(prism_replay_desc rp, IngestArgs a) {
+    __shared__ __attribute__((aligned(16))) char s_pool[TREE_WRITE_LDS_BYTES];
+    __shared__ int s_serial;
+    const int tid = threadIdx.x, bd = blockDim.x;
+    const int n = a.n;
+    const int64_t cap = rp.capacity, first = a.first_slot;
+
+    if (blockIdx.x != 0) {
+        // ---- row store: INGEST_ROW_THREADS threads per row, blockDim / INGEST_ROW_THREADS rows per workgroup and trip
+        const int O = rp.obs_elems;
+        const int per_wg = bd / INGEST_ROW_THREADS, lane = tid % INGEST_ROW_THREADS;
+        const int64_t stride = (int64_t)(gridDim.x - 1) * per_wg;
+        for (int64_t i = (int64_t)(blockIdx.x - 1) * per_wg + tid / INGEST_ROW_THREADS; i < n; i += stride) {
+            const int64_t s = (first + i) % cap;
+            const bool done = a.done[i] != 0, trunc = a.truncated[i] != 0;
+            const bool has_next = trunc || !done;
+            float *d0 = rp.obs + s * O, *d1 = rp.succ_obs + s * O;
+            if (a.obs_kind == 0) {
+                const float *s0 = static_cast<const float *>(a.obs) + i * O;
+                const float *s1 = static_cast<const float *>(a.next_obs) + i * O;
+                if (a.vec) {
+                    for (int k = lane; k < O / 4; k += INGEST_ROW_THREADS) {
+                        const float4 v0 = reinterpret_cast<const float4 *>(s0)[k];
+                        float4 v1 = make_float4(0.f, 0.f, 0.f, 0.f);
+                        if (has_next) v1 = reinterpret_cast<const float4 *>(s1)[k];
+                        reinterpret_cast<float4 *>(d0)[k] = v0;
+                        reinterpret_cast<float4 *>(d1)[k] = v1;
+                    }
+                } else {
+                    for (int k = lane; k < O; k += INGEST_ROW_THREADS) {
+                        d0[k] = s0[k];
+                        d1[k] = has_next ? s1[k] : 0.f;
+                    }
+                }
+            } else {
+                const uint8_t *s0 = static_cast<const uint8_t *>(a.obs) + i * O;
+                const uint8_t *s1 = static_cast<const uint8_t *>(a.next_obs) + i * O;
+                if (a.vec) {
+                    for (int k = lane; k < O / 4; k += INGEST_ROW_THREADS) {
+                        const uint32_t w0 = reinterpret_cast<const uint32_t *>(s0)[k];
+                        uint32_t w1 = 0u;
+                        if (has_next) w1 = reinterpret_cast<const uint32_t *>(s1)[k];
+                        reinterpret_cast<float4 *>(d0)[k] = make_float4((float)(w0 & 255u), (float)((w0 >> 8) & 255u),
+                                                                        (float)((w0 >> 16) & 255u), (float)(w0 >> 24));
+                        reinterpret_cast<float4 *>(d1)[k] = make_float4((float)(w1 & 255u), (float)((w1 >> 8) & 255u),
+                                                                        (float)((w1 >> 16) & 255u), (float)(w1 >> 24));
+                    }
+                } else {
+                    for (int k = lane; k < O; k += INGEST_ROW_THREADS) {
+                        d0[k] = (float)s0[k];
+                        d1[k] = has_next ? (float)s1[k] : 0.f;
+                    }
+                }
+            }
+            if (lane == 0) {
+                rp.reward[s] = a.reward[i];
+                rp.action[s] = a.action[i];
+                rp.flags[s] = (uint8_t)((done ? PRISM_FLAG_DONE : 0u) | (trunc ? PRISM_FLAG_TRUNC : 0u) |
+                                        (has_next ? PRISM_FLAG_HAS_NEXT : 0u));
+            }
+        }
+        return;
+    }
+
+    // ---- plan + link + default priority: one workgroup ----------------------------------------------------------------
+    uint32_t *s_seen = reinterpret_cast<uint32_t *>(s_pool + IG_SEEN.off);
+    uint32_t *s_dup = reinterpret_cast<uint32_t *>(s_pool + IG_DUP.off);
+    const int32_t *ids = a.stream_ids;
+    const int n_streams = a.n_streams;
+    const int64_t serial0 = a.serial0;
+    int64_t *tab = a.stream_tab;
+    if (tid == 0) s_serial = 0;
+    if (ids) {                                                       // (identity ids cannot repeat: no bitmap pass)
+        for (int w = tid; w < (n_streams + 31) >> 5; w += bd) {
+            s_seen[w] = 0u;
+            s_dup[w] = 0u;
+        }
+        __syncthreads();
+        bool flag = false;
+        for (int i = tid; i < n; i += bd) {
+            const int32_t sid = ids[i];
+            if ((uint32_t)sid >= (uint32_t)n_streams) {              // outside the table: stored unlinked, table untouched
+                flag = true;
+                continue;
+            }
+            const uint32_t bit = 1u << (sid & 31);
+            if (atomicOr(&s_seen[sid >> 5], bit) & bit) {
+                atomicOr(&s_dup[sid >> 5], bit);
+                flag = true;
+            }
+        }
+        if (flag) atomicOr(rp.status, PRISM_STATUS_INGEST_DUP_STREAM);
+    }
+    __syncthreads();
+    // stream of row i, or -1 when the row is stored unlinked (id outside the table / id repeated in this call)
+    auto stream_of = [&](int i) __attribute__((always_inline)) -> int32_t {
+        if (!ids) return i;
+        const int32_t sid = ids[i];
+        if ((uint32_t)sid >= (uint32_t)n_streams) return -1;
+        return (s_dup[sid >> 5] >> (sid & 31)) & 1u ? -1 : sid;
+    };
+    // slot of the row's predecessor as the table has it on entry, or -1
+    auto pred_of = [&](int i) __attribute__((always_inline)) -> int32_t {
+        const int32_t sid = stream_of(i);
+        if (sid < 0) return -1;
+        const int64_t w = tab[sid];
+        if (w < 0 || w >= serial0 + i) return -1;
+        if (serial0 + i - w >= cap) return -1;                       // its slot has been written again since
+        return (int32_t)(w % cap);
+    };
+    {
+        bool bad = false;
+        for (int i = tid; i < n; i += bd) {
+            const int32_t p = pred_of(i);
+            if (p >= 0) {
+                const int64_t pos = ((int64_t)p - first + cap) % cap;
+                // predecessor overwritten later in this call.  (pos < i cannot happen: a live predecessor has
+                // serial0 + i - w < cap, so the row of this call that reuses its slot, w + cap - serial0, comes after row i.)
+                if (pos < n && pos >= i) bad = true;
+            }
+        }
+        if (bad) s_serial = 1;
+    }
+    __syncthreads();
+    if (s_serial) {
+        if (tid == 0) {
+            for (int i = 0; i < n; ++i) {                            // the sequential loop itself (replay_link_kernel)
+                const int32_t s = (int32_t)((first + i) % cap);
+                const int32_t b = rp.back[s];
+                if (b >= 0 && rp.link[b] == s) rp.link[b] = -1;
+                const int32_t q = rp.link[s];
+                if (q >= 0 && rp.back[q] == s) rp.back[q] = -1;
+                rp.link[s] = -1;
+                rp.back[s] = -1;
+                const int32_t p = pred_of(i);
+                if (p >= 0) {
+                    rp.link[p] = s;
+                    rp.back[s] = p;
+                }
+            }
+        }
+    } else {
+        for (int i = tid; i < n; i += bd) {                          // A  detach the overwritten rows' old neighbours
+            const int32_t s = (int32_t)((first + i) % cap);
+            const int32_t b = rp.back[s], q = rp.link[s];
+            if (b >= 0 && rp.link[b] == s) rp.link[b] = -1;
+            if (q >= 0 && rp.back[q] == s) rp.back[q] = -1;
+        }
+        __syncthreads();
+        for (int i = tid; i < n; i += bd) {                          // B  reset the slots' own link / back
+            const int32_t s = (int32_t)((first + i) % cap);
+            rp.link[s] = -1;
+            rp.back[s] = -1;
+        }
+        __syncthreads();
+        for (int i = tid; i < n; i += bd) {                          // C  attach each row to its predecessor
+            const int32_t p = pred_of(i);
+            if (p >= 0) {
+                const int32_t s = (int32_t)((first + i) % cap);
+                rp.link[p] = s;
+                rp.back[s] = p;
+            }
+        }
+    }
+    __syncthreads();                                                 // every reader of the table's old state is through
+    for (int i = tid; i < n; i += bd) {                              // D  the stream's open row is this one, or none
+        const int32_t raw = ids ? ids[i] : i;
+        if ((uint32_t)raw >= (uint32_t)n_streams) continue;
+        const bool open = stream_of(i) >= 0 && a.done[i] == 0 && a.truncated[i] == 0;
+        tab[raw] = open ? serial0 + i : -1;                          // (a repeated id: every row of it writes -1)
+    }
+    if (!rp.tree) return;
+    const float prio = pow_alpha(rp.per_state[0] + a.eps, a.alpha);
+    const int pass = min(UPD_MAX, bd);
+    for (int base = 0; base < n; base += pass) {
+        const int cnt = min(pass, n - base);
+        __syncthreads();                                             // bitmaps / previous pass: LDS free
+        const int32_t me = tid < cnt ? (int32_t)((first + base + tid) % cap) : 0;
+        block_tree_write(rp, me, prio, cnt, s_pool);
+    }
+}
+
+}  // namespace prism

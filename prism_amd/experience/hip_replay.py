@@ -94,6 +94,12 @@ class HipReplayBuffer:
         self._slot_id = np.full(self.capacity, -1, np.int64)
         self._n_staged = 0
         self._index = None
+        # vectorised producer seam (extend_batch): rows ever written since init / empty / bulk load (serial % capacity ==
+        # writer cursor), the device table "write serial of each stream's open row", and its pinned staging sets
+        self._serial = 0
+        self._stream_tab = None
+        self._ing = None
+        self._ing_cur = 0
 
     # ------------------------------------------------------------------ allocation
     def _allocate(self, obs_shape):
@@ -182,6 +188,7 @@ class HipReplayBuffer:
         w._cursor = (s + 1) % self.capacity
         self._size = min(self._size + 1, self.capacity)
         self._slot_id[s] = timestep.id
+        self._serial += 1
 
         prev_slot = -1
         rec = self._pending.pop(timestep.id, None)
@@ -235,6 +242,194 @@ class HipReplayBuffer:
             self._stage_ev[self._cur_stage].synchronize()
             self._stage_ev[self._cur_stage] = None
         self._n_staged = 0
+
+    # ------------------------------------------------------------------ vectorised producer seam
+    def _stream_table(self, need):
+        """The device stream table, grown (doubling, -1 = no open row) to hold at least `need` streams."""
+        if need > N.INGEST_MAX_STREAMS:
+            raise ValueError(f"extend_batch: stream_ids must lie in [0, {N.INGEST_MAX_STREAMS})")
+        t = self._stream_tab
+        if t is None or t.numel() < need:
+            size = 64
+            while size < need:
+                size <<= 1
+            new = torch.full((size,), -1, dtype=torch.int64, device=self.device)
+            if t is not None:
+                new[:t.numel()].copy_(t)
+            self._stream_tab = new
+        return self._stream_tab
+
+    def reserve_streams(self, n_streams):
+        """Size the stream table for ids 0 .. n_streams - 1 ahead of time.  Needed only with DEVICE-side ``stream_ids``:
+        the host cannot read them without a sync, so the table cannot grow on their demand (host-side ids and the default
+        numbering grow it by themselves); a device-side id at or above the table's size is stored unlinked and sets the
+        sticky status bit."""
+        if not 1 <= int(n_streams) <= N.INGEST_MAX_STREAMS:
+            raise ValueError(f"reserve_streams: n_streams must be in [1, {N.INGEST_MAX_STREAMS}]")
+        with torch.cuda.device(self.device):
+            self._stream_table(int(n_streams))
+
+    def _reset_streams(self):
+        """After init / empty / bulk load: no stream has an open row, and serial % capacity == writer cursor."""
+        self._serial = self.buffer._writer._cursor
+        if self._stream_tab is not None:
+            self._stream_tab.fill_(-1)
+
+    def _ingest_stage(self, n):
+        """The pinned staging set (and its device twin) the next extend_batch fills: two sets in rotation as in flush(); a
+        set is waited for only when it comes round again.  Views are cached per row count."""
+        O = self.obs_elems
+        if self._ing is None or self._ing[0]["rows"] < n:
+            if self._ing is not None:
+                for st in self._ing:
+                    if st["ev"] is not None:
+                        st["ev"].synchronize()
+            rows = 64
+            while rows < n:
+                rows <<= 1
+
+            def _set():
+                # observations as raw bytes (viewed fp32 or uint8); the five per-row scalars side by side in ONE block:
+                # reward | action | stream id (4 bytes each) | done | truncated (1 each), packed for the row count in use
+                mk = lambda nbytes, **kw: torch.zeros(nbytes, dtype=torch.uint8, **kw)
+                return dict(rows=rows, ev=None, views={},
+                            h_obs=mk(4 * rows * O, pin_memory=True), h_next=mk(4 * rows * O, pin_memory=True),
+                            h_small=mk(14 * rows, pin_memory=True), d_obs=mk(4 * rows * O, device=self.device),
+                            d_next=mk(4 * rows * O, device=self.device), d_small=mk(14 * rows, device=self.device))
+            self._ing = [_set(), _set()]
+            self._ing_cur = 0
+        st = self._ing[self._ing_cur]
+        if st["ev"] is not None:
+            st["ev"].synchronize()
+            st["ev"] = None
+        return st
+
+    @staticmethod
+    def _ingest_views(st, n, O, kind):
+        v = st["views"].get((n, kind))
+        if v is None:
+            ob = n * O * (4 if kind == N.OBS_F32 else 1)
+            odt = torch.float32 if kind == N.OBS_F32 else torch.uint8
+            hs, ds = st["h_small"], st["d_small"]
+            sm = lambda t: dict(reward=t[0:4 * n].view(torch.float32), action=t[4 * n:8 * n].view(torch.int32),
+                                ids=t[8 * n:12 * n].view(torch.int32), done=t[12 * n:13 * n], trunc=t[13 * n:14 * n])
+            h, d = sm(hs), sm(ds)
+            v = dict(h_obs=st["h_obs"][:ob].view(odt).view(n, O), h_next=st["h_next"][:ob].view(odt).view(n, O),
+                     d_obs=st["d_obs"][:ob].view(odt).view(n, O), d_next=st["d_next"][:ob].view(odt).view(n, O),
+                     h_small=hs[:14 * n], d_small=ds[:14 * n], d=d)
+            v["np_obs"], v["np_next"] = v["h_obs"].numpy(), v["h_next"].numpy()
+            v["np"] = {k: t.numpy() for k, t in h.items()}
+            if len(st["views"]) >= 8:                  # (a collector that varies its subset size: keep the cache small)
+                st["views"].clear()
+            st["views"][(n, kind)] = v
+        return v
+
+    def extend_batch(self, obs, next_obs, action, reward, done, truncated, stream_ids=None):
+        """One step of a vectorised collector: row i is the transition (obs[i], action[i], reward[i], next_obs[i],
+        done[i], truncated[i]) of environment stream ``stream_ids[i]`` (None: stream i).  Equal, bit for bit, to the same
+        transitions handed to ``extend()`` as linked ``Timestep`` chains -- one kernel launch, no per-row host work:
+        predecessors come from a device table of each stream's open row.  Stream ids within one call must be distinct.
+
+        NumPy arrays / host tensors travel through pinned staging; device tensors are used in place and nothing
+        synchronises (a repeated id in a DEVICE id array cannot be refused here: its rows are stored unlinked and
+        ``check_status()`` raises; nor can the table grow for them: device-side ids must lie below the table's size, 64 or
+        what ``reserve_streams()`` / earlier calls made it).  ``obs`` / ``next_obs`` may be float32 or bool / uint8 (widened
+        on the device), both of the same class.
+        A stream's row links back to the stream's previous row while the episode goes on (not done, not truncated);
+        ``next_obs`` is kept as the successor observation when truncated or not done.  Returns the first slot."""
+        if not torch.is_tensor(obs):
+            obs = np.asarray(obs)
+        n = int(obs.shape[0])
+        if not 1 <= n <= self.capacity:
+            raise ValueError(f"extend_batch: n = {n} rows must be in [1, capacity = {self.capacity}]")
+        is_dev = lambda x: torch.is_tensor(x) and x.is_cuda
+        host = lambda x: x.numpy() if torch.is_tensor(x) else np.asarray(x)
+        small_int = (torch.bool, torch.uint8) if torch.is_tensor(obs) else (np.bool_, np.uint8)
+        kind = N.OBS_U8 if obs.dtype in small_int else N.OBS_F32
+        if not torch.is_tensor(next_obs):
+            next_obs = np.asarray(next_obs)
+        next_small = next_obs.dtype in ((torch.bool, torch.uint8) if torch.is_tensor(next_obs) else (np.bool_, np.uint8))
+        if next_small != (kind == N.OBS_U8):
+            raise ValueError(f"extend_batch: obs ({obs.dtype}) and next_obs ({next_obs.dtype}) must both be bool / uint8 "
+                             "or both be floating point")
+        ids_host = None
+        if stream_ids is not None and not is_dev(stream_ids):
+            ids_host = host(stream_ids).reshape(-1)
+            if ids_host.shape[0] != n:
+                raise ValueError("extend_batch: stream_ids must hold one id per row")
+            if int(ids_host.min()) < 0 or int(ids_host.max()) >= N.INGEST_MAX_STREAMS:
+                raise ValueError(f"extend_batch: stream_ids must lie in [0, {N.INGEST_MAX_STREAMS})")
+            seen = np.zeros(int(ids_host.max()) + 1, np.bool_)
+            seen[ids_host] = True
+            if int(seen.sum()) != n:
+                raise ValueError("extend_batch: stream_ids must be distinct within one call")
+            need = seen.shape[0]
+        else:
+            if stream_ids is not None and stream_ids.numel() != n:
+                raise ValueError("extend_batch: stream_ids must hold one id per row")
+            need = n if stream_ids is None else max(n, 0 if self._stream_tab is None else self._stream_tab.numel())
+        if self._desc is None:
+            self._allocate(tuple(obs.shape[1:]))
+        self.flush()                                   # rows staged by extend() come first
+        O, dev = self.obs_elems, self.device
+        odt = torch.float32 if kind == N.OBS_F32 else torch.uint8
+        with torch.cuda.device(dev):
+            tab = self._stream_table(need)
+            scalars = dict(reward=reward, action=action, done=done, trunc=truncated)
+            staged = not (is_dev(obs) and is_dev(next_obs) and ids_host is None and all(map(is_dev, scalars.values())))
+            if staged:
+                st = self._ingest_stage(n)
+                v = self._ingest_views(st, n, O, kind)
+
+            def dev_obs(x, key):
+                if is_dev(x):
+                    x = x.reshape(n, O)
+                    x = x.view(torch.uint8) if x.dtype == torch.bool else x
+                    return (x if x.dtype == odt else x.to(odt)).contiguous()
+                np.copyto(v["np_" + key], host(x).reshape(n, O), casting="unsafe")
+                v["d_" + key].copy_(v["h_" + key], non_blocking=True)
+                return v["d_" + key]
+            d_obs, d_next = dev_obs(obs, "obs"), dev_obs(next_obs, "next")
+            sdt = dict(reward=torch.float32, action=torch.int32, done=torch.uint8, trunc=torch.uint8)
+            args, any_host = {}, ids_host is not None
+            for k, x in scalars.items():
+                if is_dev(x):
+                    x = x.reshape(n)
+                    if sdt[k] == torch.uint8 and x.dtype != torch.uint8:
+                        x = x.view(torch.uint8) if x.dtype == torch.bool else (x != 0).view(torch.uint8)
+                    args[k] = (x if x.dtype == sdt[k] else x.to(sdt[k])).contiguous()
+                else:
+                    np.copyto(v["np"][k], host(x).reshape(n), casting="unsafe")
+                    args[k], any_host = v["d"][k], True
+            if ids_host is not None:
+                np.copyto(v["np"]["ids"], ids_host, casting="unsafe")
+                d_ids = v["d"]["ids"]
+            elif stream_ids is not None:
+                d_ids = stream_ids.reshape(-1).to(torch.int32).contiguous()
+            else:
+                d_ids = None
+            if any_host:
+                v["d_small"].copy_(v["h_small"], non_blocking=True)
+            w, smp = self.buffer._writer, self.buffer._sampler
+            first, serial = w._cursor, self._serial
+            N.check(N.lib().prism_replay_ingest(
+                ctypes.byref(self._desc), n, first, serial, N.ptr(d_obs), N.ptr(d_next), kind, N.ptr(args["reward"]),
+                N.ptr(args["action"]), N.ptr(args["done"]), N.ptr(args["trunc"]), N.ptr(d_ids), N.ptr(tab),
+                tab.numel(), smp._alpha, smp._eps, N.current_stream_handle()), "prism_replay_ingest")
+            if staged:
+                st["ev"] = torch.cuda.Event()
+                st["ev"].record()
+                self._ing_cur ^= 1
+        # host mirrors, by arithmetic; the slots get ids from a private (negative) range: no Timestep id matches them
+        cap = self.capacity
+        own = np.arange(-2 - serial, -2 - serial - n, -1, dtype=np.int64)
+        head = min(n, cap - first)
+        self._slot_id[first:first + head] = own[:head]
+        self._slot_id[:n - head] = own[head:]
+        w._cursor = (first + n) % cap
+        self._serial = serial + n
+        self._size = min(self._size + n, cap)
+        return first
 
     @torch.no_grad()
     def sample(self, batch_size=None, return_info=False):
@@ -297,6 +492,9 @@ class HipReplayBuffer:
         bits = int(self.status.item())
         if bits & (N.STATUS_NONPOSITIVE_PSUM | N.STATUS_NONPOSITIVE_PMIN):
             raise RuntimeError("non-positive p_sum / p_min in the priority trees")
+        if bits & N.STATUS_INGEST_DUP_STREAM:
+            raise RuntimeError("extend_batch: a device-side stream_ids array held a repeated or out-of-range id "
+                               "(its rows were stored unlinked)")
 
     def update_priority(self, indices, priorities, take_abs=False):
         if not self.use_per:
@@ -330,6 +528,7 @@ class HipReplayBuffer:
         self.buffer._writer._cursor = 0
         self._pending.clear()
         self._slot_id[:] = -1
+        self._reset_streams()
         if self._desc is not None:
             with torch.cuda.device(self.device):
                 N.check(N.lib().prism_replay_init(ctypes.byref(self._desc), N.current_stream_handle()),
@@ -357,6 +556,7 @@ class HipReplayBuffer:
         self.back[lk[valid].long()] = torch.arange(n, device=self.device, dtype=torch.int32)[valid]
         self._size = ns
         self.buffer._writer._cursor = ns % self.capacity
+        self._reset_streams()
         self._slot_id[:n] = np.arange(n)
         if self.use_per:
             tc = self.tree_capacity
@@ -416,3 +616,4 @@ class HipReplayBuffer:
         if st is not None:
             self.per_state.copy_(st["per_state"])
         self.buffer._writer._cursor = int(st["cursor"]) if st is not None else n % self.capacity
+        self._reset_streams()

@@ -41,6 +41,7 @@ def fill_replay(buffer, n, obs_shape=(10, 10, 4), n_actions=6, seed=0, n_streams
     buffer.back[link[valid]] = idx[valid].to(torch.int32)
     buffer._size = n
     buffer.buffer._writer._cursor = n % buffer.capacity
+    buffer._reset_streams()                  # a bulk load rewrites the ring behind the stream table (extend_batch)
     buffer._slot_id[:n] = np.arange(n)
     if buffer.use_per:
         import ctypes

@@ -1,25 +1,188 @@
-import contextlib, io, os, sys, time
-sys.path.insert(0, "/root/repo")
+"""Host-side rates of the learner loop.
+
+    python tools/host_rate.py                      enqueue / total time of Learner.step() + a cProfile of it (c1)
+    python tools/host_rate.py --mode ingest        one env step's ingestion for N streams: extend() x N + flush() against
+                                                   extend_batch(), host float32 and uint8 arrays, and the whole loop
+                                                   collector -> Agent.forward -> ingest -> Learner.step() both ways
+    --root DIR    import prism_amd from another checkout (a build of the parent commit: only the per-row path exists there)
+    --out FILE    also write the ingest table there
+"""
+import argparse
+import contextlib
+import io
+import os
+import statistics
+import sys
+import time
+import weakref
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--mode", choices=("step", "ingest"), default="step")
+ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ap.add_argument("--out", default=None)
+ap.add_argument("--steps", type=int, default=300)
+ap.add_argument("--rounds", type=int, default=5)
+args = ap.parse_args()
+sys.path.insert(0, os.path.abspath(args.root))
+import numpy as np
 import torch
 from prism_amd.config import baseline_config
 from prism_amd.learner import Learner
 from prism_amd.synthetic import fill_replay
-cfg = baseline_config(0, device="cuda:0", log_to_wandb=False)     # c1: the shortest GPU step (30 us)
-ln = Learner()
-with contextlib.redirect_stdout(io.StringIO()):
-    ln.configure(cfg, obs_shape=(10, 10, 4), n_actions=6)
-ln.time_phases = False
-fill_replay(ln.experience_buffer, ln.experience_buffer.capacity, seed=0)
-for _ in range(200): ln.step()
-torch.cuda.synchronize()
-import cProfile, pstats
-t0 = time.perf_counter()
-for _ in range(3000): ln.step()
-t1 = time.perf_counter()
-torch.cuda.synchronize()
-t2 = time.perf_counter()
-print(f"enqueue {1e6*(t1-t0)/3000:.1f} us/step, total {1e6*(t2-t0)/3000:.1f} us/step")
-pr = cProfile.Profile(); pr.enable()
-for _ in range(2000): ln.step()
-pr.disable(); torch.cuda.synchronize()
-pstats.Stats(pr).sort_stats("cumulative").print_stats(12)
+
+
+def make_learner(i):
+    cfg = baseline_config(i, device="cuda:0", log_to_wandb=False)
+    ln = Learner()
+    with contextlib.redirect_stdout(io.StringIO()):
+        ln.configure(cfg, obs_shape=(10, 10, 4), n_actions=6)
+    ln.time_phases = False
+    return ln
+
+
+def step_mode():
+    ln = make_learner(0)     # c1: the shortest GPU step (30 us)
+    fill_replay(ln.experience_buffer, ln.experience_buffer.capacity, seed=0)
+    for _ in range(200): ln.step()
+    torch.cuda.synchronize()
+    import cProfile, pstats
+    t0 = time.perf_counter()
+    for _ in range(3000): ln.step()
+    t1 = time.perf_counter()
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    print(f"enqueue {1e6*(t1-t0)/3000:.1f} us/step, total {1e6*(t2-t0)/3000:.1f} us/step")
+    pr = cProfile.Profile(); pr.enable()
+    for _ in range(2000): ln.step()
+    pr.disable(); torch.cuda.synchronize()
+    pstats.Stats(pr).sort_stats("cumulative").print_stats(12)
+
+
+class VecStub:
+    """N lockstep environments' worth of transitions from a small pool of observations (the collector's own cost -- stepping
+    environments, building Timestep objects -- is outside every timed window)."""
+
+    def __init__(self, n, dtype, seed=0):
+        self.n, self.rng = n, np.random.default_rng(seed)
+        self.pool = [(self.rng.random((n, 10, 10, 4)) < 0.1).astype(dtype) for _ in range(8)]
+        self.k = 0
+
+    def arrays(self):
+        n, rng = self.n, self.rng
+        self.k += 1
+        done = rng.random(n) < 0.02
+        return (self.pool[self.k % 8], self.pool[(self.k + 1) % 8], rng.integers(0, 6, n).astype(np.int32),
+                rng.standard_normal(n).astype(np.float32), done, np.zeros(n, np.bool_))
+
+    def timesteps(self, steps, ids):
+        """`steps` env steps as linked Timestep chains, the way the reference's collectors hand them to extend()."""
+        from prism_amd.experience import Timestep
+        cur = [Timestep(id=next(ids), obs=self.pool[0][e]) for e in range(self.n)]
+        out = []
+        for _ in range(steps):
+            obs, nxt, act, rew, done, _ = self.arrays()
+            row = []
+            for e in range(self.n):
+                t, node = cur[e], Timestep(id=next(ids), obs=nxt[e])
+                t.obs, t.action, t.reward, t.done, t.truncated = obs[e], int(act[e]), float(rew[e]), bool(done[e]), False
+                if not t.done:
+                    t.next = weakref.ref(node)
+                row.append(t)
+                cur[e] = node
+            out.append(row)
+        return out, cur
+
+
+def timed(fn, steps):
+    """us per env step: host enqueue, and host + device until the queue is empty."""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for k in range(steps):
+        fn(k)
+    t1 = time.perf_counter()
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    return 1e6 * (t1 - t0) / steps, 1e6 * (t2 - t0) / steps
+
+
+def ingest_mode():
+    from prism_amd.experience import HipReplayBuffer
+    has_batch = hasattr(HipReplayBuffer, "extend_batch")
+    lines = [f"# ingestion of one env step of N streams, us per env step (median of {args.rounds} interleaved rounds of "
+             f"{args.steps} steps): host enqueue / until the device queue is empty",
+             f"# extend_batch in this tree: {'yes' if has_batch else 'no (per-row path only)'}",
+             "N     obs      extend()xN+flush()        extend_batch()           ratio (total)"]
+    ids = iter(range(10 ** 12))
+    for n in (1, 4, 16, 64, 256):
+        for dtype in (np.float32, np.uint8):
+            row_buf = HipReplayBuffer(100_000, 32, device="cuda:0", use_per=True)
+            bat_buf = HipReplayBuffer(100_000, 32, device="cuda:0", use_per=True)
+            stub = VecStub(n, dtype)
+            res = {"row": [], "batch": []}
+            for rnd in range(args.rounds + 1):              # round 0 warms both paths up
+                ts, keep = stub.timesteps(args.steps, ids)
+
+                def per_row(k):
+                    for t in ts[k]:
+                        row_buf.extend(t)
+                    row_buf.flush()
+                r = timed(per_row, args.steps)
+                if has_batch:
+                    data = [stub.arrays() for _ in range(args.steps)]
+                    b = timed(lambda k: bat_buf.extend_batch(*data[k]), args.steps)
+                if rnd:
+                    res["row"].append(r)
+                    if has_batch:
+                        res["batch"].append(b)
+            med = lambda v, j: statistics.median(x[j] for x in v)
+            r0, r1 = med(res["row"], 0), med(res["row"], 1)
+            line = f"{n:<5d} {np.dtype(dtype).name:<8s} {r0:9.1f} / {r1:9.1f}"
+            if has_batch:
+                b0, b1 = med(res["batch"], 0), med(res["batch"], 1)
+                line += f"     {b0:9.1f} / {b1:9.1f}     {r1 / b1:6.2f}x"
+            lines.append(line)
+            print(line, flush=True)
+    # the whole loop: stub vector collector -> Agent.forward(obs[N]) -> ingestion -> Learner.step(), c3 (IQN + PER)
+    lines.append("# whole loop, c3: collector stub -> Agent.forward(obs[N]) -> ingest -> Learner.step(); us per iteration (total)")
+    for n in (8, 64):
+        ln = make_learner(2)
+        buf, agent = ln.experience_buffer, ln.agent
+        fill_replay(buf, min(buf.capacity, 50_000), seed=0)
+        stub = VecStub(n, np.float32)
+        res = {"row": [], "batch": []}
+        for rnd in range(3):
+            ts, keep = stub.timesteps(args.steps, ids)
+
+            def loop_rows(k):
+                acts = agent.forward(stub.pool[k % 8]).cpu().numpy()       # the per-row path needs the actions on the host
+                for e, t in enumerate(ts[k]):
+                    t.action = int(acts[e])
+                    buf.extend(t)
+                ln.step(n)
+            r = timed(loop_rows, args.steps)
+            if has_batch:
+                data = [stub.arrays() for _ in range(args.steps)]
+
+                def loop_batch(k):
+                    obs, nxt, _, rew, done, trunc = data[k]
+                    buf.extend_batch(obs, nxt, agent.forward(obs), rew, done, trunc)   # actions stay on the device
+                    ln.step(n)
+                b = timed(loop_batch, args.steps)
+            if rnd:
+                res["row"].append(r)
+                if has_batch:
+                    res["batch"].append(b)
+        line = f"N = {n:<4d} per-row {statistics.median(x[1] for x in res['row']):9.1f}"
+        if has_batch:
+            line += f"     extend_batch {statistics.median(x[1] for x in res['batch']):9.1f}"
+        lines.append(line)
+        print(line, flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    if not torch.cuda.is_available():
+        sys.exit("host_rate.py measures on the GPU: no device found")
+    step_mode() if args.mode == "step" else ingest_mode()
