@@ -1030,6 +1030,52 @@ class HipAgent:
         self.n_updates = state["n_updates"]
         self.train()
 
+    # ------------------------------------------------------------------ exact resume (prism_amd/util/snapshot.py)
+    def _compat_record(self):
+        """What a snapshot must share with the agent it is loaded into: the ``prism_model_dims`` fields, the parameter
+        count, the optimizer kind and where the quantile draws come from."""
+        rec = {name: getattr(self.dims, name) for name, _ in N.ModelDims._fields_}
+        rec.update(n_params=int(self.flat.numel()), optimizer_kind=int(self.optimizer.kind), tau_rng=str(self.tau_rng))
+        return rec
+
+    def _state_part(self):
+        """Part ``agent_resume`` of a snapshot: the Philox positions ``save()`` does not write.  The quantile draws of
+        ``update()`` and of fused steps share one counter space, so their sum is the position."""
+        return dict(n_updates=int(self.n_updates), seed=int(self.seed), tau_rng=str(self.tau_rng),
+                    tau_draws=int(self._draw_offset + self._fused_tau), act_draws=int(self._act_draws),
+                    optimizer_kind=int(self.optimizer.kind))
+
+    def _check_snapshot(self, manifest):
+        from prism_amd.util import snapshot
+        snapshot.check_compat((manifest.get("compat") or {}).get("agent"), self._compat_record(), "HipAgent.load_state")
+
+    def _restore_part(self, directory, part):
+        self.load(directory)
+        self.n_updates, self.seed = int(part["n_updates"]), int(part["seed"])
+        self._draw_offset, self._fused_tau = int(part["tau_draws"]), 0
+        # the device's acting word is seeded from the host count by the next graph call (_forward_graph)
+        self._act_draws, self._act_dev_draws = int(part["act_draws"]), 0
+        self._act_raw = None
+        self._graphs, self._act_graphs, self._act_ptrs, self._act_packed_at = {}, {}, {}, None
+        if self._B is not None:
+            self.rng_counters[:2].zero_()          # {PER draws, tau draws} of fused steps: counted in the host offsets now
+
+    def save_state(self, directory):
+        """``save(directory)`` (the reference's layout: it can still load ``agent/``) plus part ``agent_resume``: with it
+        ``load_state`` puts every random stream of the agent back where it was."""
+        from prism_amd.util import snapshot
+        return snapshot.write_snapshot(directory, {"agent_resume": self._state_part()},
+                                       {"compat": {"agent": self._compat_record()}}, extra=self.save)
+
+    def load_state(self, directory):
+        """Restore a ``save_state`` snapshot into an agent built from the same configuration: what follows is bit-identical
+        to the run that wrote it.  Other model dimensions, optimizer kind or ``tau_rng`` are refused before anything is
+        touched."""
+        from prism_amd.util import snapshot
+        self._check_snapshot(snapshot.read_manifest(directory))
+        parts, _ = snapshot.read_snapshot(directory, ["agent_resume"])
+        self._restore_part(directory, parts["agent_resume"])
+
     @torch.no_grad()
     def log(self, logger):
         self.check_status()

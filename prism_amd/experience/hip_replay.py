@@ -617,3 +617,109 @@ class HipReplayBuffer:
             self.per_state.copy_(st["per_state"])
         self.buffer._writer._cursor = int(st["cursor"]) if st is not None else n % self.capacity
         self._reset_streams()
+
+    # ------------------------------------------------------------------ exact resume (prism_amd/util/snapshot.py)
+    def _compat_record(self):
+        """What a snapshot must share with the buffer it is loaded into."""
+        return dict(capacity=self.capacity, obs_shape=None if self._obs_shape is None else list(self._obs_shape),
+                    n_step=self.n_step, gammas=[float(g) for g in self.gammas], use_per=self.use_per,
+                    mass_rng=str(self.mass_rng))
+
+    def _valid_rows(self):
+        """Rows of the ring arrays that hold anything: all of them once the ring has wrapped, else up to the highest row ever
+        written (link-target rows a reference-format load() placed behind ``_size`` included)."""
+        if self._size >= self.capacity:
+            return self.capacity
+        used = np.flatnonzero(self._slot_id != -1)
+        return max(self._size, int(used[-1]) + 1 if used.size else 0)
+
+    def _state_part(self):
+        """Part ``replay`` of a snapshot: the live ring, its host mirrors and counters, as plain data."""
+        self.flush()
+        if self._desc is None:
+            raise RuntimeError("save_state: the buffer holds nothing yet (no observation shape)")
+        self.check_status()
+        rows, n = self._valid_rows(), self._size
+        obs, succ = self.obs[:rows], self.succ_obs[:rows]
+        # exact as uint8? compared in bit space (-0.0 is not 0), both arrays in one reduction, one D2H sync
+        as_u8 = lambda x: x.clamp(0, 255).to(torch.uint8)
+        exact = lambda x: (as_u8(x).to(torch.float32).view(torch.int32) == x.view(torch.int32)).all()
+        small = rows > 0 and bool((exact(obs) & exact(succ)).item())
+        pack = (lambda x: as_u8(x).cpu()) if small else (lambda x: x.cpu())
+        smp = self.buffer._sampler
+        part = dict(rows=rows, size=n, obs_shape=list(self._obs_shape), cursor=int(self.buffer._writer._cursor),
+                    serial=int(self._serial),
+                    obs_dtype="uint8" if small else "float32", obs=pack(obs), succ_obs=pack(succ),
+                    reward=self.reward[:rows].cpu(), action=self.action[:rows].cpu(), flags=self.flags[:rows].cpu(),
+                    link=self.link[:rows].cpu(), back=self.back[:rows].cpu(), per_state=self.per_state.cpu(),
+                    slot_id=torch.from_numpy(self._slot_id[:rows].copy()),
+                    pending=[[int(k), int(v[0]), int(v[1])] for k, v in self._pending.items()],
+                    stream_tab=None if self._stream_tab is None else self._stream_tab.cpu(),
+                    seed=int(self.seed), draws=int(self._draws + self._fused_draws),
+                    alpha=float(smp._alpha), beta=float(smp._beta), eps=float(smp._eps))
+        if self.use_per:
+            tc = self.tree_capacity
+            part["leaves"] = self.tree[tc:tc + n].cpu()          # {sum, min} of every stored item; the nodes above follow
+        return part
+
+    def _restore_part(self, part, keep_streams=True):
+        rows, n = int(part["rows"]), int(part["size"])
+        dev = self.device
+        if self._desc is None:
+            self._allocate(tuple(int(s) for s in part["obs_shape"]))
+        else:
+            self.empty()
+        O = self.obs_elems
+        for name in ("obs", "succ_obs"):
+            getattr(self, name)[:rows].copy_(part[name].to(dev).reshape(rows, O))          # (uint8 widens here)
+        for name in ("reward", "action", "flags", "link", "back"):
+            getattr(self, name)[:rows].copy_(part[name].to(dev))
+        self.per_state.copy_(part["per_state"].to(dev))
+        if self.use_per:
+            tc = self.tree_capacity
+            self.tree[tc:tc + n].copy_(part["leaves"].to(dev))
+            with torch.cuda.device(dev):
+                N.check(N.lib().prism_per_rebuild(ctypes.byref(self._desc), N.current_stream_handle()),
+                        "prism_per_rebuild")
+        self._size = n
+        self.buffer._writer._cursor = int(part["cursor"])
+        self._serial = int(part["serial"])
+        self._slot_id[:] = -1
+        self._slot_id[:rows] = part["slot_id"].numpy()
+        self._pending = {int(k): (int(s), int(i)) for k, s, i in part["pending"]}
+        self._n_staged = 0
+        tab = part["stream_tab"]
+        self._stream_tab = None if tab is None else tab.to(dev, torch.int64).contiguous()
+        self.seed = int(part["seed"])
+        # one counter space for sample() and the fused step: a new agent's device word starts at 0, the sum is what counts
+        self._draws, self._fused_draws = int(part["draws"]), 0
+        smp = self.buffer._sampler
+        smp._alpha, smp._beta, smp._eps = float(part["alpha"]), float(part["beta"]), float(part["eps"])
+        if not keep_streams:
+            self._pending.clear()
+            self._reset_streams()
+
+    def save_state(self, path):
+        """The live ring as an exact-resume snapshot (part ``replay``): every row, link and tree leaf, the host mirrors, the
+        open chains (``_pending``, the stream table) and the draw count -- what ``save()`` (the reference's format) cannot
+        hold.  Observations travel as uint8 when every value is an integer in [0, 255] (bit-exact either way)."""
+        from prism_amd.util import snapshot
+        part = self._state_part()
+        return snapshot.write_snapshot(path, {"replay": part}, {"compat": {"replay": self._compat_record()}})
+
+    def _check_snapshot(self, manifest):
+        from prism_amd.util import snapshot
+        cur = self._compat_record()
+        if cur["obs_shape"] is None:
+            del cur["obs_shape"]
+        snapshot.check_compat((manifest.get("compat") or {}).get("replay"), cur, "HipReplayBuffer.load_state")
+
+    def load_state(self, path, keep_streams=True):
+        """Restore a ``save_state`` snapshot into a freshly constructed buffer of the same configuration: what follows is
+        bit-identical to the run that wrote it.  ``keep_streams=False`` closes every open chain (a collector that restarts
+        its environments): the first row of every stream is then stored unlinked.  A snapshot of another capacity,
+        observation shape, ``n_step``, gammas, ``use_per`` or ``mass_rng`` is refused before anything is touched."""
+        from prism_amd.util import snapshot
+        self._check_snapshot(snapshot.read_manifest(path))
+        parts, _ = snapshot.read_snapshot(path, ["replay"])
+        self._restore_part(parts["replay"], keep_streams)

@@ -5,7 +5,9 @@ update -> priority writeback -> target sync) with everything resident in HBM.
 Quirks kept on purpose: beta is forced to 0.5 every step (learner.py:104-107); the target network
 is synced on a *timestep* period (learner.py:122-124).
 """
+import os
 import time
+import warnings
 
 import numpy as np
 
@@ -29,6 +31,7 @@ class Learner:
         self.time_phases = True
         self.fused = True
         self.hip_graph = True
+        self._resumed = False
 
     def configure(self, config, collector=None, obs_shape=None, n_actions=None, process_group=None):
         (self.agent, self.timestep_collector, self.experience_buffer, self.logger,
@@ -53,6 +56,8 @@ class Learner:
         self.fused = bool(getattr(config, "fused_step", True)) and \
             getattr(config, "per_mass_rng", "philox") == "philox" and getattr(config, "tau_rng", "philox") == "philox"
         self.hip_graph = bool(getattr(config, "hip_graph", True))
+        self._resumed = False
+        self.checkpointer.attach(self, config)              # config.backup_checkpoints: the hourly exact-resume snapshot
 
     # ------------------------------------------------------------------ the hot path
     def step(self, timesteps_this_iteration=0, eager=False):
@@ -100,11 +105,13 @@ class Learner:
     # ------------------------------------------------------------------ the outer loop
     def _learn(self):
         col = self.timestep_collector
-        self.cumulative_timesteps = col.collect_timesteps(self.initial_random_timesteps, self.agent,
-                                                          self.experience_buffer, random=True)
-        self.timesteps_since_report = self.cumulative_timesteps
-        self.logger.set_holdout_data(self.experience_buffer.sample(return_info=False).clone())
-        self.checkpointer.checkpoint(self.cumulative_timesteps)
+        if not self._resumed:          # (after load_state the prologue has happened: its results came with the snapshot)
+            self.cumulative_timesteps = col.collect_timesteps(self.initial_random_timesteps, self.agent,
+                                                              self.experience_buffer, random=True)
+            self.timesteps_since_report = self.cumulative_timesteps
+            self.logger.set_holdout_data(self.experience_buffer.sample(return_info=False).clone())
+            self.checkpointer.checkpoint(self.cumulative_timesteps)
+        self._resumed = False
         while self.cumulative_timesteps < self.timestep_limit:
             loop_start = time.perf_counter()
             n = col.collect_timesteps(self.timesteps_per_iteration, self.agent, self.experience_buffer)
@@ -158,10 +165,99 @@ class Learner:
             return
         if self.timestep_collector is None:
             raise RuntimeError("learn() needs a collector; use step() when feeding the buffer directly")
+        finished = False
         try:
             self._learn()
+            finished = True
         finally:
-            self.checkpointer.save_backup_checkpoint()
-            self.experience_buffer.empty()
-            self.timestep_collector.close()
-            self.logger.close()
+            try:
+                self.checkpointer.save_backup_checkpoint()
+            except Exception as e:          # noqa: BLE001 -- a snapshot that fails must not mask what ended the loop
+                if finished:
+                    raise
+                warnings.warn(f"prism_amd: the backup checkpoint on the way out failed ({e!r})")
+            finally:
+                self.experience_buffer.empty()
+                self.timestep_collector.close()
+                self.logger.close()
+
+    # ------------------------------------------------------------------ exact resume (prism_amd/util/snapshot.py)
+    def _snapshot_dir(self, path):
+        """Rank-local: with more than one rank every rank writes and reads ``path/rank<r>``; no collective call."""
+        if getattr(self.agent, "world", 1) > 1:
+            import torch.distributed as dist
+            return os.path.join(str(path), f"rank{dist.get_rank(self.agent.pg)}")
+        return str(path)
+
+    def _state_part(self):
+        from prism_amd.util import snapshot
+
+        def plain(b):
+            return None if b is None else {k: plain(v) if isinstance(v, dict) else v.detach().cpu() for k, v in b.items()}
+
+        opt = lambda x: None if x is None else float(x)
+        hold = getattr(self.logger, "holdout_data", None)
+        col = self.timestep_collector
+        return dict(
+            cumulative_timesteps=int(self.cumulative_timesteps), cumulative_model_updates=int(self.cumulative_model_updates),
+            timesteps_since_report=int(self.timesteps_since_report),
+            timesteps_since_target_model_update=int(self.timesteps_since_target_model_update),
+            collected_steps_per_second_ema=opt(self.collected_steps_per_second_ema),
+            overall_steps_per_second_ema=opt(self.overall_steps_per_second_ema),
+            per_beta=None if self.per_beta is None else self.per_beta.get_state(),
+            last_agent_checkpoint_timesteps=int(self.checkpointer.last_agent_checkpoint_timesteps),
+            holdout=plain(hold), holdout_batch_size=None if hold is None else getattr(hold, "batch_size", None),
+            numpy_rng=snapshot.numpy_rng_state(), python_rng=snapshot.python_rng_state(),
+            torch_rng=snapshot.torch_rng_state(), device_rng=snapshot.device_rng_state(self.agent.device),
+            collector=col.state_dict() if hasattr(col, "state_dict") else None)
+
+    def save_state(self, path):
+        """One exact-resume snapshot of the whole run: the replay ring (part ``replay``), the agent (``agent/`` in the
+        reference's layout + part ``agent_resume``) and the loop (part ``learner``: counters, target-sync timer, PER anneal,
+        holdout batch, checkpoint mark, the global NumPy / Python / torch generators, the collector's ``state_dict()`` where
+        it has one).  Wall-clock timers are not part of it."""
+        from prism_amd.util import snapshot
+        agent, buf = self.agent, self.experience_buffer
+        parts = {"replay": buf._state_part(), "agent_resume": agent._state_part(), "learner": self._state_part()}
+        manifest = {"compat": {"replay": buf._compat_record(), "agent": agent._compat_record()}}
+        return snapshot.write_snapshot(self._snapshot_dir(path), parts, manifest, extra=agent.save)
+
+    def load_state(self, path):
+        """After ``configure()`` on fresh objects of the same configuration: put buffer, agent and loop back where
+        ``save_state`` found them.  A following ``learn()`` skips its prologue (random collection, holdout sample, first
+        checkpoint) and goes on with the loop; what it computes is bit-identical to the uninterrupted run."""
+        from prism_amd.experience.hip_replay import Batch
+        from prism_amd.util import snapshot
+        agent, buf = self.agent, self.experience_buffer
+        d = self._snapshot_dir(path)
+        d = snapshot.latest(d) or d
+        manifest = snapshot.read_manifest(d)
+        agent._check_snapshot(manifest)          # every refusal comes before anything is touched
+        buf._check_snapshot(manifest)
+        parts, _ = snapshot.read_snapshot(d, ["replay", "agent_resume", "learner"])
+        st = parts["learner"]
+        buf._restore_part(parts["replay"])
+        agent._restore_part(d, parts["agent_resume"])
+        for name in ("cumulative_timesteps", "cumulative_model_updates", "timesteps_since_report",
+                     "timesteps_since_target_model_update", "collected_steps_per_second_ema",
+                     "overall_steps_per_second_ema"):
+            setattr(self, name, st[name])
+        if self.per_beta is not None and st["per_beta"] is not None:
+            self.per_beta.set_state(st["per_beta"])
+        self.checkpointer.last_agent_checkpoint_timesteps = st["last_agent_checkpoint_timesteps"]
+        if st["holdout"] is not None:
+            B, dev = st["holdout_batch_size"], agent.device
+
+            def batch(b):
+                return Batch({k: batch(v) if isinstance(v, dict) else v.to(dev) for k, v in b.items()}, B, dev)
+            self.logger.set_holdout_data(batch(st["holdout"]))
+        col = self.timestep_collector
+        if st["collector"] is not None and hasattr(col, "load_state_dict"):
+            col.load_state_dict(st["collector"])
+        # last: nothing above may draw from them
+        snapshot.set_numpy_rng_state(st["numpy_rng"])
+        snapshot.set_python_rng_state(st["python_rng"])
+        snapshot.set_torch_rng_state(st["torch_rng"])
+        snapshot.set_device_rng_state(st["device_rng"], agent.device)
+        self.reset_loggables()
+        self._resumed = True

@@ -4,6 +4,9 @@
     python tools/host_rate.py --mode ingest        one env step's ingestion for N streams: extend() x N + flush() against
                                                    extend_batch(), host float32 and uint8 arrays, and the whole loop
                                                    collector -> Agent.forward -> ingest -> Learner.step() both ways
+    python tools/host_rate.py --mode snapshot      exact-resume snapshots at the c3 shapes (capacity 100 000, (10, 10, 4), binary
+                                                   observations): Learner.save_state / load_state against the reference-format
+                                                   HipReplayBuffer.save / load, median seconds of --rounds runs and bytes on disk
     --root DIR    import prism_amd from another checkout (a build of the parent commit: only the per-row path exists there)
     --out FILE    also write the ingest table there
 """
@@ -17,7 +20,7 @@ import time
 import weakref
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--mode", choices=("step", "ingest"), default="step")
+ap.add_argument("--mode", choices=("step", "ingest", "snapshot"), default="step")
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument("--out", default=None)
 ap.add_argument("--steps", type=int, default=300)
@@ -182,7 +185,61 @@ def ingest_mode():
             f.write("\n".join(lines) + "\n")
 
 
+def dir_bytes(path):
+    return sum(os.path.getsize(os.path.join(b, f)) for b, _d, fs in os.walk(path) for f in fs)
+
+
+def snapshot_mode():
+    import shutil
+    import tempfile
+    ln = make_learner(2)                                  # c3: IQN + PER, capacity 100 000
+    buf = ln.experience_buffer
+    fill_replay(buf, buf.capacity, seed=0)
+    for _ in range(20):
+        ln.step()
+    torch.cuda.synchronize()
+    root = tempfile.mkdtemp(prefix="prism_snapshot_")
+    res = {k: [] for k in ("save_state", "load_state", "save", "load")}
+    size = {}
+    try:
+        for rnd in range(args.rounds):
+            snap, ref = os.path.join(root, "snap"), os.path.join(root, f"ref{rnd}")
+            t0 = time.perf_counter()
+            ln.save_state(snap)
+            res["save_state"].append(time.perf_counter() - t0)
+            size["save_state"] = dir_bytes(snap)
+            fresh = make_learner(2)
+            t0 = time.perf_counter()
+            fresh.load_state(snap)
+            torch.cuda.synchronize()
+            res["load_state"].append(time.perf_counter() - t0)
+            del fresh
+            t0 = time.perf_counter()
+            buf.save(ref)
+            res["save"].append(time.perf_counter() - t0)
+            size["save"] = dir_bytes(ref)
+            other = make_learner(2).experience_buffer
+            t0 = time.perf_counter()
+            other.load(ref)
+            torch.cuda.synchronize()
+            res["load"].append(time.perf_counter() - t0)
+            del other
+            shutil.rmtree(ref)
+            print(f"round {rnd}: " + "  ".join(f"{k} {v[-1]:.3f} s" for k, v in res.items()), flush=True)
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+    lines = [f"# snapshots at the c3 shapes: ring of {buf.capacity} x (10, 10, 4) binary observations, PER; median of {args.rounds} runs",
+             f"Learner.save_state            {statistics.median(res['save_state']):8.3f} s   {size['save_state']:>12d} bytes",
+             f"Learner.load_state            {statistics.median(res['load_state']):8.3f} s",
+             f"HipReplayBuffer.save (ref.)   {statistics.median(res['save']):8.3f} s   {size['save']:>12d} bytes",
+             f"HipReplayBuffer.load (ref.)   {statistics.median(res['load']):8.3f} s"]
+    print("\n".join(lines), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
     if not torch.cuda.is_available():
         sys.exit("host_rate.py measures on the GPU: no device found")
-    step_mode() if args.mode == "step" else ingest_mode()
+    {"step": step_mode, "ingest": ingest_mode, "snapshot": snapshot_mode}[args.mode]()
