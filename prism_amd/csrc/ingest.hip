@@ -3,28 +3,15 @@
 
 using namespace prism;
 
-static int check_ingest_ring(const prism_replay_desc *rp) {
-    PRISM_CHECK_ARG(rp != nullptr, "null descriptor");
-    PRISM_CHECK_ARG(rp->capacity > 0 && rp->capacity < (1ll << 31), "capacity out of range");
-    int64_t cap = 1;
-    while (cap <= rp->capacity) cap <<= 1;
-    PRISM_CHECK_ARG(rp->tree_capacity == cap, "tree_capacity must be the smallest power of two > capacity");
-    PRISM_CHECK_ARG(!rp->tree || cap <= (1ll << TREE_MAX_LEVELS), "prioritized capacity above 2^24 - 1 rows");
-    PRISM_CHECK_ARG(rp->obs_elems > 0, "obs_elems");
-    PRISM_CHECK_ARG(rp->obs && rp->succ_obs && rp->reward && rp->action && rp->flags && rp->link && rp->back,
-                    "null ring array");
-    PRISM_CHECK_ARG(rp->per_state && rp->status, "null per_state/status");
-    PRISM_CHECK_ARG((reinterpret_cast<uintptr_t>(rp->tree) & 15) == 0, "tree must be 16-byte aligned");
-    return PRISM_OK;
-}
-
 extern "C" int prism_replay_ingest(const prism_replay_desc *rp, int32_t n, int64_t first_slot, int64_t serial0,
                                    const void *obs, const void *next_obs, int32_t obs_kind, const float *reward,
                                    const int32_t *action, const uint8_t *done, const uint8_t *truncated,
                                    const int32_t *stream_ids, int64_t *stream_tab, int32_t n_streams, float alpha,
                                    float eps, prism_stream_t stream) {
-    int rc = check_ingest_ring(rp);
+    int rc = check_ring(rp, false);
     if (rc) return rc;
+    PRISM_CHECK_ARG(!rp->tree || rp->tree_capacity <= (1ll << TREE_MAX_LEVELS),
+                    "prioritized capacity above 2^24 - 1 rows");
     PRISM_CHECK_ARG(n >= 1 && n <= rp->capacity, "n must be in [1, capacity]");
     PRISM_CHECK_ARG(n_streams >= 1 && n_streams <= INGEST_MAX_STREAMS, "n_streams must be in [1, 65536]");
     PRISM_CHECK_ARG(obs_kind == PRISM_OBS_F32 || obs_kind == PRISM_OBS_U8,

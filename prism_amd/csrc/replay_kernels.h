@@ -1018,4 +1018,22 @@ static __global__ __launch_bounds__(128) void replay_gather_kernel(prism_replay_
     }
 }
 
+// host: what every entry point that takes a ring descriptor checks first (need_tree: the call reads or writes the trees)
+static inline int check_ring(const prism_replay_desc *rp, bool need_tree) {
+    PRISM_CHECK_ARG(rp != nullptr, "null descriptor");
+    PRISM_CHECK_ARG(rp->capacity > 0 && rp->capacity < (1ll << 31), "capacity out of range");
+    int64_t cap = 1;
+    while (cap <= rp->capacity) cap <<= 1;
+    PRISM_CHECK_ARG(rp->tree_capacity == cap, "tree_capacity must be the smallest power of two > capacity");
+    PRISM_CHECK_ARG(!need_tree || cap <= (1ll << TREE_MAX_LEVELS), "prioritized capacity above 2^24 - 1 rows");
+    PRISM_CHECK_ARG(rp->obs_elems > 0, "obs_elems");
+    PRISM_CHECK_ARG(rp->n_step >= 1 && rp->n_step <= PRISM_MAX_NSTEP, "n_step out of range");
+    PRISM_CHECK_ARG(rp->obs && rp->succ_obs && rp->reward && rp->action && rp->flags && rp->link && rp->back,
+                    "null ring array");
+    PRISM_CHECK_ARG(rp->per_state && rp->status, "null per_state/status");
+    if (need_tree) PRISM_CHECK_ARG(rp->tree, "prioritized call on a ring without trees");
+    PRISM_CHECK_ARG((reinterpret_cast<uintptr_t>(rp->tree) & 15) == 0, "tree must be 16-byte aligned");
+    return PRISM_OK;
+}
+
 }  // namespace prism

@@ -62,6 +62,89 @@ class _RingShim:
         return len(self._owner)
 
 
+class _Staging:
+    """Two sets of pinned host blocks with their device twins, in rotation: the host fills one while the copies and the
+    kernel that read the other are still in flight.  An event recorded behind the launch that reads a set guards it, and
+    is waited for only when that set comes round again -- a whole submission later."""
+
+    def __init__(self, make_set):
+        self.sets, self._ev, self._cur = (make_set(), make_set()), [None, None], 0
+
+    def acquire(self):
+        """The set to fill next; waits only if the launch that last read it has not finished."""
+        ev = self._ev[self._cur]
+        if ev is not None:
+            ev.synchronize()
+            self._ev[self._cur] = None
+        return self.sets[self._cur]
+
+    def submit(self):
+        """Behind the launch that reads the current set (same device, same stream): guard it and turn to the other."""
+        self._ev[self._cur] = ev = torch.cuda.Event()
+        ev.record()
+        self._cur ^= 1
+
+    def drain(self):
+        """Before the sets are dropped: nothing in flight reads them any more."""
+        for ev in self._ev:
+            if ev is not None:
+                ev.synchronize()
+
+
+_SMALL_INT = {True: (torch.bool, torch.uint8), False: (np.bool_, np.uint8)}       # observation dtypes stored as uint8
+
+
+def _is_dev(x):
+    return torch.is_tensor(x) and x.is_cuda
+
+
+def _host(x):
+    return x.numpy() if torch.is_tensor(x) else np.asarray(x)
+
+
+def _obs_kind(obs, next_obs):
+    """OBS_U8 / OBS_F32 of one extend_batch call: both observation arrays small-int (bool / uint8) or both float."""
+    small = [x.dtype in _SMALL_INT[torch.is_tensor(x)] for x in (obs, next_obs)]
+    if small[0] != small[1]:
+        raise ValueError(f"extend_batch: obs ({obs.dtype}) and next_obs ({next_obs.dtype}) must both be bool / uint8 "
+                         "or both be floating point")
+    return N.OBS_U8 if small[0] else N.OBS_F32
+
+
+def _check_stream_ids(stream_ids, n, table_size):
+    """The stream ids of one extend_batch call, checked as far as the host can without touching a device: (the ids as a
+    host array, or None for device-side / default ids; the number of table entries the call needs)."""
+    if stream_ids is None:
+        return None, n
+    if _is_dev(stream_ids):
+        if stream_ids.numel() != n:
+            raise ValueError("extend_batch: stream_ids must hold one id per row")
+        return None, max(n, table_size)
+    ids = _host(stream_ids).reshape(-1)
+    if ids.shape[0] != n:
+        raise ValueError("extend_batch: stream_ids must hold one id per row")
+    if int(ids.min()) < 0 or int(ids.max()) >= N.INGEST_MAX_STREAMS:
+        raise ValueError(f"extend_batch: stream_ids must lie in [0, {N.INGEST_MAX_STREAMS})")
+    seen = np.zeros(int(ids.max()) + 1, np.bool_)
+    seen[ids] = True
+    if int(seen.sum()) != n:
+        raise ValueError("extend_batch: stream_ids must be distinct within one call")
+    return ids, seen.shape[0]
+
+
+def _device_array(x, shape, dtype, stage):
+    """`x` as a contiguous device array of `dtype`, and whether it went through staging.  A device tensor is used in place
+    (bool is viewed as uint8, any other dtype bound for uint8 becomes x != 0, the rest is converted); anything else is
+    written into `stage` = (NumPy view of a pinned block, the same bytes of its device twin), which the caller copies."""
+    if not _is_dev(x):
+        np.copyto(stage[0], _host(x).reshape(shape), casting="unsafe")
+        return stage[1], True
+    x = x.reshape(shape)
+    if dtype == torch.uint8 and x.dtype != torch.uint8:
+        x = x.view(torch.uint8) if x.dtype == torch.bool else (x != 0).view(torch.uint8)
+    return (x if x.dtype == dtype else x.to(dtype)).contiguous(), False
+
+
 class HipReplayBuffer:
     STAGE_ROWS = 1024
 
@@ -95,14 +178,19 @@ class HipReplayBuffer:
         self._n_staged = 0
         self._index = None
         # vectorised producer seam (extend_batch): rows ever written since init / empty / bulk load (serial % capacity ==
-        # writer cursor), the device table "write serial of each stream's open row", and its pinned staging sets
+        # writer cursor), the device table "write serial of each stream's open row", and its staging rotation
         self._serial = 0
         self._stream_tab = None
         self._ing = None
-        self._ing_cur = 0
 
     # ------------------------------------------------------------------ allocation
     def _allocate(self, obs_shape):
+        """Step a of every bulk install, and of the first extend: the ring for this observation shape, empty -- allocated
+        now, or (a load into a buffer that has been used) brought back to the state of a fresh one."""
+        if self._desc is not None:
+            for t in (self.obs, self.succ_obs, self.reward, self.action):      # (empty() leaves the rows' payload behind)
+                t.zero_()
+            return self.empty()
         dev, cap = self.device, self.capacity
         self._obs_shape = tuple(int(s) for s in obs_shape)
         O = int(np.prod(self._obs_shape))
@@ -130,32 +218,35 @@ class HipReplayBuffer:
             setattr(d, name, t.data_ptr() if t is not None else None)
         for i, g in enumerate(self.gammas):
             d.gammas[i] = g
-        self._desc = d
-        with torch.cuda.device(dev):
-            N.check(N.lib().prism_replay_init(ctypes.byref(d), N.current_stream_handle()), "prism_replay_init")
-        # staging (pinned host -> device) for extend()
-        S = self.STAGE_ROWS
-        pin = dict(pin_memory=True)
-        # two staging sets: extend() fills one while the H2D copies + insert kernels of the other are in
-        # flight; a set is only waited for (its event) when it comes round again
+        self._desc, self._desc_ref = d, ctypes.byref(d)
+        self._on_device = torch.cuda.device(dev)         # entered around every native call (_call; never nested)
+        self._call("prism_replay_init")
+        # staging (pinned host -> device) for extend(): a _Staging rotation of two sets.
         # The five per-row scalars live side by side in ONE pinned block (and one device block): a flush is three
         # host-to-device copies -- that block whole (17 bytes a row), the used observation rows, the used successor rows --
-        # instead of seven.  extend() writes through NumPy views of the pinned memory (a torch scalar store costs 2 us).
-        def _stage(device=None):
-            kw = dict(device=device) if device is not None else pin
+        # instead of seven.  extend() writes through NumPy views of the pinned memory (a torch scalar store costs 2 us),
+        # bound to plain attributes (_h, _d, _hn) at rotation time: the per-row body pays for no call and no lookup chain.
+        S = self.STAGE_ROWS
+
+        def _blocks(**kw):
             small = torch.zeros(17 * S, dtype=torch.uint8, **kw)      # slots | reward | action | prev (4 bytes each) | flags (1)
             w = lambda k: small[4 * S * k:4 * S * (k + 1)]
-            st = dict(small=small, slots=w(0).view(torch.int32), reward=w(1).view(torch.float32),
-                      action=w(2).view(torch.int32), prev=w(3).view(torch.int32), flags=small[16 * S:],
-                      obs=torch.zeros(S, O, **kw), succ=torch.zeros(S, O, **kw))
-            return st
-        self._stages = [_stage(), _stage()]
-        self._stage_np = [{k: v.numpy() for k, v in st.items()} for st in self._stages]
-        self._stage_dev = [_stage(dev), _stage(dev)]
-        self._stage_ev = [None, None]
-        self._cur_stage = 0
-        self._h, self._d, self._hn = self._stages[0], self._stage_dev[0], self._stage_np[0]
+            return dict(small=small, slots=w(0).view(torch.int32), reward=w(1).view(torch.float32),
+                        action=w(2).view(torch.int32), prev=w(3).view(torch.int32), flags=small[16 * S:],
+                        obs=torch.zeros(S, O, **kw), succ=torch.zeros(S, O, **kw))
+
+        def _set():
+            h, d = _blocks(pin_memory=True), _blocks(device=dev)
+            # (the device twins never move: prism_replay_insert's seven array arguments are made once)
+            args = tuple(N.ptr(d[k]) for k in ("slots", "obs", "succ", "reward", "action", "flags", "prev"))
+            return dict(h=h, d=d, np={k: v.numpy() for k, v in h.items()}, args=args)
+        self._row_stage = _Staging(_set)
+        self._bind_row_stage()
         self._alloc_batch(self.buffer._batch_size)
+
+    def _bind_row_stage(self):
+        st = self._row_stage.acquire()
+        self._h, self._d, self._hn, self._insert_args = st["h"], st["d"], st["np"], st["args"]
 
     def _alloc_batch(self, B):
         dev, fs = self.device, self.frame_stack
@@ -172,6 +263,16 @@ class HipReplayBuffer:
         self._weight = torch.ones(B, dtype=torch.float32, device=dev)
         self._mass = torch.zeros(B, dtype=torch.float32, device=dev)
         self._q2 = torch.zeros(2, dtype=torch.float32, device=dev)
+
+    def _call(self, name, *args, desc=True, submit=None):
+        """One native call on this buffer's device and its current stream: the ring descriptor in front (desc=False:
+        the entry point takes none), the stream behind, the return code checked.  `submit`: the staging rotation whose
+        current set the launch reads, guarded and turned right behind it."""
+        with self._on_device:
+            head = (self._desc_ref,) if desc else ()
+            N.check(getattr(N.lib(), name)(*head, *args, N.current_stream_handle()), name)
+            if submit is not None:
+                submit.submit()
 
     # ------------------------------------------------------------------ reference API
     def __len__(self):
@@ -222,25 +323,12 @@ class HipReplayBuffer:
         n = self._n_staged
         if n == 0:
             return
-        self._d["small"].copy_(self._h["small"], non_blocking=True)
-        self._d["obs"][:n].copy_(self._h["obs"][:n], non_blocking=True)
-        self._d["succ"][:n].copy_(self._h["succ"][:n], non_blocking=True)
-        d, smp = self._d, self.buffer._sampler
-        with torch.cuda.device(self.device):
-            N.check(N.lib().prism_replay_insert(
-                ctypes.byref(self._desc), n, N.ptr(d["slots"]), N.ptr(d["obs"]), N.ptr(d["succ"]),
-                N.ptr(d["reward"]), N.ptr(d["action"]), N.ptr(d["flags"]), N.ptr(d["prev"]),
-                smp._alpha, smp._eps, N.current_stream_handle()), "prism_replay_insert")
-            ev = torch.cuda.Event()
-            ev.record()
-        # the other staging set takes the next rows; it was submitted a whole batch ago
-        self._stage_ev[self._cur_stage] = ev
-        self._cur_stage ^= 1
-        self._h, self._d = self._stages[self._cur_stage], self._stage_dev[self._cur_stage]
-        self._hn = self._stage_np[self._cur_stage]
-        if self._stage_ev[self._cur_stage] is not None:
-            self._stage_ev[self._cur_stage].synchronize()
-            self._stage_ev[self._cur_stage] = None
+        h, d, smp = self._h, self._d, self.buffer._sampler
+        d["small"].copy_(h["small"], non_blocking=True)
+        d["obs"][:n].copy_(h["obs"][:n], non_blocking=True)
+        d["succ"][:n].copy_(h["succ"][:n], non_blocking=True)
+        self._call("prism_replay_insert", n, *self._insert_args, smp._alpha, smp._eps, submit=self._row_stage)
+        self._bind_row_stage()         # the other set takes the next rows; it was submitted a whole batch ago
         self._n_staged = 0
 
     # ------------------------------------------------------------------ vectorised producer seam
@@ -269,56 +357,36 @@ class HipReplayBuffer:
         with torch.cuda.device(self.device):
             self._stream_table(int(n_streams))
 
-    def _reset_streams(self):
-        """After init / empty / bulk load: no stream has an open row, and serial % capacity == writer cursor."""
-        self._serial = self.buffer._writer._cursor
-        if self._stream_tab is not None:
-            self._stream_tab.fill_(-1)
-
-    def _ingest_stage(self, n):
-        """The pinned staging set (and its device twin) the next extend_batch fills: two sets in rotation as in flush(); a
-        set is waited for only when it comes round again.  Views are cached per row count."""
+    def _ingest_views(self, n, kind):
+        """The staging set the next extend_batch fills (a _Staging rotation, regrown to a power of two of rows when a call
+        needs more) as views for `n` rows of observation kind `kind`, cached per (n, kind): key -> (NumPy view of the
+        pinned block, the same bytes of the device twin), and ``copies``: block -> (device twin, pinned block) in use."""
         O = self.obs_elems
-        if self._ing is None or self._ing[0]["rows"] < n:
+        if self._ing is None or self._ing.sets[0]["rows"] < n:
             if self._ing is not None:
-                for st in self._ing:
-                    if st["ev"] is not None:
-                        st["ev"].synchronize()
+                self._ing.drain()
             rows = 64
             while rows < n:
                 rows <<= 1
-
-            def _set():
-                # observations as raw bytes (viewed fp32 or uint8); the five per-row scalars side by side in ONE block:
-                # reward | action | stream id (4 bytes each) | done | truncated (1 each), packed for the row count in use
-                mk = lambda nbytes, **kw: torch.zeros(nbytes, dtype=torch.uint8, **kw)
-                return dict(rows=rows, ev=None, views={},
-                            h_obs=mk(4 * rows * O, pin_memory=True), h_next=mk(4 * rows * O, pin_memory=True),
-                            h_small=mk(14 * rows, pin_memory=True), d_obs=mk(4 * rows * O, device=self.device),
-                            d_next=mk(4 * rows * O, device=self.device), d_small=mk(14 * rows, device=self.device))
-            self._ing = [_set(), _set()]
-            self._ing_cur = 0
-        st = self._ing[self._ing_cur]
-        if st["ev"] is not None:
-            st["ev"].synchronize()
-            st["ev"] = None
-        return st
-
-    @staticmethod
-    def _ingest_views(st, n, O, kind):
+            # observations as raw bytes (viewed fp32 or uint8); the five per-row scalars side by side in ONE block:
+            # reward | action | stream id (4 bytes each) | done | truncated (1 each), packed for the row count in use
+            mk = lambda nbytes: (torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True),
+                                 torch.zeros(nbytes, dtype=torch.uint8, device=self.device))
+            with torch.cuda.device(self.device):
+                self._ing = _Staging(lambda: dict(rows=rows, views={}, obs=mk(4 * rows * O), next=mk(4 * rows * O),
+                                                  small=mk(14 * rows)))
+        st = self._ing.acquire()
         v = st["views"].get((n, kind))
         if v is None:
-            ob = n * O * (4 if kind == N.OBS_F32 else 1)
-            odt = torch.float32 if kind == N.OBS_F32 else torch.uint8
-            hs, ds = st["h_small"], st["d_small"]
-            sm = lambda t: dict(reward=t[0:4 * n].view(torch.float32), action=t[4 * n:8 * n].view(torch.int32),
-                                ids=t[8 * n:12 * n].view(torch.int32), done=t[12 * n:13 * n], trunc=t[13 * n:14 * n])
-            h, d = sm(hs), sm(ds)
-            v = dict(h_obs=st["h_obs"][:ob].view(odt).view(n, O), h_next=st["h_next"][:ob].view(odt).view(n, O),
-                     d_obs=st["d_obs"][:ob].view(odt).view(n, O), d_next=st["d_next"][:ob].view(odt).view(n, O),
-                     h_small=hs[:14 * n], d_small=ds[:14 * n], d=d)
-            v["np_obs"], v["np_next"] = v["h_obs"].numpy(), v["h_next"].numpy()
-            v["np"] = {k: t.numpy() for k, t in h.items()}
+            ob, odt = (4 * n * O, torch.float32) if kind == N.OBS_F32 else (n * O, torch.uint8)
+            small = lambda t: dict(reward=t[0:4 * n].view(torch.float32), action=t[4 * n:8 * n].view(torch.int32),
+                                   ids=t[8 * n:12 * n].view(torch.int32), done=t[12 * n:13 * n], trunc=t[13 * n:14 * n])
+            h, d = small(st["small"][0]), small(st["small"][1])
+            for k in ("obs", "next"):
+                h[k], d[k] = (t[:ob].view(odt).view(n, O) for t in st[k])
+            v = {k: (h[k].numpy(), d[k]) for k in h}
+            v["copies"] = dict(obs=(d["obs"], h["obs"]), next=(d["next"], h["next"]),
+                               small=(st["small"][1][:14 * n], st["small"][0][:14 * n]))
             if len(st["views"]) >= 8:                  # (a collector that varies its subset size: keep the cache small)
                 st["views"].clear()
             st["views"][(n, kind)] = v
@@ -342,84 +410,33 @@ class HipReplayBuffer:
         n = int(obs.shape[0])
         if not 1 <= n <= self.capacity:
             raise ValueError(f"extend_batch: n = {n} rows must be in [1, capacity = {self.capacity}]")
-        is_dev = lambda x: torch.is_tensor(x) and x.is_cuda
-        host = lambda x: x.numpy() if torch.is_tensor(x) else np.asarray(x)
-        small_int = (torch.bool, torch.uint8) if torch.is_tensor(obs) else (np.bool_, np.uint8)
-        kind = N.OBS_U8 if obs.dtype in small_int else N.OBS_F32
         if not torch.is_tensor(next_obs):
             next_obs = np.asarray(next_obs)
-        next_small = next_obs.dtype in ((torch.bool, torch.uint8) if torch.is_tensor(next_obs) else (np.bool_, np.uint8))
-        if next_small != (kind == N.OBS_U8):
-            raise ValueError(f"extend_batch: obs ({obs.dtype}) and next_obs ({next_obs.dtype}) must both be bool / uint8 "
-                             "or both be floating point")
-        ids_host = None
-        if stream_ids is not None and not is_dev(stream_ids):
-            ids_host = host(stream_ids).reshape(-1)
-            if ids_host.shape[0] != n:
-                raise ValueError("extend_batch: stream_ids must hold one id per row")
-            if int(ids_host.min()) < 0 or int(ids_host.max()) >= N.INGEST_MAX_STREAMS:
-                raise ValueError(f"extend_batch: stream_ids must lie in [0, {N.INGEST_MAX_STREAMS})")
-            seen = np.zeros(int(ids_host.max()) + 1, np.bool_)
-            seen[ids_host] = True
-            if int(seen.sum()) != n:
-                raise ValueError("extend_batch: stream_ids must be distinct within one call")
-            need = seen.shape[0]
-        else:
-            if stream_ids is not None and stream_ids.numel() != n:
-                raise ValueError("extend_batch: stream_ids must hold one id per row")
-            need = n if stream_ids is None else max(n, 0 if self._stream_tab is None else self._stream_tab.numel())
+        kind = _obs_kind(obs, next_obs)
+        ids_host, need = _check_stream_ids(stream_ids, n, 0 if self._stream_tab is None else self._stream_tab.numel())
         if self._desc is None:
             self._allocate(tuple(obs.shape[1:]))
         self.flush()                                   # rows staged by extend() come first
-        O, dev = self.obs_elems, self.device
-        odt = torch.float32 if kind == N.OBS_F32 else torch.uint8
-        with torch.cuda.device(dev):
-            tab = self._stream_table(need)
-            scalars = dict(reward=reward, action=action, done=done, trunc=truncated)
-            staged = not (is_dev(obs) and is_dev(next_obs) and ids_host is None and all(map(is_dev, scalars.values())))
-            if staged:
-                st = self._ingest_stage(n)
-                v = self._ingest_views(st, n, O, kind)
-
-            def dev_obs(x, key):
-                if is_dev(x):
-                    x = x.reshape(n, O)
-                    x = x.view(torch.uint8) if x.dtype == torch.bool else x
-                    return (x if x.dtype == odt else x.to(odt)).contiguous()
-                np.copyto(v["np_" + key], host(x).reshape(n, O), casting="unsafe")
-                v["d_" + key].copy_(v["h_" + key], non_blocking=True)
-                return v["d_" + key]
-            d_obs, d_next = dev_obs(obs, "obs"), dev_obs(next_obs, "next")
-            sdt = dict(reward=torch.float32, action=torch.int32, done=torch.uint8, trunc=torch.uint8)
-            args, any_host = {}, ids_host is not None
-            for k, x in scalars.items():
-                if is_dev(x):
-                    x = x.reshape(n)
-                    if sdt[k] == torch.uint8 and x.dtype != torch.uint8:
-                        x = x.view(torch.uint8) if x.dtype == torch.bool else (x != 0).view(torch.uint8)
-                    args[k] = (x if x.dtype == sdt[k] else x.to(sdt[k])).contiguous()
-                else:
-                    np.copyto(v["np"][k], host(x).reshape(n), casting="unsafe")
-                    args[k], any_host = v["d"][k], True
-            if ids_host is not None:
-                np.copyto(v["np"]["ids"], ids_host, casting="unsafe")
-                d_ids = v["d"]["ids"]
-            elif stream_ids is not None:
-                d_ids = stream_ids.reshape(-1).to(torch.int32).contiguous()
-            else:
-                d_ids = None
-            if any_host:
-                v["d_small"].copy_(v["h_small"], non_blocking=True)
-            w, smp = self.buffer._writer, self.buffer._sampler
-            first, serial = w._cursor, self._serial
-            N.check(N.lib().prism_replay_ingest(
-                ctypes.byref(self._desc), n, first, serial, N.ptr(d_obs), N.ptr(d_next), kind, N.ptr(args["reward"]),
-                N.ptr(args["action"]), N.ptr(args["done"]), N.ptr(args["trunc"]), N.ptr(d_ids), N.ptr(tab),
-                tab.numel(), smp._alpha, smp._eps, N.current_stream_handle()), "prism_replay_ingest")
-            if staged:
-                st["ev"] = torch.cuda.Event()
-                st["ev"].record()
-                self._ing_cur ^= 1
+        O, odt = self.obs_elems, torch.float32 if kind == N.OBS_F32 else torch.uint8
+        rows = [("obs", obs, (n, O), odt), ("next", next_obs, (n, O), odt), ("reward", reward, n, torch.float32),
+                ("action", action, n, torch.int32), ("done", done, n, torch.uint8), ("trunc", truncated, n, torch.uint8)]
+        if stream_ids is not None:
+            rows.append(("ids", stream_ids if ids_host is None else ids_host, n, torch.int32))
+        tab = self._stream_table(need)
+        staged = not all(_is_dev(r[1]) for r in rows)
+        v = self._ingest_views(n, kind) if staged else {}
+        dev, copies = {"ids": None}, {}
+        for k, x, shape, dtype in rows:
+            dev[k], was_staged = _device_array(x, shape, dtype, v.get(k))
+            if was_staged:                             # (at most three copies: obs, next, the scalar block whole)
+                copies[k if k in ("obs", "next") else "small"] = True
+        for k in copies:
+            v["copies"][k][0].copy_(v["copies"][k][1], non_blocking=True)
+        w, smp = self.buffer._writer, self.buffer._sampler
+        first, serial = w._cursor, self._serial
+        self._call("prism_replay_ingest", n, first, serial, N.ptr(dev["obs"]), N.ptr(dev["next"]), kind,
+                   N.ptr(dev["reward"]), N.ptr(dev["action"]), N.ptr(dev["done"]), N.ptr(dev["trunc"]), N.ptr(dev["ids"]),
+                   N.ptr(tab), tab.numel(), smp._alpha, smp._eps, submit=self._ing if staged else None)
         # host mirrors, by arithmetic; the slots get ids from a private (negative) range: no Timestep id matches them
         cap = self.capacity
         own = np.arange(-2 - serial, -2 - serial - n, -1, dtype=np.int64)
@@ -437,31 +454,24 @@ class HipReplayBuffer:
             raise RuntimeError("Cannot sample from an empty storage.")
         self.flush()
         B = self.buffer._batch_size if batch_size is None else int(batch_size)
-        if self._index is None or self._index.shape[0] != B:
-            self._alloc_batch(B)
-        L, dsc, st = N.lib(), ctypes.byref(self._desc), N.current_stream_handle
-        with torch.cuda.device(self.device):
-            if self.use_per:
-                mass = None
-                if self.mass_rng == "numpy":
-                    N.check(L.prism_per_query(dsc, self._size, N.ptr(self._q2), st()), "prism_per_query")
-                    p_sum, p_min = self._q2.tolist()
-                    if p_sum <= 0 or p_min <= 0:
-                        raise RuntimeError("non-positive p_sum / p_min")
-                    m = np.random.uniform(0.0, p_sum, size=B).astype(np.float32)
-                    self._mass.copy_(torch.from_numpy(m))
-                    mass = self._mass
-                N.check(L.prism_per_sample(dsc, self._size, B, N.ptr(mass), self.seed, self._draws + self._fused_draws,
-                                           self.buffer._sampler._beta, N.ptr(self._index), N.ptr(self._weight),
-                                           st()), "prism_per_sample")
-            else:
-                N.check(L.prism_uniform_sample(self._size, B, self.seed, self._draws + self._fused_draws,
-                                               N.ptr(self._index), st()),
-                        "prism_uniform_sample")
-            self._draws += B
-            N.check(L.prism_replay_gather(dsc, N.ptr(self._index), B, N.ptr(self._obs), N.ptr(self._next_obs),
-                                          N.ptr(self._reward), N.ptr(self._nonterminal), N.ptr(self._gamma),
-                                          N.ptr(self._action), st()), "prism_replay_gather")
+        offset = self._draws + self._fused_draws
+        self._batch_for(B)
+        if self.use_per:
+            mass = None
+            if self.mass_rng == "numpy":
+                self._call("prism_per_query", self._size, N.ptr(self._q2))
+                p_sum, p_min = self._q2.tolist()
+                if p_sum <= 0 or p_min <= 0:
+                    raise RuntimeError("non-positive p_sum / p_min")
+                m = np.random.uniform(0.0, p_sum, size=B).astype(np.float32)
+                self._mass.copy_(torch.from_numpy(m))
+                mass = self._mass
+            self._call("prism_per_sample", self._size, B, N.ptr(mass), self.seed, offset, self.buffer._sampler._beta,
+                       N.ptr(self._index), N.ptr(self._weight))
+        else:
+            self._call("prism_uniform_sample", self._size, B, self.seed, offset, N.ptr(self._index), desc=False)
+        self._draws += B
+        self._gather_into_batch(B)
         if self.strict:
             self.check_status()
         if return_info:
@@ -471,20 +481,25 @@ class HipReplayBuffer:
             return self._batch, info
         return self._batch
 
+    def _batch_for(self, B):
+        """The index array of the static batch, (re)allocated for B rows."""
+        if self._index is None or self._index.shape[0] != B:
+            self._alloc_batch(B)
+        return self._index
+
+    def _gather_into_batch(self, B):
+        """n-step walk + row gather of the slots in ``_index`` into the static batch."""
+        self._call("prism_replay_gather", N.ptr(self._index), B, N.ptr(self._obs), N.ptr(self._next_obs),
+                   N.ptr(self._reward), N.ptr(self._nonterminal), N.ptr(self._gamma), N.ptr(self._action))
+
     @torch.no_grad()
     def gather(self, indices):
         """The static batch for given slots: n-step return + collate (timestep_buffer.py:79-238) without sampling."""
         self.flush()
         idx = torch.as_tensor(indices).to(self.device, torch.int64).reshape(-1).contiguous()
         B = int(idx.numel())
-        if self._index is None or self._index.shape[0] != B:
-            self._alloc_batch(B)
-        self._index.copy_(idx)
-        with torch.cuda.device(self.device):
-            N.check(N.lib().prism_replay_gather(ctypes.byref(self._desc), N.ptr(self._index), B, N.ptr(self._obs),
-                                                N.ptr(self._next_obs), N.ptr(self._reward), N.ptr(self._nonterminal),
-                                                N.ptr(self._gamma), N.ptr(self._action), N.current_stream_handle()),
-                    "prism_replay_gather")
+        self._batch_for(B).copy_(idx)
+        self._gather_into_batch(B)
         return self._batch
 
     def check_status(self):
@@ -503,12 +518,8 @@ class HipReplayBuffer:
         pr = torch.as_tensor(priorities).detach().to(self.device, torch.float32).reshape(-1)
         if pr.numel() == 1 and idx.numel() > 1:
             pr = pr.expand(idx.numel())
-        pr = pr.contiguous()
         smp = self.buffer._sampler
-        with torch.cuda.device(self.device):
-            N.check(N.lib().prism_per_update(ctypes.byref(self._desc), N.ptr(idx), N.ptr(pr), idx.numel(),
-                                             smp._alpha, smp._eps, int(take_abs), N.current_stream_handle()),
-                    "prism_per_update")
+        self._call("prism_per_update", N.ptr(idx), N.ptr(pr.contiguous()), idx.numel(), smp._alpha, smp._eps, int(take_abs))
 
     def set_static_batch(self, batch):
         self._batch = batch
@@ -523,49 +534,59 @@ class HipReplayBuffer:
         return self._batch
 
     def empty(self):
-        self._size = 0
-        self._n_staged = 0
-        self.buffer._writer._cursor = 0
-        self._pending.clear()
-        self._slot_id[:] = -1
-        self._reset_streams()
         if self._desc is not None:
-            with torch.cuda.device(self.device):
-                N.check(N.lib().prism_replay_init(ctypes.byref(self._desc), N.current_stream_handle()),
-                        "prism_replay_init")
+            self._call("prism_replay_init")
+        self._seal(0)
 
-    # ------------------------------------------------------------------ bulk fill (bench / restore)
-    def load_arrays(self, obs, succ_obs, reward, action, flags, link, priorities=None, n_sampleable=None):
-        """Fill the first n slots from device/host arrays and rebuild the trees from the given leaf
-        values (already (p+eps)**alpha).  Used for synthetic pre-fill and restore.  ``n_sampleable`` < n: only the
-        first rows are stored items (sampled, counted by len()); the rest only serve as link targets."""
-        n = int(obs.shape[0])
+    # ------------------------------------------------------------------ bulk installs (bench / restore)
+    def _seal(self, n, n_sampleable=None, cursor=None, leaves=None, back=None, slot_ids=None):
+        """Step c of every bulk install -- after a. ``_allocate`` (an empty ring) and b. the caller's writes of rows [0, n)
+        of ``obs`` .. ``link``: everything the ring's contents imply, set in ONE place.  The first ``n_sampleable`` rows are
+        stored items (sampled, counted by len()), the rest only serve as link targets; the writer goes on at ``cursor``
+        (default: behind the items).  ``leaves``: the items' tree leaves, [ns] or [ns, 2] as {sum, min} (default 1);
+        ``back``: the inverse of ``link`` if the caller holds it (else derived); ``slot_ids``: the rows' Timestep ids
+        (default 0 .. n - 1).  No stream has an open row, no Timestep a pending predecessor, nothing is staged."""
         ns = n if n_sampleable is None else int(n_sampleable)
-        if self._desc is None:
-            self._allocate(tuple(obs.shape[1:]))
+        self._size = ns
+        self.buffer._writer._cursor = ns % self.capacity if cursor is None else int(cursor)
+        self._serial = self.buffer._writer._cursor       # serial % capacity == writer cursor
+        if self._stream_tab is not None:
+            self._stream_tab.fill_(-1)
+        self._slot_id[:] = -1
+        self._slot_id[:n] = np.arange(n) if slot_ids is None else slot_ids
+        self._pending.clear()
+        self._n_staged = 0
+        if n == 0:                                       # (empty(): prism_replay_init has left nothing to finish)
+            return
+        if back is None:
+            lk = self.link[:n]
+            valid = lk >= 0
+            self.back[lk[valid].long()] = torch.arange(n, device=self.device, dtype=torch.int32)[valid]
+        else:
+            self.back[:n].copy_(back)
+        if self.use_per:
+            tc = self.tree_capacity
+            p = torch.ones(ns, device=self.device) if leaves is None else torch.as_tensor(leaves)[:ns]
+            self.tree[tc:tc + ns].copy_(p if p.dim() == 2 else p.unsqueeze(1))
+            self._call("prism_per_rebuild")
+
+    def load_arrays(self, obs, succ_obs, reward, action, flags, link, priorities=None, n_sampleable=None, cursor=None,
+                    slot_ids=None):
+        """Replace the buffer's contents by n rows from device/host arrays, with the trees rebuilt from the given leaf
+        values (already (p+eps)**alpha).  Used for synthetic pre-fill and restore.  ``n_sampleable`` < n: only the
+        first rows are stored items (sampled, counted by len()); the rest only serve as link targets.  ``cursor`` /
+        ``slot_ids``: where the writer goes on and the rows' Timestep ids, when a saved directory holds them (``_seal``).
+        Nothing of what the buffer held before survives: the result is that of loading into a fresh buffer."""
+        n = int(obs.shape[0])
+        self._allocate(tuple(obs.shape[1:]))
         O = self.obs_elems
         self.obs[:n].copy_(torch.as_tensor(obs).reshape(n, O))
         self.succ_obs[:n].copy_(torch.as_tensor(succ_obs).reshape(n, O))
         self.reward[:n].copy_(torch.as_tensor(reward))
         self.action[:n].copy_(torch.as_tensor(action))
         self.flags[:n].copy_(torch.as_tensor(flags))
-        lk = torch.as_tensor(link).to(self.device, torch.int32)
-        self.link[:n].copy_(lk)
-        self.back.fill_(-1)
-        valid = lk >= 0
-        self.back[lk[valid].long()] = torch.arange(n, device=self.device, dtype=torch.int32)[valid]
-        self._size = ns
-        self.buffer._writer._cursor = ns % self.capacity
-        self._reset_streams()
-        self._slot_id[:n] = np.arange(n)
-        if self.use_per:
-            tc = self.tree_capacity
-            p = torch.ones(ns, device=self.device) if priorities is None else torch.as_tensor(priorities)[:ns]
-            self.sum_tree[tc:tc + ns].copy_(p)
-            self.min_tree[tc:tc + ns].copy_(p)
-            with torch.cuda.device(self.device):
-                N.check(N.lib().prism_per_rebuild(ctypes.byref(self._desc), N.current_stream_handle()),
-                        "prism_per_rebuild")
+        self.link[:n].copy_(torch.as_tensor(link).to(self.device, torch.int32))
+        self._seal(n, n_sampleable, cursor, priorities, slot_ids=slot_ids)
 
     def save(self, path):
         """``TimestepBuffer.save`` (timestep_buffer.py:259-296): ``experience_buffer/timesteps.pkl`` in the reference's
@@ -611,12 +632,10 @@ class HipReplayBuffer:
             leaves = torch.full((n,), float(np.float32(np.float32(1.0 + smp._eps) ** np.float32(smp._alpha))))
         link = np.where(r["link"][:n_all] < n_all, r["link"][:n_all], -1)
         self.load_arrays(r["obs"][:n_all], r["succ_obs"][:n_all], r["reward"][:n_all], r["action"][:n_all], r["flags"][:n_all],
-                         link, leaves, n_sampleable=n)
-        self._slot_id[:n_all] = r["ids"][:n_all]
+                         link, leaves, n_sampleable=n, cursor=None if st is None else int(st["cursor"]),
+                         slot_ids=r["ids"][:n_all])
         if st is not None:
             self.per_state.copy_(st["per_state"])
-        self.buffer._writer._cursor = int(st["cursor"]) if st is not None else n % self.capacity
-        self._reset_streams()
 
     # ------------------------------------------------------------------ exact resume (prism_amd/util/snapshot.py)
     def _compat_record(self):
@@ -663,41 +682,29 @@ class HipReplayBuffer:
         return part
 
     def _restore_part(self, part, keep_streams=True):
-        rows, n = int(part["rows"]), int(part["size"])
-        dev = self.device
-        if self._desc is None:
-            self._allocate(tuple(int(s) for s in part["obs_shape"]))
-        else:
-            self.empty()
+        rows, dev = int(part["rows"]), self.device
+        self._allocate(tuple(int(s) for s in part["obs_shape"]))
         O = self.obs_elems
         for name in ("obs", "succ_obs"):
             getattr(self, name)[:rows].copy_(part[name].to(dev).reshape(rows, O))          # (uint8 widens here)
-        for name in ("reward", "action", "flags", "link", "back"):
+        for name in ("reward", "action", "flags", "link"):
             getattr(self, name)[:rows].copy_(part[name].to(dev))
+        self._seal(rows, part["size"], part["cursor"], part.get("leaves"), part["back"].to(dev), part["slot_id"].numpy())
+        # what only a snapshot has, layered on the sealed ring: the sampler's state and counters ...
         self.per_state.copy_(part["per_state"].to(dev))
-        if self.use_per:
-            tc = self.tree_capacity
-            self.tree[tc:tc + n].copy_(part["leaves"].to(dev))
-            with torch.cuda.device(dev):
-                N.check(N.lib().prism_per_rebuild(ctypes.byref(self._desc), N.current_stream_handle()),
-                        "prism_per_rebuild")
-        self._size = n
-        self.buffer._writer._cursor = int(part["cursor"])
-        self._serial = int(part["serial"])
-        self._slot_id[:] = -1
-        self._slot_id[:rows] = part["slot_id"].numpy()
-        self._pending = {int(k): (int(s), int(i)) for k, s, i in part["pending"]}
-        self._n_staged = 0
-        tab = part["stream_tab"]
-        self._stream_tab = None if tab is None else tab.to(dev, torch.int64).contiguous()
         self.seed = int(part["seed"])
         # one counter space for sample() and the fused step: a new agent's device word starts at 0, the sum is what counts
         self._draws, self._fused_draws = int(part["draws"]), 0
         smp = self.buffer._sampler
         smp._alpha, smp._beta, smp._eps = float(part["alpha"]), float(part["beta"]), float(part["eps"])
-        if not keep_streams:
-            self._pending.clear()
-            self._reset_streams()
+        # ... a stream table of the size the run had reached, and (keep_streams) the chains that were open in it
+        tab = part["stream_tab"]
+        self._stream_tab = None if tab is None else tab.to(dev, torch.int64).contiguous()
+        if keep_streams:
+            self._serial = int(part["serial"])
+            self._pending = {int(k): (int(s), int(i)) for k, s, i in part["pending"]}
+        elif tab is not None:
+            self._stream_tab.fill_(-1)
 
     def save_state(self, path):
         """The live ring as an exact-resume snapshot (part ``replay``): every row, link and tree leaf, the host mirrors, the

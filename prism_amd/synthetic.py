@@ -14,8 +14,7 @@ def fill_replay(buffer, n, obs_shape=(10, 10, 4), n_actions=6, seed=0, n_streams
     gen = torch.Generator(device=dev)
     gen.manual_seed(int(seed))
     O = int(np.prod(obs_shape))
-    if buffer._desc is None:
-        buffer._allocate(tuple(obs_shape))
+    buffer._allocate(tuple(obs_shape))       # (a used buffer comes back empty: the fill replaces its contents)
     idx = torch.arange(n, device=dev)
     done = torch.rand(n, device=dev, generator=gen) < p_done
     link = idx + n_streams
@@ -36,23 +35,9 @@ def fill_replay(buffer, n, obs_shape=(10, 10, 4), n_actions=6, seed=0, n_streams
     buffer.action[:n] = torch.randint(0, n_actions, (n,), device=dev, generator=gen, dtype=torch.int32)
     buffer.flags[:n] = flags
     buffer.link[:n] = link.to(torch.int32)
-    buffer.back.fill_(-1)
-    valid = link >= 0
-    buffer.back[link[valid]] = idx[valid].to(torch.int32)
-    buffer._size = n
-    buffer.buffer._writer._cursor = n % buffer.capacity
-    buffer._reset_streams()                  # a bulk load rewrites the ring behind the stream table (extend_batch)
-    buffer._slot_id[:n] = np.arange(n)
+    p = torch.randn(n, device=dev, generator=gen).abs().pow(alpha) + 1e-8 if buffer.use_per else None
+    buffer._seal(n, leaves=p)                # back-links, host mirrors, tree leaves + rebuild
     if buffer.use_per:
-        import ctypes
-        from prism_amd import _native as N
-        tc = buffer.tree_capacity
-        p = torch.randn(n, device=dev, generator=gen).abs().pow(alpha) + 1e-8
-        buffer.sum_tree[tc:tc + n] = p
-        buffer.min_tree[tc:tc + n] = p
         buffer.per_state[0] = 1.0
-        with torch.cuda.device(dev):
-            N.check(N.lib().prism_per_rebuild(ctypes.byref(buffer._desc), N.current_stream_handle()),
-                    "prism_per_rebuild")
     torch.cuda.synchronize(dev)
     return buffer

@@ -66,6 +66,18 @@ def test_ingest_argument_checks_without_device(lib, case):
     assert text in lib.prism_last_error(), lib.prism_last_error()
 
 
+@pytest.mark.parametrize("n_step", [0, 16])
+def test_ingest_shares_the_ring_check_n_step_range(lib, n_step):
+    """prism_replay_ingest runs the ring check every replay entry point runs: a descriptor whose n_step lies outside
+    [1, PRISM_MAX_NSTEP = 15] is refused before any device is touched."""
+    d = _fake_ring()
+    d.n_step = n_step
+    a = 0x40000000
+    rc = lib.prism_replay_ingest(ctypes.byref(d), 4, 7, 207, a, a, 0, a, a, a, a, None, a, 8, 0.5, 1e-8, None)
+    assert rc == -1, (rc, lib.prism_last_error())
+    assert b"n_step out of range" in lib.prism_last_error(), lib.prism_last_error()
+
+
 def test_extend_batch_rejects_host_side_ids_before_any_launch(lib):
     """Duplicate / out-of-range / miscounted ids in a HOST array are refused before the buffer allocates anything."""
     from prism_amd.experience import HipReplayBuffer

@@ -49,7 +49,7 @@ for cap, n in ((100_000, 30_000),):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     L = N.lib(); d = ctypes.byref(buf._desc); st = N.current_stream_handle()
-    dd = buf._stage_dev[0]
+    dd = buf._row_stage.sets[0]["d"]
     t_ins = timeit(lambda: L.prism_replay_insert(d, 1024, N.ptr(dd["slots"]), N.ptr(dd["obs"]), N.ptr(dd["succ"]), N.ptr(dd["reward"]),
                                                  N.ptr(dd["action"]), N.ptr(dd["flags"]), N.ptr(dd["prev"]), 0.5, 1e-8, st), n=50)
     print(f"extend+flush: {n / dt:9.0f} timesteps/s end to end (Python staging included); "
