@@ -1,5 +1,6 @@
 """Shared test helpers: golden-fixture decoding and oracle construction."""
 import contextlib
+import glob
 import io
 import os
 
@@ -15,6 +16,14 @@ UPDATE_CASES = ["iqn_small", "iqn_c3", "dqn_c2", "dqn_ln", "dqn_target_c2", "ful
                 "abl_iqn", "abl_ln_notarget", "abl_doubleq", "abl_ids", "abl_ids_var", "abl_sub",
                 # value squish of the TD target (loss_squish_fn_id): symlog / obs_look_further
                 "iqn_symlog", "full_olf", "dqn_symlog"]
+
+# n-step chains recorded from the live reference (tools/gen_golden.py gen_nstep / NSTEP_CHAINS): whatever lies in the fixture
+# directory, nstep_chain (n_step 3) first; tests/test_oracle_replay.py asserts which lengths and discounts they cover
+NSTEP_CHAINS = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(GOLDEN, "nstep_chain*.npz")))
+
+
+def load_chain(name):
+    return np.load(os.path.join(GOLDEN, f"{name}.npz"))
 
 
 def load_case(name):
@@ -214,3 +223,86 @@ def philox_uniform_index(seed, offset, batch, size):
     exp_buffer_factory.py:30-33): floor(x * size / 2**64) of a 64-bit Philox word, key "UNIF"."""
     r = philox4x32(seed, np.uint64(offset) + np.arange(batch, dtype=np.uint64), 0x554E4946)
     return np.array([((int(a) << 32 | int(b)) * int(size)) >> 64 for a, b in zip(r[:, 0], r[:, 1])], dtype=np.int64)
+
+
+# ---- the replay half of one fused step against the oracle (tests/test_gpu_fullsize_parity.py, tests/test_gpu_replay_geometry.py)
+def oracle_ring(buf, cfg):
+    """ReplayOracle over the device ring's small arrays; observation rows are filled lazily (calloc'ed, only the sampled
+    slots' pages ever become resident: the 1.25 M-slot ring would be 4 GB of host memory otherwise)."""
+    from oracle import per_ref
+    orc = per_ref.ReplayOracle(buf.capacity, buf.obs_elems, cfg.n_step_returns_length, cfg.gamma, cfg.per_alpha, 0.5)
+    orc.reward[:] = buf.reward.cpu().numpy()
+    orc.action[:] = buf.action.cpu().numpy()
+    orc.flags[:] = buf.flags.cpu().numpy()
+    orc.link[:] = buf.link.cpu().numpy()
+    orc.length = buf._size
+    assert orc.sampler.sum_tree.capacity == buf.tree_capacity
+    return orc
+
+
+def fill_rows(orc, buf, idx):
+    """Observation rows the n-step walk of `idx` can touch: the slots themselves and <= n_step - 1 hops of links."""
+    slots, cur = [idx], idx
+    for _ in range(orc.n_step - 1):
+        nxt = orc.link[cur]
+        cur = np.where(nxt >= 0, nxt, cur)
+        slots.append(cur)
+    s = np.unique(np.concatenate(slots))
+    st = torch.from_numpy(s).to(buf.device)
+    orc.obs[s] = buf.obs[st].cpu().numpy()
+    orc.succ_obs[s] = buf.succ_obs[st].cpu().numpy()
+
+
+def replay_snapshot(buf, agent):
+    """Before a fused step: both priority trees, the running maximum and the Philox counters the step's draws start at."""
+    snap = dict(per_ctr=int(agent.rng_counters[0].item()) if agent._B is not None else 0, draws0=buf._draws)
+    if buf.use_per:
+        snap.update(sum0=buf.sum_tree.cpu().numpy().copy(), min0=buf.min_tree.cpu().numpy().copy(),
+                    max0=float(buf.per_state[0].item()))
+    return snap
+
+
+def check_replay_front(buf, orc_ring, snap, B, step, fill=True):
+    """After the step: same trees, same masses -> same slots and IS weights; then the n-step walk + collate of those slots.
+    Returns (slots, the oracle's IS weights, the oracle's batch).  `fill`: the oracle's observation rows are filled lazily
+    from the device ring (oracle_ring)."""
+    smp = orc_ring.sampler
+    idx = buf._index.cpu().numpy()
+    sum0, min0, max0, per_ctr, draws0 = (snap.get(k) for k in ("sum0", "min0", "max0", "per_ctr", "draws0"))
+    if buf.use_per:
+        smp.sum_tree.values()[:] = sum0
+        smp.min_tree.values()[:] = min0
+        smp.max_priority = max0
+        p_sum = smp.sum_tree.query(0, buf._size)
+        mass = philox_per_mass(buf.seed, draws0 + per_ctr, B, p_sum)
+        idx_o, w_o, ps_o, pm_o = smp.sample(buf._size, mass)
+        np.testing.assert_array_equal(idx, idx_o, err_msg=f"step {step}: sampled slots")
+        np.testing.assert_array_equal(buf._weight.cpu().numpy(), w_o, err_msg=f"step {step}: IS weights")
+        assert np.float32(ps_o) == np.float32(buf.per_state[1].item()) and np.float32(pm_o) == np.float32(buf.per_state[2].item())
+    else:
+        # uniform replay (configs[0]; exp_buffer_factory.py:30-33): slot = floor(u * size) of the same Philox word, IS weight 1
+        idx_o = philox_uniform_index(buf.seed, draws0 + per_ctr, B, buf._size)
+        np.testing.assert_array_equal(idx, idx_o, err_msg=f"step {step}: uniformly sampled slots")
+        w_o = np.ones(B, dtype=np.float32)
+    # ---- n-step walk + collate
+    if fill:
+        fill_rows(orc_ring, buf, idx)
+    g = orc_ring.gather(idx)
+    np.testing.assert_array_equal(buf._obs.cpu().numpy().reshape(B, -1), g["obs"])
+    np.testing.assert_array_equal(buf._next_obs.cpu().numpy().reshape(B, -1), g["next_obs"])
+    np.testing.assert_array_equal(buf._reward.cpu().numpy().ravel(), g["reward"])
+    np.testing.assert_array_equal(buf._gamma.cpu().numpy().ravel(), g["gamma"])
+    np.testing.assert_array_equal(buf._nonterminal.cpu().numpy().ravel().astype(np.uint8), g["nonterminal"])
+    np.testing.assert_array_equal(buf._action.cpu().numpy().ravel(), g["action"])
+    return idx, w_o, g
+
+
+def check_replay_writeback(buf, smp, idx, td_abs, step):
+    """The oracle's update_priority fed the device's own |td|: EVERY node of both trees, duplicates included, and the
+    running maximum.  Uniform replay has nothing to write back."""
+    if not buf.use_per:
+        return
+    smp.update_priority(idx, td_abs)
+    np.testing.assert_array_equal(buf.sum_tree.cpu().numpy(), smp.sum_tree.values(), err_msg=f"step {step}: sum tree")
+    np.testing.assert_array_equal(buf.min_tree.cpu().numpy(), smp.min_tree.values(), err_msg=f"step {step}: min tree")
+    assert np.float32(smp.max_priority) == np.float32(buf.per_state[0].item())

@@ -16,6 +16,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import helpers as H
+
 pytestmark = pytest.mark.gpu
 
 CHECK_STEPS = (1, 10, 100)
@@ -34,36 +36,8 @@ def _learner(dev, base, B, cap, **over):
     return ln, cfg
 
 
-def _oracle_ring(buf, cfg):
-    """ReplayOracle over the device ring's small arrays; observation rows are filled lazily (calloc'ed, only the sampled
-    slots' pages ever become resident: the 1.25 M-slot ring would be 4 GB of host memory otherwise)."""
-    from oracle import per_ref
-    orc = per_ref.ReplayOracle(buf.capacity, buf.obs_elems, cfg.n_step_returns_length, cfg.gamma, cfg.per_alpha, 0.5)
-    orc.reward[:] = buf.reward.cpu().numpy()
-    orc.action[:] = buf.action.cpu().numpy()
-    orc.flags[:] = buf.flags.cpu().numpy()
-    orc.link[:] = buf.link.cpu().numpy()
-    orc.length = buf._size
-    assert orc.sampler.sum_tree.capacity == buf.tree_capacity
-    return orc
-
-
-def _fill_rows(orc, buf, idx):
-    """Observation rows the n-step walk of `idx` can touch: the slots themselves and <= n_step - 1 hops of links."""
-    slots, cur = [idx], idx
-    for _ in range(orc.n_step - 1):
-        nxt = orc.link[cur]
-        cur = np.where(nxt >= 0, nxt, cur)
-        slots.append(cur)
-    s = np.unique(np.concatenate(slots))
-    st = torch.from_numpy(s).to(buf.device)
-    orc.obs[s] = buf.obs[st].cpu().numpy()
-    orc.succ_obs[s] = buf.succ_obs[st].cpu().numpy()
-
-
 def _check_step(ln, cfg, orc_ring, step):
     from oracle.learner_ref import LearnerOracle
-    from tests import helpers as H
     buf, agent = ln.experience_buffer, ln.agent
     B = cfg.batch_size
     torch.cuda.synchronize()
@@ -71,44 +45,15 @@ def _check_step(ln, cfg, orc_ring, step):
     sd0 = {k: v.detach().cpu().clone() for k, v in agent.model.state_dict().items()}
     tg0 = None if agent.target_model is None else {k: v.detach().cpu().clone() for k, v in agent.target_model.state_dict().items()}
     opt0 = agent.optimizer.state_dict()
-    if buf.use_per:
-        sum0, min0 = buf.sum_tree.cpu().numpy().copy(), buf.min_tree.cpu().numpy().copy()
-        max0 = float(buf.per_state[0].item())
-    per_ctr = int(agent.rng_counters[0].item()) if agent._B is not None else 0
-    draws0 = buf._draws
+    snap = H.replay_snapshot(buf, agent)
     td = ln.step(timesteps_this_iteration=1).clone()
     torch.cuda.synchronize()
     buf.check_status()
     if step > 2:
         assert any(isinstance(g, tuple) for g in agent._graphs.values()), "the step did not run from a hipGraph"
 
-    # ---- sampling: same trees, same masses -> same slots and IS weights
-    smp = orc_ring.sampler
-    idx = buf._index.cpu().numpy()
-    if buf.use_per:
-        smp.sum_tree.values()[:] = sum0
-        smp.min_tree.values()[:] = min0
-        smp.max_priority = max0
-        p_sum = smp.sum_tree.query(0, buf._size)
-        mass = H.philox_per_mass(buf.seed, draws0 + per_ctr, B, p_sum)
-        idx_o, w_o, ps_o, pm_o = smp.sample(buf._size, mass)
-        np.testing.assert_array_equal(idx, idx_o, err_msg=f"step {step}: sampled slots")
-        np.testing.assert_array_equal(buf._weight.cpu().numpy(), w_o, err_msg=f"step {step}: IS weights")
-        assert np.float32(ps_o) == np.float32(buf.per_state[1].item()) and np.float32(pm_o) == np.float32(buf.per_state[2].item())
-    else:
-        # uniform replay (configs[0]; exp_buffer_factory.py:30-33): slot = floor(u * size) of the same Philox word, IS weight 1
-        idx_o = H.philox_uniform_index(buf.seed, draws0 + per_ctr, B, buf._size)
-        np.testing.assert_array_equal(idx, idx_o, err_msg=f"step {step}: uniformly sampled slots")
-        w_o = np.ones(B, dtype=np.float32)
-    # ---- n-step walk + collate
-    _fill_rows(orc_ring, buf, idx)
-    g = orc_ring.gather(idx)
-    np.testing.assert_array_equal(buf._obs.cpu().numpy().reshape(B, -1), g["obs"])
-    np.testing.assert_array_equal(buf._next_obs.cpu().numpy().reshape(B, -1), g["next_obs"])
-    np.testing.assert_array_equal(buf._reward.cpu().numpy().ravel(), g["reward"])
-    np.testing.assert_array_equal(buf._gamma.cpu().numpy().ravel(), g["gamma"])
-    np.testing.assert_array_equal(buf._nonterminal.cpu().numpy().ravel().astype(np.uint8), g["nonterminal"])
-    np.testing.assert_array_equal(buf._action.cpu().numpy().ravel(), g["action"])
+    # ---- sampling, n-step walk + collate (tests/helpers.py: the replay half, shared with tests/test_gpu_replay_geometry.py)
+    idx, w_o, g = H.check_replay_front(buf, orc_ring, snap, B, step)
     # ---- the TD update on that minibatch
     batch = dict(obs=torch.from_numpy(g["obs"]).view(B, 10, 10, 4), next_obs=torch.from_numpy(g["next_obs"]).view(B, 10, 10, 4),
                  reward=torch.from_numpy(g["reward"]), nonterminal=torch.from_numpy(g["nonterminal"].astype(bool)),
@@ -160,13 +105,8 @@ def _check_step(ln, cfg, orc_ring, step):
             needed.append(k)
         perr = max(perr, d)
     assert len(needed) <= 4, f"step {step}: {needed} needed the ill-conditioning allowance"
-    if not buf.use_per:
-        return err, perr, B - len(np.unique(idx))
     # ---- priority writeback with the device's own |td|: every node of both trees, duplicates included
-    smp.update_priority(idx, td_d.abs().numpy())
-    np.testing.assert_array_equal(buf.sum_tree.cpu().numpy(), smp.sum_tree.values(), err_msg=f"step {step}: sum tree")
-    np.testing.assert_array_equal(buf.min_tree.cpu().numpy(), smp.min_tree.values(), err_msg=f"step {step}: min tree")
-    assert np.float32(smp.max_priority) == np.float32(buf.per_state[0].item())
+    H.check_replay_writeback(buf, orc_ring.sampler, idx, td_d.abs().numpy(), step)
     return err, perr, B - len(np.unique(idx))
 
 
@@ -203,7 +143,7 @@ def test_graph_step_matches_oracle_at_bench_sizes(name):
     buf = ln.experience_buffer
     levels = int(np.log2(buf.tree_capacity))
     assert levels == (21 if cap > 1_000_000 else 17)
-    ring = _oracle_ring(buf, cfg)
+    ring = H.oracle_ring(buf, cfg)
     worst = [0.0, 0.0, 0]
     for step in range(1, max(CHECK_STEPS) + 1):
         if step in CHECK_STEPS:

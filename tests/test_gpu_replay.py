@@ -1,7 +1,6 @@
 """GPU parity: HBM replay ring + PER trees (through the C ABI) vs the CPU oracle.
 Bit-exact bar: sampled indices, tree nodes, IS weights (alpha = beta = 0.5 uses correctly
 rounded sqrt/div on both sides), n-step returns, gathered rows."""
-import os
 import weakref
 
 import numpy as np
@@ -25,10 +24,10 @@ def _mk_buffer(dev, capacity, B, O_shape=(10, 10, 4), **kw):
     return HipReplayBuffer(capacity, B, device=dev, **kw)
 
 
-def _chain_timesteps():
-    """Rebuild linked Timestep objects from the golden chain, in insertion order."""
+def _chain_timesteps(chain):
+    """Rebuild linked Timestep objects from a golden chain, in insertion order."""
     from prism_amd.experience import Timestep
-    g = np.load(os.path.join(H.GOLDEN, "nstep_chain.npz"))
+    g = H.load_chain(chain)
     N = int(g["N"])
     ts = [Timestep(id=i) for i in range(N)]
     keep = []
@@ -48,8 +47,9 @@ def _chain_timesteps():
     return g, ts, keep
 
 
-def test_extend_then_gather_matches_reference_chain(dev):
-    g, ts, keep = _chain_timesteps()
+@pytest.mark.parametrize("chain", H.NSTEP_CHAINS)
+def test_extend_then_gather_matches_reference_chain(dev, chain):
+    g, ts, keep = _chain_timesteps(chain)
     N = len(ts)
     buf = _mk_buffer(dev, N + 9, N, n_step=int(g["n_step"]), gamma=float(g["gamma"]), use_per=True)
     for t in ts:

@@ -1,6 +1,5 @@
-"""CPU oracle for the replay half: n-step/collate pinned to the reference's golden chain; the
+"""CPU oracle for the replay half: n-step/collate pinned to the reference's golden chains (n_step 1, 2, 3, 5, 15); the
 segment tree (PARITY UNPINNED, see oracle/per_oracle.c) checked for its own invariants."""
-import os
 
 import numpy as np
 import pytest
@@ -8,10 +7,6 @@ from hypothesis import given, settings, strategies as st
 
 from oracle import per_ref
 from tests import helpers as H
-
-
-def _load_chain():
-    return np.load(os.path.join(H.GOLDEN, "nstep_chain.npz"))
 
 
 def replay_from_chain(g):
@@ -25,8 +20,9 @@ def replay_from_chain(g):
     return rp
 
 
-def test_nstep_collate_matches_reference():
-    g = _load_chain()
+@pytest.mark.parametrize("chain", H.NSTEP_CHAINS)
+def test_nstep_collate_matches_reference(chain):
+    g = H.load_chain(chain)
     rp = replay_from_chain(g)
     N = int(g["N"])
     out = rp.gather(np.arange(N))
@@ -40,7 +36,30 @@ def test_nstep_collate_matches_reference():
     np.testing.assert_array_equal(out["obs"].reshape(g["exp_batch_obs"].shape), g["exp_batch_obs"])
     np.testing.assert_array_equal(out["next_obs"].reshape(g["exp_batch_next_obs"].shape),
                                   g["exp_batch_next_obs"])
-    assert g["exp_needs_n_step"].sum() > 0 and (~g["exp_batch_nonterminal"]).sum() > 0
+    assert (~g["exp_batch_nonterminal"]).sum() > 0
+    assert g["exp_needs_n_step"].sum() > 0 or int(g["n_step"]) == 1          # (a one-step walk is never incomplete)
+
+
+def test_golden_chains_hold_every_way_a_walk_ends():
+    """Over the recorded chains: walks that exhaust n_step, stop at a done, at a truncation and at a successor that is not
+    stored yet -- for every n_step > 1; n_step 1, 2, 3, 5 and 15 are all there, and two discounts besides 0.99."""
+    seen = {}
+    for chain in H.NSTEP_CHAINS:
+        g = H.load_chain(chain)
+        n_step, kinds = int(g["n_step"]), set()
+        for i in range(int(g["N"])):
+            cur, hops = i, 1
+            while hops < n_step and g["has_next"][cur] and not g["truncated"][cur] and g["link"][cur] >= 0:
+                cur, hops = int(g["link"][cur]), hops + 1
+            kinds.add("exhausted" if hops == n_step else "done" if g["done"][cur] else
+                      "truncated" if g["truncated"][cur] else "open")
+        seen.setdefault(n_step, set()).update(kinds)
+        seen.setdefault("gamma", set()).add(float(g["gamma"]))
+    assert {k for k in seen if k != "gamma"} == {1, 2, 3, 5, 15}
+    assert seen["gamma"] >= {0.99, 1.0, 0.5, 0.997}
+    assert seen[1] == {"exhausted"}
+    for n_step in (2, 3, 5, 15):
+        assert seen[n_step] == {"exhausted", "done", "truncated", "open"}, (n_step, seen[n_step])
 
 
 def test_tree_capacity_rule():

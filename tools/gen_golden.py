@@ -15,6 +15,8 @@ What is captured:
                      checksums after every step (+ full tensors for the small cases).
   nstep_chain.npz    TimestepBuffer._compute_n_step / _timesteps_to_batch
                      (prism/experience/timestep_buffer.py:79-238) on hand-built Timestep chains.
+  nstep_chain_*.npz  the same at n_step 1, 2, 5 and 15 and other discounts (NSTEP_CHAINS); written by
+                     `python tools/gen_golden.py nstep_more`, which never touches nstep_chain.npz.
 """
 import contextlib
 import io
@@ -228,19 +230,33 @@ def gen_update_case(name, overrides, B, steps, store_full):
     print(f"update_{name}: P={out['n_params']} total[-1]={out[pre + 'total']:.6f} act={out['act/action'].tolist()}")
 
 
-def gen_nstep():
-    """Hand-built Timestep chains pushed through the reference's n-step + collate."""
+# The additional n-step chains, each `tests/golden/<name>.npz`: (n_step, gamma, rows, per stream the period of episode ends,
+# per stream the period of truncations; 0 = never).  Streams of unequal episode lengths, so that the chains together hold walks
+# that exhaust n_step, stop at a done, stop at a truncation and stop at a successor that is not stored yet (the open row of
+# every stream at the end).  tests/helpers.py NSTEP_CHAINS lists the same names.
+NSTEP_CHAINS = {
+    "nstep_chain_n1": (1, 0.99, 66, (7, 5, 11), (5, 0, 4), 101),
+    "nstep_chain_n2": (2, 0.5, 68, (3, 6, 0, 9), (0, 4, 5, 7), 102),
+    "nstep_chain_n5": (5, 0.997, 70, (6, 13, 4, 0, 9), (11, 5, 0, 7, 0), 105),
+    "nstep_chain_n15_g1": (15, 1.0, 69, (0, 9, 17), (22, 5, 0), 115),
+    "nstep_chain_n15": (15, 0.99, 72, (17, 0, 6, 19), (0, 16, 11, 7), 116),
+}
+
+
+def _nstep_chain(n_step, gamma, rows, done_every, trunc_every, seed):
+    """Timestep chains of len(done_every) interleaved env streams, as the collector links them
+    (experience_collector.py:94-120), pushed through the reference's n-step + collate.  Returns (stored timesteps, arrays,
+    the buffer, its stand-in ring class, keep): `keep` holds the strong references -- the streams' open successors among them,
+    which the chain reaches through weak links only; whoever goes on using `stored` must hold it as long."""
     from prism.experience import Timestep, TimestepBuffer
     import weakref
 
     class FakeRB:
         _batch_size = 0
 
-    rng = np.random.default_rng(7)
-    n_step, gamma = 3, 0.99
+    rng = np.random.default_rng(seed)
     keep = []            # strong refs (links are weak)
-    rows = []            # per stored timestep: dict of scalars
-    env_streams = 3
+    env_streams = len(done_every)
     O = (10, 10, 4)
     next_id = [0]
 
@@ -249,7 +265,6 @@ def gen_nstep():
         next_id[0] += 1
         return t
 
-    # interleave several env streams, as the collector does (experience_collector.py:94-120)
     current = []
     for e in range(env_streams):
         t = new_ts()
@@ -257,13 +272,13 @@ def gen_nstep():
         current.append(t)
     stored = []          # completed timesteps in insertion order
     steps_per_stream = [0] * env_streams
-    for it in range(67):
+    for it in range(rows):
         e = it % env_streams
         cur = current[e]
         steps_per_stream[e] += 1
         k = steps_per_stream[e]
-        done = (k % 7 == 0)
-        trunc = (not done) and (k % 5 == 0)
+        done = bool(done_every[e]) and (k % done_every[e] == 0)
+        trunc = (not done) and bool(trunc_every[e]) and (k % trunc_every[e] == 0)
         cur.action = int(rng.integers(0, 6))
         cur.reward = float(np.float32(rng.standard_normal()))
         cur.done, cur.truncated = bool(done), bool(trunc)
@@ -315,6 +330,25 @@ def gen_nstep():
     out["exp_batch_nonterminal"] = batch["nonterminal"].numpy()
     out["exp_batch_gamma"] = batch["gamma"].numpy()
     out["exp_batch_action"] = batch["action"].numpy()
+    return stored, out, buf, FakeRB, keep
+
+
+def gen_nstep_more():
+    """The chains of NSTEP_CHAINS: other n-step lengths and discounts than nstep_chain.npz, which this leaves alone."""
+    for name, spec in NSTEP_CHAINS.items():
+        out = _nstep_chain(*spec)[1]
+        np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
+        print(f"{name}: n_step {spec[0]}, gamma {spec[1]}, {out['N']} timesteps; needs_n_step:",
+              int(out["exp_needs_n_step"].sum()), "terminal rows:", int((~out["exp_batch_nonterminal"]).sum()))
+
+
+def gen_nstep():
+    """Hand-built Timestep chains pushed through the reference's n-step + collate."""
+    from prism.experience import TimestepBuffer
+    n_step, gamma = 3, 0.99
+    # (`keep` lives to the end of this function: the open rows' successors must be alive when the reference saves the chain)
+    stored, out, buf, FakeRB, keep = _nstep_chain(n_step, gamma, 67, (7, 7, 7), (5, 5, 5), 7)
+    N = out["N"]
     np.savez_compressed(os.path.join(OUT, "nstep_chain.npz"), **out)
     print("nstep_chain:", N, "timesteps; needs_n_step:", int(out["exp_needs_n_step"].sum()),
           "terminal rows:", int((~out["exp_batch_nonterminal"]).sum()))
@@ -348,6 +382,7 @@ def gen_nstep():
                         reward=batch2["next"]["reward"].numpy(), nonterminal=batch2["nonterminal"].numpy(),
                         gamma=batch2["gamma"].numpy(), action=batch2["action"].numpy())
     print("ref_buffer: saved", N, "timesteps, the reference's own load keeps", len(kept))
+    del keep
 
 
 def gen_checkpoint():
@@ -424,10 +459,12 @@ def gen_checkpoint_rmsprop():
 def main():
     os.makedirs(OUT, exist_ok=True)
     _import_reference()
-    which = sys.argv[1:] or (list(CASES) + ["nstep", "config", "checkpoint", "checkpoint_rmsprop"])
+    which = sys.argv[1:] or (list(CASES) + ["nstep", "nstep_more", "config", "checkpoint", "checkpoint_rmsprop"])
     for name in which:
         if name == "nstep":
             gen_nstep()
+        elif name == "nstep_more":
+            gen_nstep_more()
         elif name == "checkpoint":
             gen_checkpoint()
         elif name == "checkpoint_rmsprop":
