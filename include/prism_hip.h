@@ -185,8 +185,8 @@ typedef struct prism_model_dims {
     int32_t embed_dim;     /* 1024 = 16*8*8 (minatar_cnn_model.py:14)                         */
     int32_t use_iqn;
     int32_t n_basis;       /* 64                                                              */
-    int32_t iqn_layers;    /* iqn_quantile_model_layers (1)                                   */
-    int32_t iqn_width;     /* iqn_quantile_model_feature_dim (128)                            */
+    int32_t iqn_layers;    /* iqn_quantile_model_layers: 1, or 0 = no trunk (the linear head)   */
+    int32_t iqn_width;     /* iqn_quantile_model_feature_dim (128 | 256); ignored at depth 0  */
     int32_t n_tau;         /* current-state quantile samples T                                */
     int32_t n_tau_next;    /* next-state quantile samples T'                                  */
     int32_t use_layer_norm;
@@ -210,8 +210,8 @@ typedef struct prism_param_offsets {
     int64_t n_params;
     int64_t conv_w, conv_b;
     int64_t phi_w, phi_b;
-    int64_t iqn_ln1_g, iqn_ln1_b, iqn_w1, iqn_b1;
-    int64_t iqn_ln2_g, iqn_ln2_b, iqn_w2, iqn_b2;
+    int64_t iqn_ln1_g, iqn_ln1_b, iqn_w1, iqn_b1;   /* the trunk: all -1 at iqn_layers 0                 */
+    int64_t iqn_ln2_g, iqn_ln2_b, iqn_w2, iqn_b2;   /* [LayerNorm] -> Linear(., A) in front of the estimates */
     int64_t head_base;    /* first float of head 0                                           */
     int64_t head_stride;  /* floats per head                                                 */
     int64_t h_ln1_g, h_ln1_b, h_w1, h_b1; /* relative to the head's base                     */
@@ -309,7 +309,17 @@ typedef struct prism_learner_desc {
 /* host: bytes of scratch prism_learner_fwd_bwd needs for (dims, batch). 0 on unsupported dims. */
 size_t prism_learner_workspace_bytes(const prism_model_dims *dims, int32_t batch);
 
-/* host: PRISM_OK if the kernels cover this (dims, batch) combination. */
+/* host: PRISM_OK if the kernels cover this (dims, batch) combination.  The envelope: embed_dim 1024, A 1..16, C 1..10,
+ * B 1..4096, squish_fn one of PRISM_SQUISH_*; and
+ *   IQN (use_iqn): n_basis 64; T, T' in {4, 8, 16, 32, 64}; B*T and B*T' multiples of 16; and either
+ *     iqn_layers 1 with iqn_width 128 or 256 (one trunk layer), or
+ *     iqn_layers 0 (iqn_model.py:32-46 with self.model = None: Hadamard product -> [LayerNorm(1024)] -> Linear(1024, A)),
+ *     iqn_width ignored as the reference ignores it, and n_heads 0.  Its parameter offsets: iqn_w1 / iqn_b1 / iqn_ln1_* = -1,
+ *     the final LayerNorm in iqn_ln2_*, and phi | [LayerNorm] | head contiguous in model.parameters() order;
+ *   Q heads: one single-Linear head (head_layers 1) without IQN, or up to 16 two-layer heads of width 128 or 256 with
+ *     B % 16 == 0, beside a one-layer IQN trunk or alone.
+ * Refused (PRISM_ERR_UNSUPPORTED): iqn_layers >= 2, other widths, Q heads beside a depth-0 IQN (the two-layer ensemble
+ * there would need the merged loss launch and the heads' embedding-gradient sum: not built). */
 int prism_learner_supported(const prism_model_dims *dims, int32_t batch);
 
 /* get_losses + backward: fills out_*, grads (complete dL/dparams of

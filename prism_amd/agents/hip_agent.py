@@ -236,7 +236,9 @@ def _offsets(model):
     o.conv_w, o.conv_b = g("embedding_model.model.0.weight", -1), g("embedding_model.model.0.bias", -1)
     d = "distribution_model."
     o.phi_w, o.phi_b = g(d + "phi.0.weight", -1), g(d + "phi.0.bias", -1)
-    if d + "model.model.1.weight" in table:          # LayerNorm on: [LN, Linear, ReLU] / [LN, Linear]
+    # LayerNorm on: trunk [LN, Linear, ReLU], head [LN, Linear].  Decided by the head: a model without a trunk
+    # (iqn_quantile_model_layers = 0, iqn_model.py:32-46) has no model.model.* at all and keeps every trunk field at -1
+    if d + "embedding_to_quantile_layer.1.weight" in table:
         o.iqn_ln1_g, o.iqn_ln1_b = g(d + "model.model.0.weight", -1), g(d + "model.model.0.bias", -1)
         o.iqn_w1, o.iqn_b1 = g(d + "model.model.1.weight", -1), g(d + "model.model.1.bias", -1)
         o.iqn_ln2_g = g(d + "embedding_to_quantile_layer.0.weight", -1)

@@ -90,7 +90,9 @@ static int check_learner(const prism_learner_desc *ld, LearnerPlan &pl, bool nee
     PRISM_CHECK_ARG(ld != nullptr, "null descriptor");
     if (iqn_supported(&ld->dims, ld->batch) != PRISM_OK) {
         set_error("prism_learner: model dims / batch not covered by the HIP kernels "
-                  "(need E=1024; IQN: K=64, H in {128,256}, one trunk layer, T in {4,8,16,32,64}, B*T %% 16 == 0; "
+                  "(need E=1024; IQN: K=64, T in {4,8,16,32,64}, B*T %% 16 == 0, and either one trunk layer with H in {128,256} "
+                  "or no trunk layer and no Q heads beside it -- the linear head next to a Q ensemble needs the merged loss "
+                  "launch and the heads' embedding-gradient sum, which are not built for it; "
                   "Q heads: one layer, or two layers of width 128/256 with B %% 16 == 0)");
         return PRISM_ERR_UNSUPPORTED;
     }
@@ -109,9 +111,23 @@ static int check_learner(const prism_learner_desc *ld, LearnerPlan &pl, bool nee
     PRISM_CHECK_ARG(ld->dims.n_heads == 0 || ld->dims.head_layers == 1 ||
                         (ld->off.h_w2 >= 0 && (!ld->dims.use_layer_norm || (ld->off.h_ln1_g >= 0 && ld->off.h_ln2_g >= 0))),
                     "two-layer Q-head parameter offsets missing");
-    PRISM_CHECK_ARG(!ld->dims.use_iqn || (ld->off.iqn_w1 >= 0 && ld->off.iqn_w2 >= 0 &&
-                                          (!ld->dims.use_layer_norm || (ld->off.iqn_ln1_g >= 0 && ld->off.iqn_ln2_g >= 0))),
-                    "IQN parameter offsets missing");
+    PRISM_CHECK_ARG(!ld->dims.use_iqn || pl.lin ||
+                        (ld->off.iqn_w1 >= 0 && ld->off.iqn_w2 >= 0 &&
+                         (!ld->dims.use_layer_norm || (ld->off.iqn_ln1_g >= 0 && ld->off.iqn_ln2_g >= 0))),
+                    "IQN parameter offsets missing (one trunk layer: iqn_w1, iqn_w2 and, with LayerNorm, iqn_ln1_g, iqn_ln2_g)");
+    if (pl.lin) {
+        // no trunk: phi | [the final LayerNorm, in iqn_ln2_*] | head, contiguous in model.parameters() order -- the
+        // backward's slabs are laid out like that and summed straight into the flat gradient
+        const prism_param_offsets &o = ld->off;
+        const int64_t after_phi = o.phi_w + (int64_t)E_DIM * K_BASIS + E_DIM;
+        PRISM_CHECK_ARG(o.phi_w >= 0 && o.phi_b == o.phi_w + (int64_t)E_DIM * K_BASIS && o.iqn_w2 >= 0 && o.iqn_b2 >= 0,
+                        "linear IQN head: parameter offsets missing (phi_w, phi_b, iqn_w2, iqn_b2)");
+        PRISM_CHECK_ARG(ld->dims.use_layer_norm
+                            ? (o.iqn_ln2_g == after_phi && o.iqn_ln2_b == after_phi + E_DIM && o.iqn_w2 == after_phi + 2 * E_DIM)
+                            : o.iqn_w2 == after_phi,
+                        "linear IQN head: phi, [LayerNorm in iqn_ln2_g / iqn_ln2_b] and iqn_w2 must follow each other");
+        PRISM_CHECK_ARG(o.iqn_b2 == o.iqn_w2 + (int64_t)ld->dims.n_actions * E_DIM, "linear IQN head: iqn_b2 must follow iqn_w2");
+    }
     if (!need_batch) return PRISM_OK;
     PRISM_CHECK_ARG(ld->obs && ld->next_obs && ld->reward && ld->nonterminal && ld->gamma && ld->action,
                     "null batch arrays");
@@ -142,6 +158,15 @@ static IqnPass make_pass(const IqnArgs &a, int kind, int set, const float *e, co
     p.stream_id = sid;
     p.kind = kind;
     return p;
+}
+
+// The arguments the embed / front launch sees.  Its parameter-only roles (front_extra_blocks: u / v tables, stream-packed
+// weight copies, cos tiles) exist for an IQN TRUNK; the linear head has none, and says so the one way those kernels read
+// it: no IQN part.  (The sampling and convolution workgroups do not look at the field.)
+static IqnArgs front_args(const IqnArgs &a) {
+    IqnArgs f = a;
+    if (iqn_linear(a.use_iqn, a.Hi)) f.use_iqn = 0;
+    return f;
 }
 
 // the kernel arguments of an update: the plan's decisions, the descriptor's pointers, the learner's pass list
@@ -355,6 +380,14 @@ static bool fwd_four_waves(const IqnArgs &aa, int tiles) {
 
 // the forward tiles of every pass: one launch when every tile kind has the same hidden width, else one per kind
 static int launch_fwd_tiles(const IqnArgs &a, hipStream_t stream) {
+    if (iqn_linear(a.use_iqn, a.Hi)) {
+        // the linear head: every pass is IQN rows (no Q heads beside it), one tile form for both gemm modes
+        int tiles = 0;
+        for (int i = 0; i < a.n_pass; ++i) tiles += a.pass[i].n_tiles;
+        if (tiles > 0)
+            hipLaunchKernelGGL(a.ln ? lin_fwd_tile_kernel<true> : lin_fwd_tile_kernel<false>, dim3(tiles), dim3(256), 0, stream, a);
+        return PRISM_OK;
+    }
     auto launch = [&](const IqnArgs &aa, int H, int tiles) {
         int rc = PRISM_OK;
         dispatch_hl(H, aa.ln, [&](auto h, auto l) {
@@ -393,7 +426,11 @@ static int launch_fwd_tiles(const IqnArgs &a, hipStream_t stream) {
 // its instantiation: the fused tail (always the full writer) with the dense tree top or without | preparing a writeback
 // the back launch finishes (`planned`) | the full writer, dense or not (also: no writeback at all)
 using PostKernel = void (*)(IqnArgs, PostWriteback, TailArgs);
-static PostKernel post_kernel(bool tail, bool planned, bool dense) {
+static PostKernel post_kernel(bool tail, bool planned, bool dense, bool lin = false) {
+    if (lin) {          // (the linear IQN head: its own instantiations, never the fused tail)
+        if (planned) return iqn_post_kernel<false, false, false, true>;
+        return dense ? iqn_post_kernel<true, false, true, true> : iqn_post_kernel<true, false, false, true>;
+    }
     if (tail) return dense ? iqn_post_kernel<true, true, true> : iqn_post_kernel<true, true, false>;
     if (planned) return iqn_post_kernel<false, false, false>;
     return dense ? iqn_post_kernel<true, false, true> : iqn_post_kernel<true, false, false>;
@@ -441,7 +478,7 @@ static int launch_post(const prism_learner_desc *ld, const LearnerPlan &pl, cons
     }
     TailArgs none;
     memset(&none, 0, sizeof(none));
-    hipLaunchKernelGGL(post_kernel(tail != nullptr, wb.plan != nullptr, pl.post_dense), dim3(nb), dim3(1024), 0, stream, a, wb,
+    hipLaunchKernelGGL(post_kernel(tail != nullptr, wb.plan != nullptr, pl.post_dense, pl.lin), dim3(nb), dim3(1024), 0, stream, a, wb,
                        tail ? *tail : none);
     PRISM_CHECK_LAUNCH();
     return PRISM_OK;
@@ -460,7 +497,8 @@ extern "C" int prism_learner_fwd_bwd(const prism_learner_desc *ld, prism_stream_
 
     if (!ld->embed_done) {
         ProfileScope ps_(K_EMBED, stream);
-        hipLaunchKernelGGL(iqn_embed_kernel, dim3(2 * B + front_extra_blocks(extra_dims(a))), dim3(256), 0, stream, a);
+        const IqnArgs af = front_args(a);
+        hipLaunchKernelGGL(iqn_embed_kernel, dim3(2 * B + front_extra_blocks(extra_dims(af))), dim3(256), 0, stream, af);
         PRISM_CHECK_LAUNCH();
     }
     {
@@ -474,6 +512,10 @@ extern "C" int prism_learner_fwd_bwd(const prism_learner_desc *ld, prism_stream_
         dispatch_hl(a.Hi, a.ln, [&](auto h, auto l) {
             hipLaunchKernelGGL((loss_both_kernel<decltype(h)::value, decltype(l)::value>), dim3(2 * B), dim3(512), 0, stream, a);
         });
+        PRISM_CHECK_LAUNCH();
+    } else if (pl.lin) {
+        ProfileScope ps_(K_LOSS, stream);
+        hipLaunchKernelGGL(a.ln ? lin_loss_kernel<true> : lin_loss_kernel<false>, dim3(B), dim3(256), 0, stream, a);
         PRISM_CHECK_LAUNCH();
     } else if (ld->dims.use_iqn && !pl.local_loss) {
         ProfileScope ps_(K_LOSS, stream);
@@ -512,6 +554,10 @@ extern "C" int prism_learner_fwd_bwd(const prism_learner_desc *ld, prism_stream_
         case BWD_BW4:
             rc = launch_lds(a.ln ? iqn_bwd4_kernel<true> : iqn_bwd4_kernel<false>, "iqn_bwd4", dim3((E_DIM / 32) * a.n_chunks), dim3(512),
                             BW4_LDS_BYTES, stream, a);
+            break;
+        case BWD_LIN:
+            hipLaunchKernelGGL(a.ln ? lin_bwd_kernel<true> : lin_bwd_kernel<false>, dim3((E_DIM / 16) * a.n_chunks), dim3(256), 0,
+                               stream, a);
             break;
         default:
             dispatch_hl(a.Hi, a.ln, [&](auto h, auto l) {
@@ -588,8 +634,9 @@ extern "C" int prism_act_forward(const prism_learner_desc *ld, const float *obs,
     a.act_inc = act_inc;
     // PRISM_ACT_WEIGHTS_CURRENT: the stream-packed weight copies / LayerNorm helpers in the workspace were built from the
     // parameters as they are now (by an earlier acting call since the last update): the launch is the n embeddings alone
-    const int extra = (ld->act_flags & PRISM_ACT_WEIGHTS_CURRENT) ? 0 : front_extra_blocks(extra_dims(a));
-    hipLaunchKernelGGL(iqn_embed_kernel, dim3((extra ? 2 * n : n) + extra), dim3(256), 0, stream, a);
+    const IqnArgs af = front_args(a);
+    const int extra = (ld->act_flags & PRISM_ACT_WEIGHTS_CURRENT) ? 0 : front_extra_blocks(extra_dims(af));
+    hipLaunchKernelGGL(iqn_embed_kernel, dim3((extra ? 2 * n : n) + extra), dim3(256), 0, stream, af);
     PRISM_CHECK_LAUNCH();
     if (heads > 0 && ld->dims.head_layers == 1) {
         // single-Linear DQN head: one workgroup per observation on the embeddings just written
@@ -731,8 +778,9 @@ extern "C" int prism_step_front(const prism_learner_desc *ld, const prism_replay
     f.action = const_cast<int64_t *>(ld->action);
     {
         ProfileScope ps_(K_FRONT, stream);
-        const int extra = front_extra_blocks(extra_dims(a));
-        hipLaunchKernelGGL(step_front_kernel, dim3(ld->batch + extra), dim3(256), 0, stream, a, *rp, f);
+        const IqnArgs af = front_args(a);
+        const int extra = front_extra_blocks(extra_dims(af));
+        hipLaunchKernelGGL(step_front_kernel, dim3(ld->batch + extra), dim3(256), 0, stream, af, *rp, f);
         PRISM_CHECK_LAUNCH();
     }
     return PRISM_OK;

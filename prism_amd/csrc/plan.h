@@ -49,7 +49,14 @@ static int iqn_supported(const prism_model_dims *d, int32_t B) {
     if (d->embed_dim != E_DIM) return PRISM_ERR_UNSUPPORTED;
     if (d->squish_fn < PRISM_SQUISH_NONE || d->squish_fn > PRISM_SQUISH_SYMLOG) return PRISM_ERR_UNSUPPORTED;
     if (d->use_iqn) {
-        if (d->n_basis != K_BASIS || d->iqn_layers != 1 || !width_ok(d->iqn_width)) return PRISM_ERR_UNSUPPORTED;
+        if (d->n_basis != K_BASIS) return PRISM_ERR_UNSUPPORTED;
+        if (d->iqn_layers == 0) {
+            // the linear head (iqn_lin_kernels.h): no trunk, so iqn_width is ignored as the reference ignores it; no Q heads
+            // beside it (the two-layer ensemble would need the merged loss launch and the de_q sum: not built)
+            if (d->n_heads != 0) return PRISM_ERR_UNSUPPORTED;
+        } else if (d->iqn_layers != 1 || !width_ok(d->iqn_width)) {
+            return PRISM_ERR_UNSUPPORTED;
+        }
         if (!pow2_ok(d->n_tau) || !pow2_ok(d->n_tau_next)) return PRISM_ERR_UNSUPPORTED;
         if ((B * d->n_tau) % 16 || (B * d->n_tau_next) % 16) return PRISM_ERR_UNSUPPORTED;
     }
@@ -71,13 +78,16 @@ static int iqn_supported(const prism_model_dims *d, int32_t B) {
 
 // the IQN trunk's backward: none (no IQN) | iqn_bwd_kernel | the 64-column bf16 form of width 128 (bwd3_kernels.h; the forward
 // then saves ReLU(phi)) | its width-256 form (bwd4_kernels.h: pairs of waves share 16 columns, one hidden half each)
-enum BwdForm { BWD_NONE, BWD_FP32, BWD_BW3, BWD_BW4 };
+// | lin_bwd_kernel of the linear head (no trunk)
+enum BwdForm { BWD_NONE, BWD_FP32, BWD_BW3, BWD_BW4, BWD_LIN };
 // the two-layer Q heads' input-side backward: none | qh_bwd_kernel by rows | by columns (B <= 128: a wave per column slice
 // over all rows) | two shared-operand GEMMs on the bf16 pipe (qbwd2_kernels.h)
 enum QBwdForm { QB_NONE, QB_ROWS, QB_COLS, QB_QB2 };
 
 struct LearnerPlan {
-    int Hi, Hq;                // hidden width of the IQN trunk / of the Q heads (128 where the part is absent)
+    int Hi, Hq;                // hidden width of the IQN trunk / of the Q heads (128 where the part is absent; Hi == 0: an IQN
+                               // without a trunk, the linear head)
+    bool lin;                  // ... that one: lin_fwd_tile / lin_loss / lin_bwd launches, post + back behind them
     int split;                 // forward GEMMs on the bf16 matrix pipe
     BwdForm bwd;
     int n_chunks, conv_in_bwd, conv_rows;
@@ -113,7 +123,7 @@ static void carve(const prism_model_dims &d, int B, void *base, LearnerPlan &p) 
     w.wpk[1] = c.f(iqn_pack_split_floats((int)Hi));
     w.cosb = c.f(R * K_BASIS);
     w.cospk = (unsigned int *)c.f((size_t)((R + 2 * Rn + 15) / 16 + 3) * CP_TILE);
-    w.phis = c.f(((R + 15) / 16) * 16 * (size_t)E_DIM);
+    w.phis = c.f(p.lin ? 0 : ((R + 15) / 16) * 16 * (size_t)E_DIM);
     w.mu1 = c.f(R);
     w.rstd1 = c.f(R);
     w.pre1 = c.f(R * Hi);
@@ -125,13 +135,13 @@ static void carve(const prism_model_dims &d, int B, void *base, LearnerPlan &p) 
     w.dq = c.f(R);
     w.c1 = c.f(R);
     w.c2 = c.f(R);
-    w.dpre1 = c.f(R * Hi);
+    w.dpre1 = c.f(p.lin ? R * LIN_AP : R * Hi);      // (linear head: dz[R][LIN_AP])
     w.Sb = c.f((size_t)B * Hi);
     w.Pb = c.f((size_t)B * Hi);
     w.Db = c.f(B);
     w.lossw = c.f(B);
     w.de_iqn = c.f((size_t)B * E_DIM);
-    w.slabs = c.f((size_t)MAX_CHUNKS * iqn_slab_floats((int)Hi, ln));
+    w.slabs = c.f((size_t)MAX_CHUNKS * p.slab);
     {
         const size_t post_rows = (size_t)((B + 3) / 4) * CONV_ROW;      // (post_conv_blocks(B, C) <= this)
         const size_t bwd_rows = (size_t)(E_DIM / 16) * MAX_CHUNKS * BWD_CONV_ROW;
@@ -178,16 +188,22 @@ static LearnerPlan make_plan(const prism_model_dims &d, int B, int gemm_mode = 0
     LearnerPlan p;
     memset(&p, 0, sizeof(p));
     const bool heads2 = d.n_heads && d.head_layers == 2;
-    p.Hi = d.use_iqn ? d.iqn_width : 128;
+    p.lin = d.use_iqn && d.iqn_layers == 0;
+    p.Hi = p.lin ? 0 : d.use_iqn ? d.iqn_width : 128;
     p.Hq = heads2 ? d.head_width : 128;
     const int mode = gemm_mode == PRISM_GEMM_FP32 || gemm_mode == PRISM_GEMM_BF16X3 ? gemm_mode : default_gemm_mode();
-    p.split = mode == PRISM_GEMM_BF16X3 && (d.use_iqn || heads2);
-    p.slab = iqn_slab_floats(p.Hi, d.use_layer_norm);
+    // (the linear head's products run the fp32 chain in both modes: iqn_lin_kernels.h)
+    p.split = mode == PRISM_GEMM_BF16X3 && ((d.use_iqn && !p.lin) || heads2);
+    p.slab = p.lin ? lin_slab_floats(d.n_actions, d.use_layer_norm) : iqn_slab_floats(p.Hi, d.use_layer_norm);
     p.q_slab = q_slab_floats(p.Hq, d.use_layer_norm);
     p.maxT = std::max(d.n_tau, d.n_tau_next);
     // the IQN backward and what depends on it: row chunks (gradient slabs), who folds the conv backward, in how many rows
     p.conv_rows = 4;
-    if (d.use_iqn && p.split && bw3_ok(p.Hi, B, d.n_tau, true)) {
+    if (p.lin) {
+        p.bwd = BWD_LIN;
+        p.n_chunks = lin_chunks(B, d.n_tau);
+        p.conv_in_bwd = 0;          // (d e is final per (sample, column) there: the post launch's conv role takes it)
+    } else if (d.use_iqn && p.split && bw3_ok(p.Hi, B, d.n_tau, true)) {
         p.bwd = BWD_BW3;
         p.n_chunks = BW3_RC;
         p.conv_in_bwd = bw3_conv_ok(d.use_iqn, d.n_heads, d.propagate_grad, d.n_tau, d.in_channels, B);
@@ -203,13 +219,15 @@ static LearnerPlan make_plan(const prism_model_dims &d, int B, int gemm_mode = 0
     }
     // the IQN loss finishes inside the forward tiles when current- and next-state rows of a sample run through the SAME
     // weights (no target network) and a 16-row tile holds whole samples (2 T <= 16)
-    p.local_loss = d.use_iqn && !d.has_target && d.n_tau_next == d.n_tau && d.n_tau <= 8;
+    p.local_loss = d.use_iqn && !p.lin && !d.has_target && d.n_tau_next == d.n_tau && d.n_tau <= 8;
     p.loss_waves = loss_waves(d.n_tau);
     p.merged_loss = d.use_iqn && !p.local_loss && heads2 && p.Hi == p.Hq && p.loss_waves == LOSS_WAVES;
     p.q_bwd = !heads2 ? QB_NONE : p.split && qb2_ok(p.Hq, B, d.n_heads, d.head_layers) ? QB_QB2 : B <= 128 ? QB_COLS : QB_ROWS;
     p.q_de_slots = p.q_bwd == QB_QB2 ? 2 : d.n_heads;
     p.post_blocks = d.head_layers == 1 && d.n_heads
                         ? post_blocks_dqn1(d.in_channels)
+                    : p.lin      // conv role | slab sums | lin_small_block
+                        ? post_conv_blocks(B, d.in_channels) + post_slab_blocks(p.slab, p.n_chunks) + 1
                         : post_blocks(B, d.in_channels, d.use_iqn, d.n_heads, p.conv_in_bwd != 0, p.slab, p.q_slab, p.Hi, p.Hq, p.n_chunks);
     p.writeback_rides = fused_replay && fused_replay->tree && fused_index;
     p.split_writeback = B <= 256;
@@ -220,7 +238,8 @@ static LearnerPlan make_plan(const prism_model_dims &d, int B, int gemm_mode = 0
     // to hide behind its grid barrier: a priority writeback riding along (measured without, uniform replay + one-layer DQN
     // head: 32.7 us fused vs 30.1 us as two launches) or an IQN's gradient slabs (additive ablation base, uniform replay,
     // width 256: 95.5 vs 97.3 us per step).
-    p.tail_wanted = fuse_tail && grad_scale == 1.0f && (p.writeback_rides || d.use_iqn);
+    // (The linear head takes the post + back pair: the fused tail has not been measured for it.)
+    p.tail_wanted = fuse_tail && grad_scale == 1.0f && (p.writeback_rides || d.use_iqn) && !p.lin;
     carve(d, B, workspace, p);
     return p;
 }

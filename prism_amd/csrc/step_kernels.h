@@ -5,6 +5,7 @@
 // replay_kernels.h, so fused and unfused paths execute the same arithmetic.
 #pragma once
 #include "iqn_kernels.h"
+#include "iqn_lin_kernels.h"
 #include "qhead_kernels.h"
 #include "replay_kernels.h"
 #include "opt_kernels.h"
@@ -694,9 +695,12 @@ struct PostWriteback {        // optional: prism_per_update(index, |out_td|) as 
 // TAIL: the launch also clips and applies Adam (single GPU): a grid barrier after the partial norms, then every role
 // block updates its share of the flat parameter vector; the writeback block (always the full writer then) advances the
 // device RNG counters and does not take part in the barrier.
-template <bool WB_FULL, bool TAIL, bool DENSE>
+// LIN: the IQN has no trunk (iqn_lin_kernels.h): its small-tensor role is ONE workgroup (lin_small_block), never with TAIL.
+// An instantiation of its own, so that the forms every other model runs compile to what they compiled to without it.
+template <bool WB_FULL, bool TAIL, bool DENSE, bool LIN = false>
 __global__ __launch_bounds__(1024) void iqn_post_kernel(IqnArgs a, PostWriteback wb, TailArgs tl) {
     static_assert(WB_FULL || !TAIL, "the fused tail has nobody to finish a prepared writeback");
+    static_assert(!(LIN && TAIL), "the linear head runs the post + back launch pair");
     kernarg_prefetch<sizeof(IqnArgs) + sizeof(PostWriteback) + sizeof(TailArgs)>();
     // (fused tail) the optimizer's step count, read before anything else: workgroup 0 advances it behind the barrier
     const int64_t step_now = TAIL ? tl.adam.step[0] : 0;
@@ -704,7 +708,8 @@ __global__ __launch_bounds__(1024) void iqn_post_kernel(IqnArgs a, PostWriteback
     constexpr int POOL = PER_UPDATE_LDS_BYTES > (int)(CONV_LDS_FLOATS * sizeof(float)) ? PER_UPDATE_LDS_BYTES
                                                                                        : (int)(CONV_LDS_FLOATS * sizeof(float));
     // (one role per workgroup: the roles never share the pool in time; each must fit it)
-    static_assert(POOL >= (int)(SMALL_POOL_FLOATS * sizeof(float)), "small-tensor fold must fit the pool");
+    static_assert(POOL >= (int)(SMALL_POOL_FLOATS * sizeof(float)) && POOL >= (int)(LIN_SMALL_POOL_FLOATS * sizeof(float)),
+                  "small-tensor folds must fit the pool");
     static_assert(POOL >= (int)(16 * CONV_FOLD_W * sizeof(float)) && POOL >= (int)(1024 * sizeof(float)),
                   "conv fold staging must fit the pool");
     __shared__ __attribute__((aligned(16))) char s_pool[POOL];
@@ -879,7 +884,7 @@ __global__ __launch_bounds__(1024) void iqn_post_kernel(IqnArgs a, PostWriteback
         blk -= n_conv;
         bool done = false;
         if (a.use_iqn) {
-            const int n_slab = post_slab_blocks(a.slab, a.n_chunks), n_small = post_small_blocks(a.Hi);
+            const int n_slab = post_slab_blocks(a.slab, a.n_chunks), n_small = LIN ? 1 : post_small_blocks(a.Hi);
             if (blk < n_slab) {
                 // sixteen row chunks (the 64-column backward): a float4 is summed by TWO adjacent lanes, eight chunks each
                 // ((c0 + .. + c7) + (c8 + .. + c15), the same in both lanes); the even lane owns the result
@@ -919,7 +924,8 @@ __global__ __launch_bounds__(1024) void iqn_post_kernel(IqnArgs a, PostWriteback
                 }
                 done = true;
             } else if (blk < n_slab + n_small) {
-                small_tensor_block(a, blk - n_slab, sq, reinterpret_cast<float *>(s_pool));
+                if constexpr (LIN) lin_small_block(a, sq, reinterpret_cast<float *>(s_pool));
+                else small_tensor_block(a, blk - n_slab, sq, reinterpret_cast<float *>(s_pool));
                 far_all = true;
                 done = true;
             } else {

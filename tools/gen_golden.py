@@ -114,6 +114,11 @@ CASES = {
     "full_olf": (dict(use_ids=True, use_iqn=True, use_target_network=True, loss_squish_fn_id="obs_look_further"), 16, 2, False),
     "dqn_symlog": (dict(use_ids=False, use_iqn=False, use_dqn=True, use_layer_norm=False, loss_squish_fn_id="symlog"),
                    32, 2, False),
+    # ---- the linear IQN head (iqn_quantile_model_layers = 0: no trunk, iqn_model.py:32-46), LayerNorm on and off
+    "iqn_l0": (dict(use_ids=False, use_iqn=True, use_dqn=False, iqn_quantile_model_layers=0), 32, 2, False),
+    "iqn_l0_noln_dq": (dict(use_ids=False, use_iqn=True, use_dqn=False, iqn_quantile_model_layers=0, use_layer_norm=False,
+                            use_target_network=True, use_double_q_learning=True, iqn_n_current_state_quantile_samples=16,
+                            iqn_n_next_state_quantile_samples=16, loss_squish_fn_id="symlog"), 16, 2, False),
     # ---- the optimizers beside Adam (agent_factory.py:48-58): centered RMSprop (use_adam off, use_rmsprop on), plain SGD
     "dqn_c2_rmsprop": (dict(use_ids=False, use_iqn=False, use_dqn=True, use_layer_norm=False, use_adam=False,
                             use_rmsprop=True), 256, 3, True),
