@@ -131,6 +131,35 @@ int prism_replay_ingest(const prism_replay_desc *rp, int32_t n, int64_t first_sl
                         const int32_t *stream_ids, int64_t *stream_tab, int32_t n_streams,
                         float alpha, float eps, prism_stream_t stream);
 
+/* prism_replay_ingest with the rest of what the reference's collector does per timestep
+ * (collector_process_interface.py:129-139, experience_collector.py:113-118): the reward clip and, per stream,
+ * the episodic return with the training-reward EMA -- same launch, one more workgroup, still no host read. */
+#define PRISM_CLIP_NONE  0
+#define PRISM_CLIP_CLAMP 1  /* r < -1 ? -1 : (r > 1 ? 1 : r): NaN and -0.0 pass through unchanged ("dopamine_clamp") */
+typedef struct prism_episode_desc {
+    int32_t reward_clip;       /* PRISM_CLIP_*: applied to the reward STORED in the ring only               */
+    int32_t count_first_step;  /* 0: the reference's rule (an episode's first reward is not counted); 1: it is */
+    double ema;                /* training_reward_ema, in [0, 1]                                            */
+    double *ep_return;         /* [n_streams] running return of each stream's open episode; NULL: no tracking */
+    int32_t *ep_length;        /* [n_streams] steps of the open episode so far (0 = none open)              */
+    double *stats;             /* [4] training reward (EMA) | sum of finished returns | last finished return | unused */
+    int64_t *counts;           /* [4] episodes finished | sum of their lengths | rows tracked | unused      */
+} prism_episode_desc;
+
+/* The ring, flags, links, stream table, default priorities and status word come out bit for bit as from
+ * prism_replay_ingest fed rewards the host clipped beforehand.  Per row of stream s, in float64 on the RAW reward:
+ * len = ep_length[s] + 1; ret = 0 if the episode had no step yet and count_first_step == 0, else reward + ep_return[s];
+ * done | truncated: an episode end (ret, len), both accumulators of s return to 0; else they are stored back.  Ends are
+ * folded in row order: counts[0] += 1, counts[1] += len, stats[1] += ret, stats[2] = ret and
+ * stats[0] = first ever ? ret : ema * stats[0] + (1 - ema) * ret (two products, one sum, each rounded).  counts[2] grows
+ * by the rows tracked.  Rows stored unlinked (id outside the table / repeated in the call) are not tracked; a repeated
+ * stream's accumulators are zeroed.  ep_return .. counts are all set or all NULL (clip only). */
+int prism_replay_ingest_tracked(const prism_replay_desc *rp, int32_t n, int64_t first_slot, int64_t serial0,
+                                const void *obs, const void *next_obs, int32_t obs_kind, const float *reward,
+                                const int32_t *action, const uint8_t *done, const uint8_t *truncated,
+                                const int32_t *stream_ids, int64_t *stream_tab, int32_t n_streams,
+                                float alpha, float eps, const prism_episode_desc *ep, prism_stream_t stream);
+
 /* PrioritizedSampler.sample (called at timestep_buffer.py:37): p_sum/p_min = query(0,size);
  * index[i] = min(scan_lower_bound(mass[i]), size-1); weight[i] = (leaf/p_min) ** -beta.
  * mass == NULL: masses are drawn on the device, U(0,p_sum) in float64 narrowed to fp32, from

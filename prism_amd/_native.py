@@ -16,6 +16,7 @@ PRISM_MAX_NSTEP = 15
 FLAG_DONE, FLAG_TRUNC, FLAG_HAS_NEXT = 1, 2, 4
 STATUS_NONPOSITIVE_PSUM, STATUS_NONPOSITIVE_PMIN, STATUS_INGEST_DUP_STREAM = 1, 2, 4
 OBS_F32, OBS_U8 = 0, 1
+CLIP_NONE, CLIP_CLAMP = 0, 1
 INGEST_MAX_STREAMS = 65536
 WS_STATUS_WORD, WS_STATUS_BARRIER_TIMEOUT, WS_STATUS_COLLECTIVE_TIMEOUT = 7, 1, 2
 GEMM_MODES = {"auto": 0, "fp32": 1, "bf16x3": 2}
@@ -37,6 +38,11 @@ class ReplayDesc(ctypes.Structure):
                 ("obs", c_vp), ("succ_obs", c_vp), ("reward", c_vp), ("action", c_vp), ("flags", c_vp),
                 ("link", c_vp), ("back", c_vp), ("tree", c_vp), ("per_state", c_vp),
                 ("status", c_vp), ("gammas", ctypes.c_double * (PRISM_MAX_NSTEP + 1))]
+
+
+class EpisodeDesc(ctypes.Structure):
+    _fields_ = [("reward_clip", c_i32), ("count_first_step", c_i32), ("ema", ctypes.c_double), ("ep_return", c_vp),
+                ("ep_length", c_vp), ("stats", c_vp), ("counts", c_vp)]
 
 
 class ModelDims(ctypes.Structure):
@@ -101,6 +107,8 @@ SIGNATURES = {
                                             c_f32, c_f32, c_vp]),
     "prism_replay_ingest": (ctypes.c_int, [_P(ReplayDesc), c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
                                             c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_vp]),
+    "prism_replay_ingest_tracked": (ctypes.c_int, [_P(ReplayDesc), c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                                    c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, _P(EpisodeDesc), c_vp]),
     "prism_per_sample": (ctypes.c_int, [_P(ReplayDesc), c_i64, c_i32, c_vp, c_u64, c_u64, c_f32, c_vp, c_vp,
                                          c_vp]),
     "prism_uniform_sample": (ctypes.c_int, [c_i64, c_i32, c_u64, c_u64, c_vp, c_vp]),

@@ -1,28 +1,43 @@
-// Host entry point of the vectorised producer seam (C ABI in include/prism_hip.h).
+// Host entry points of the vectorised producer seam (C ABI in include/prism_hip.h).
+#include <cmath>
+
 #include "ingest_kernels.h"
 
 using namespace prism;
 
-extern "C" int prism_replay_ingest(const prism_replay_desc *rp, int32_t n, int64_t first_slot, int64_t serial0,
-                                   const void *obs, const void *next_obs, int32_t obs_kind, const float *reward,
-                                   const int32_t *action, const uint8_t *done, const uint8_t *truncated,
-                                   const int32_t *stream_ids, int64_t *stream_tab, int32_t n_streams, float alpha,
-                                   float eps, prism_stream_t stream) {
-    int rc = check_ring(rp, false);
-    if (rc) return rc;
-    PRISM_CHECK_ARG(!rp->tree || rp->tree_capacity <= (1ll << TREE_MAX_LEVELS),
-                    "prioritized capacity above 2^24 - 1 rows");
-    PRISM_CHECK_ARG(n >= 1 && n <= rp->capacity, "n must be in [1, capacity]");
-    PRISM_CHECK_ARG(n_streams >= 1 && n_streams <= INGEST_MAX_STREAMS, "n_streams must be in [1, 65536]");
-    PRISM_CHECK_ARG(obs_kind == PRISM_OBS_F32 || obs_kind == PRISM_OBS_U8,
-                    "obs_kind must be PRISM_OBS_F32 or PRISM_OBS_U8");
-    PRISM_CHECK_ARG(first_slot >= 0 && first_slot < rp->capacity, "first_slot must be in [0, capacity)");
-    PRISM_CHECK_ARG(serial0 >= 0 && serial0 % rp->capacity == first_slot,
-                    "serial0 must be >= 0 and serial0 % capacity == first_slot");
-    PRISM_CHECK_ARG(obs && next_obs && reward && action && done && truncated, "null transition array");
-    PRISM_CHECK_ARG(stream_tab != nullptr, "null stream_tab");
-    PRISM_CHECK_ARG(stream_ids != nullptr || n <= n_streams, "stream_ids NULL (row i is stream i) needs n <= n_streams");
+// The checks both entry points run (a macro: the message names the entry point that was called).
+#define INGEST_CHECK_ARGS()                                                                                             \
+    do {                                                                                                                \
+        int rc = check_ring(rp, false);                                                                                 \
+        if (rc) return rc;                                                                                              \
+        PRISM_CHECK_ARG(!rp->tree || rp->tree_capacity <= (1ll << TREE_MAX_LEVELS),                                     \
+                        "prioritized capacity above 2^24 - 1 rows");                                                    \
+        PRISM_CHECK_ARG(n >= 1 && n <= rp->capacity, "n must be in [1, capacity]");                                     \
+        PRISM_CHECK_ARG(n_streams >= 1 && n_streams <= INGEST_MAX_STREAMS, "n_streams must be in [1, 65536]");          \
+        PRISM_CHECK_ARG(obs_kind == PRISM_OBS_F32 || obs_kind == PRISM_OBS_U8,                                          \
+                        "obs_kind must be PRISM_OBS_F32 or PRISM_OBS_U8");                                              \
+        PRISM_CHECK_ARG(first_slot >= 0 && first_slot < rp->capacity, "first_slot must be in [0, capacity)");           \
+        PRISM_CHECK_ARG(serial0 >= 0 && serial0 % rp->capacity == first_slot,                                           \
+                        "serial0 must be >= 0 and serial0 % capacity == first_slot");                                   \
+        PRISM_CHECK_ARG(obs && next_obs && reward && action && done && truncated, "null transition array");             \
+        PRISM_CHECK_ARG(stream_tab != nullptr, "null stream_tab");                                                      \
+        PRISM_CHECK_ARG(stream_ids != nullptr || n <= n_streams,                                                        \
+                        "stream_ids NULL (row i is stream i) needs n <= n_streams");                                    \
+    } while (0)
+
+namespace {
+
+struct IngestLaunch {
     IngestArgs a;
+    int threads, row_wgs;
+};
+
+IngestLaunch ingest_plan(const prism_replay_desc *rp, int32_t n, int64_t first_slot, int64_t serial0, const void *obs,
+                         const void *next_obs, int32_t obs_kind, const float *reward, const int32_t *action,
+                         const uint8_t *done, const uint8_t *truncated, const int32_t *stream_ids, int64_t *stream_tab,
+                         int32_t n_streams, float alpha, float eps) {
+    IngestLaunch L;
+    IngestArgs &a = L.a;
     a.n = n;
     a.n_streams = n_streams;
     a.obs_kind = obs_kind;
@@ -41,11 +56,46 @@ extern "C" int prism_replay_ingest(const prism_replay_desc *rp, int32_t n, int64
     a.stream_tab = stream_tab;
     a.alpha = alpha;
     a.eps = eps;
-    const int threads = n >= 1024 ? 1024 : ((n + 127) / 128) * 128;
-    const int per_wg = threads / INGEST_ROW_THREADS;
-    int row_wgs = (n + per_wg - 1) / per_wg;
-    if (row_wgs > INGEST_MAX_ROW_WGS) row_wgs = INGEST_MAX_ROW_WGS;
-    hipLaunchKernelGGL(replay_ingest_kernel, dim3(1 + row_wgs), dim3(threads), 0, (hipStream_t)stream, *rp, a);
+    L.threads = n >= 1024 ? 1024 : ((n + 127) / 128) * 128;
+    const int per_wg = L.threads / INGEST_ROW_THREADS;
+    L.row_wgs = (n + per_wg - 1) / per_wg;
+    if (L.row_wgs > INGEST_MAX_ROW_WGS) L.row_wgs = INGEST_MAX_ROW_WGS;
+    return L;
+}
+
+}  // namespace
+
+extern "C" int prism_replay_ingest(const prism_replay_desc *rp, int32_t n, int64_t first_slot, int64_t serial0,
+                                   const void *obs, const void *next_obs, int32_t obs_kind, const float *reward,
+                                   const int32_t *action, const uint8_t *done, const uint8_t *truncated,
+                                   const int32_t *stream_ids, int64_t *stream_tab, int32_t n_streams, float alpha,
+                                   float eps, prism_stream_t stream) {
+    INGEST_CHECK_ARGS();
+    const IngestLaunch L = ingest_plan(rp, n, first_slot, serial0, obs, next_obs, obs_kind, reward, action, done, truncated,
+                                       stream_ids, stream_tab, n_streams, alpha, eps);
+    hipLaunchKernelGGL(replay_ingest_kernel, dim3(1 + L.row_wgs), dim3(L.threads), 0, (hipStream_t)stream, *rp, L.a);
+    PRISM_CHECK_LAUNCH();
+    return PRISM_OK;
+}
+
+extern "C" int prism_replay_ingest_tracked(const prism_replay_desc *rp, int32_t n, int64_t first_slot, int64_t serial0,
+                                           const void *obs, const void *next_obs, int32_t obs_kind, const float *reward,
+                                           const int32_t *action, const uint8_t *done, const uint8_t *truncated,
+                                           const int32_t *stream_ids, int64_t *stream_tab, int32_t n_streams, float alpha,
+                                           float eps, const prism_episode_desc *ep, prism_stream_t stream) {
+    INGEST_CHECK_ARGS();
+    PRISM_CHECK_ARG(ep != nullptr, "null episode descriptor");
+    PRISM_CHECK_ARG(ep->reward_clip == PRISM_CLIP_NONE || ep->reward_clip == PRISM_CLIP_CLAMP,
+                    "reward_clip must be PRISM_CLIP_NONE or PRISM_CLIP_CLAMP");
+    PRISM_CHECK_ARG(std::isfinite(ep->ema) && ep->ema >= 0.0 && ep->ema <= 1.0, "ema must be finite and in [0, 1]");
+    const int set = (ep->ep_return != nullptr) + (ep->ep_length != nullptr) + (ep->stats != nullptr) + (ep->counts != nullptr);
+    PRISM_CHECK_ARG(set == 0 || set == 4, "ep_return, ep_length, stats and counts must be all set or all NULL");
+    PRISM_CHECK_ARG(ep->count_first_step == 0 || ep->count_first_step == 1, "count_first_step must be 0 or 1");
+    const IngestLaunch L = ingest_plan(rp, n, first_slot, serial0, obs, next_obs, obs_kind, reward, action, done, truncated,
+                                       stream_ids, stream_tab, n_streams, alpha, eps);
+    // workgroup 0 and the row stores keep their indices; the episode role is the last workgroup
+    hipLaunchKernelGGL(replay_ingest_tracked_kernel, dim3(2 + L.row_wgs), dim3(L.threads), 0, (hipStream_t)stream, *rp, L.a,
+                       *ep);
     PRISM_CHECK_LAUNCH();
     return PRISM_OK;
 }

@@ -5,7 +5,8 @@
 //
 // Roles by workgroup, no data shared between them (so no cross-workgroup wait):
 //   workgroup 0        plan (predecessor of every row from the stream table) + link + default priority
-//   workgroups 1 ..    row store: copy / widen the observations, reward, action, flags
+//   workgroups 1 ..    row store: copy / widen the observations, reward (clipped, tracked launch), action, flags
+//   last workgroup     (tracked launch only, prism_replay_ingest_tracked) episode returns + the training-reward EMA
 // The stream table holds, per stream, the WRITE SERIAL of the stream's open row (or -1).  A ring slot is reused exactly
 // every `capacity` writes, so "the open row is still in the ring" is `serial0 + i - w < capacity` and its slot is
 // `w % capacity`: no per-slot owner array, no host dict.
@@ -37,19 +38,163 @@ struct IngestArgs {
     float alpha, eps;
 };
 
-static __global__ __launch_bounds__(1024) void replay_ingest_kernel(prism_replay_desc rp, IngestArgs a) {
+// The two bitmaps of one call's stream ids, by the whole workgroup (zeroed here; a barrier must follow before they are
+// read).  True for a thread that met an id outside the table or one already seen.
+// (tid, bd and the grid's shape are read by the two kernels and handed down to these routines: read in a kernel they are
+// plain words of the dispatch, read in a function the compiler also emits the partial-last-workgroup form of blockDim.)
+static __device__ __forceinline__ bool ingest_mark_streams(const int32_t *ids, int n, int n_streams, uint32_t *s_seen,
+                                                           uint32_t *s_dup, int tid, int bd) {
+    for (int w = tid; w < (n_streams + 31) >> 5; w += bd) {
+        s_seen[w] = 0u;
+        s_dup[w] = 0u;
+    }
+    __syncthreads();
+    bool flag = false;
+    for (int i = tid; i < n; i += bd) {
+        const int32_t sid = ids[i];
+        if ((uint32_t)sid >= (uint32_t)n_streams) {                  // outside the table: stored unlinked, table untouched
+            flag = true;
+            continue;
+        }
+        const uint32_t bit = 1u << (sid & 31);
+        if (atomicOr(&s_seen[sid >> 5], bit) & bit) {
+            atomicOr(&s_dup[sid >> 5], bit);
+            flag = true;
+        }
+    }
+    return flag;
+}
+
+// ---- episode role: one workgroup, the last of the tracked launch.  It reads the call's arguments and its own four
+// arrays only -- nothing the other roles write -- and rebuilds the id bitmaps for itself, so it waits on nobody.
+// Passes of blockDim.x rows.  Per row in parallel (the ids of a call are distinct): the stream's running return and
+// length; a row with done | truncated is an episode end.  The ends of a pass are compacted in ROW ORDER (ballot +
+// per-wave counts) and ONE lane folds them in that order: the EMA is a sequential recurrence in float64 whose rounding
+// order is the host's (the reference folds timesteps as they reach the buffer).  The build's -ffp-contract=off keeps its
+// two products and the sum separate roundings; it must not be written with fma.
+constexpr int EP_PASS = 1024;
+static __device__ __forceinline__ void ingest_episode_role(const IngestArgs &a, const prism_episode_desc &ep, char *s_pool,
+                                                           int tid, int bd) {
+    __shared__ double s_ret[EP_PASS];
+    __shared__ int32_t s_len[EP_PASS];
+    __shared__ int s_wcnt[EP_PASS / 64];
+    __shared__ int s_tracked;
+    if (!ep.ep_return) return;                                       // clip without tracking
+    const int lane = tid & 63, wave = tid >> 6, n_waves = bd >> 6;
+    const int n = a.n, n_streams = a.n_streams;
+    const int32_t *ids = a.stream_ids;
+    uint32_t *s_seen = reinterpret_cast<uint32_t *>(s_pool + IG_SEEN.off);
+    uint32_t *s_dup = reinterpret_cast<uint32_t *>(s_pool + IG_DUP.off);
+    if (tid == 0) s_tracked = 0;
+    if (ids) ingest_mark_streams(ids, n, n_streams, s_seen, s_dup, tid, bd);      // (workgroup 0 owns the status bit)
+    __syncthreads();
+    const bool count_first = ep.count_first_step != 0;
+    const double ema = ep.ema;
+    // lane 0 of wave 0 carries the finished-episode words through the passes
+    int64_t c_eps = 0, c_len = 0;
+    double st_ema = 0.0, st_sum = 0.0, st_last = 0.0;
+    if (tid == 0) {
+        c_eps = ep.counts[0];
+        c_len = ep.counts[1];
+        st_ema = ep.stats[0];
+        st_sum = ep.stats[1];
+        st_last = ep.stats[2];
+    }
+    for (int base = 0; base < n; base += bd) {
+        const int i = base + tid;
+        bool end = false, tracked = false;
+        double ret = 0.0;
+        int32_t len = 0;
+        if (i < n) {
+            int32_t s = i;
+            bool closed = false;                                     // a repeated stream: in the table, not tracked
+            if (ids) {
+                const int32_t sid = ids[i];
+                if ((uint32_t)sid >= (uint32_t)n_streams) {
+                    s = -1;
+                } else if ((s_dup[sid >> 5] >> (sid & 31)) & 1u) {
+                    s = sid;
+                    closed = true;
+                } else {
+                    s = sid;
+                }
+            }
+            if (s >= 0 && closed) {                                  // (every row of it writes the same zeros)
+                ep.ep_return[s] = 0.0;
+                ep.ep_length[s] = 0;
+            } else if (s >= 0) {
+                tracked = true;
+                const int32_t had = ep.ep_length[s];
+                len = had + 1;
+                ret = (had == 0 && !count_first) ? 0.0 : (double)a.reward[i] + ep.ep_return[s];
+                end = (a.done[i] | a.truncated[i]) != 0;
+                ep.ep_return[s] = end ? 0.0 : ret;
+                ep.ep_length[s] = end ? 0 : len;
+            }
+        }
+        const unsigned long long ends = __ballot(end), trk = __ballot(tracked);
+        if (lane == 0) {
+            s_wcnt[wave] = __popcll(ends);
+            if (trk) atomicAdd(&s_tracked, __popcll(trk));
+        }
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int w = 0; w < n_waves; ++w) {
+            const int c = s_wcnt[w];
+            before += w < wave ? c : 0;
+            total += c;
+        }
+        if (end) {
+            const int pos = before + __popcll(ends & ((1ull << lane) - 1ull));
+            s_ret[pos] = ret;
+            s_len[pos] = len;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            for (int k = 0; k < total; ++k) {
+                const double r = s_ret[k];
+                st_ema = c_eps == 0 ? r : ema * st_ema + (1.0 - ema) * r;
+                st_sum += r;
+                st_last = r;
+                c_eps += 1;
+                c_len += s_len[k];
+            }
+        }
+        __syncthreads();                                             // the lists and counts are free for the next pass
+    }
+    if (tid == 0) {
+        ep.counts[0] = c_eps;
+        ep.counts[1] = c_len;
+        ep.counts[2] += s_tracked;
+        ep.stats[0] = st_ema;
+        ep.stats[1] = st_sum;
+        ep.stats[2] = st_last;
+    }
+}
+
+// TRACKED: the launch of prism_replay_ingest_tracked -- one more workgroup behind the row stores, a reward clip in them.
+template <bool TRACKED>
+static __device__ __forceinline__ void replay_ingest_body(const prism_replay_desc &rp, const IngestArgs &a,
+                                                          const prism_episode_desc &ep, const int tid, const int bd,
+                                                          const unsigned wg, const unsigned n_wgs) {
     __shared__ __attribute__((aligned(16))) char s_pool[TREE_WRITE_LDS_BYTES];
     __shared__ int s_serial;
-    const int tid = threadIdx.x, bd = blockDim.x;
     const int n = a.n;
     const int64_t cap = rp.capacity, first = a.first_slot;
+    const unsigned row_wgs = n_wgs - (TRACKED ? 2u : 1u);
 
-    if (blockIdx.x != 0) {
+    if constexpr (TRACKED) {
+        if (wg == n_wgs - 1) {
+            ingest_episode_role(a, ep, s_pool, tid, bd);
+            return;
+        }
+    }
+    if (wg != 0) {
         // ---- row store: INGEST_ROW_THREADS threads per row, blockDim / INGEST_ROW_THREADS rows per workgroup and trip
         const int O = rp.obs_elems;
         const int per_wg = bd / INGEST_ROW_THREADS, lane = tid % INGEST_ROW_THREADS;
-        const int64_t stride = (int64_t)(gridDim.x - 1) * per_wg;
-        for (int64_t i = (int64_t)(blockIdx.x - 1) * per_wg + tid / INGEST_ROW_THREADS; i < n; i += stride) {
+        const int64_t stride = (int64_t)(row_wgs)*per_wg;
+        for (int64_t i = (int64_t)(wg - 1) * per_wg + tid / INGEST_ROW_THREADS; i < n; i += stride) {
             const int64_t s = (first + i) % cap;
             const bool done = a.done[i] != 0, trunc = a.truncated[i] != 0;
             const bool has_next = trunc || !done;
@@ -92,7 +237,11 @@ static __global__ __launch_bounds__(1024) void replay_ingest_kernel(prism_replay
                 }
             }
             if (lane == 0) {
-                rp.reward[s] = a.reward[i];
+                float r = a.reward[i];
+                if constexpr (TRACKED) {                             // NaN and -0.0 fail both compares: stored as they are
+                    if (ep.reward_clip == PRISM_CLIP_CLAMP) r = r < -1.f ? -1.f : (r > 1.f ? 1.f : r);
+                }
+                rp.reward[s] = r;
                 rp.action[s] = a.action[i];
                 rp.flags[s] = (uint8_t)((done ? PRISM_FLAG_DONE : 0u) | (trunc ? PRISM_FLAG_TRUNC : 0u) |
                                         (has_next ? PRISM_FLAG_HAS_NEXT : 0u));
@@ -110,25 +259,8 @@ static __global__ __launch_bounds__(1024) void replay_ingest_kernel(prism_replay
     int64_t *tab = a.stream_tab;
     if (tid == 0) s_serial = 0;
     if (ids) {                                                       // (identity ids cannot repeat: no bitmap pass)
-        for (int w = tid; w < (n_streams + 31) >> 5; w += bd) {
-            s_seen[w] = 0u;
-            s_dup[w] = 0u;
-        }
-        __syncthreads();
-        bool flag = false;
-        for (int i = tid; i < n; i += bd) {
-            const int32_t sid = ids[i];
-            if ((uint32_t)sid >= (uint32_t)n_streams) {              // outside the table: stored unlinked, table untouched
-                flag = true;
-                continue;
-            }
-            const uint32_t bit = 1u << (sid & 31);
-            if (atomicOr(&s_seen[sid >> 5], bit) & bit) {
-                atomicOr(&s_dup[sid >> 5], bit);
-                flag = true;
-            }
-        }
-        if (flag) atomicOr(rp.status, PRISM_STATUS_INGEST_DUP_STREAM);
+        if (ingest_mark_streams(ids, n, n_streams, s_seen, s_dup, tid, bd))
+            atomicOr(rp.status, PRISM_STATUS_INGEST_DUP_STREAM);
     }
     __syncthreads();
     // stream of row i, or -1 when the row is stored unlinked (id outside the table / id repeated in this call)
@@ -217,6 +349,15 @@ static __global__ __launch_bounds__(1024) void replay_ingest_kernel(prism_replay
         const int32_t me = tid < cnt ? (int32_t)((first + base + tid) % cap) : 0;
         block_tree_write(rp, me, prio, cnt, s_pool);
     }
+}
+
+static __global__ __launch_bounds__(1024) void replay_ingest_kernel(prism_replay_desc rp, IngestArgs a) {
+    replay_ingest_body<false>(rp, a, prism_episode_desc{}, threadIdx.x, blockDim.x, blockIdx.x, gridDim.x);
+}
+
+static __global__ __launch_bounds__(1024) void replay_ingest_tracked_kernel(prism_replay_desc rp, IngestArgs a,
+                                                                            prism_episode_desc ep) {
+    replay_ingest_body<true>(rp, a, ep, threadIdx.x, blockDim.x, blockIdx.x, gridDim.x);
 }
 
 }  // namespace prism

@@ -149,7 +149,7 @@ class HipReplayBuffer:
     STAGE_ROWS = 1024
 
     def __init__(self, capacity, batch_size, device="cuda:0", frame_stack=1, n_step=3, gamma=0.99,
-                 use_per=True, alpha=0.5, beta=0.5, mass_rng="philox", seed=123, strict=False):
+                 use_per=True, alpha=0.5, beta=0.5, mass_rng="philox", seed=123, strict=False, reward_clipping_type=None):
         if frame_stack != 1:
             raise NotImplementedError("prism_amd replay: frame_stack_size > 1 is not implemented")
         if not str(device).startswith("cuda"):
@@ -182,6 +182,14 @@ class HipReplayBuffer:
         self._serial = 0
         self._stream_tab = None
         self._ing = None
+        # ... its reward clip, compared as collector_process_interface.py:136-139 compares it ("dopamine_clamp" clamps,
+        # "sign" divides by zero there, every other value -- DEFAULT_CONFIG's "dopamine_clip" included -- clips nothing),
+        # and the episode bookkeeping track_episodes() turns on: per-stream accumulators as long as the stream table
+        self.reward_clipping_type = reward_clipping_type
+        self._clip = N.CLIP_CLAMP if reward_clipping_type == "dopamine_clamp" else N.CLIP_NONE
+        self._ep = None            # dict(ema, count_first_step) while tracking
+        self._ep_return = self._ep_length = self._ep_words = self._ep_stats = self._ep_counts = None
+        self._ep_desc = self._ep_desc_ref = None
 
     # ------------------------------------------------------------------ allocation
     def _allocate(self, obs_shape):
@@ -345,7 +353,75 @@ class HipReplayBuffer:
             if t is not None:
                 new[:t.numel()].copy_(t)
             self._stream_tab = new
+            self._fit_episode_arrays()
         return self._stream_tab
+
+    # ------------------------------------------------------------------ reward clip + episode returns on the device
+    def _fit_episode_arrays(self):
+        """The per-stream accumulators, as long as the stream table: old entries kept, the rest zero."""
+        if self._ep is None:
+            return
+        size = self._stream_tab.numel()
+        if self._ep_return is None or self._ep_return.numel() != size:
+            ret = torch.zeros(size, dtype=torch.float64, device=self.device)
+            length = torch.zeros(size, dtype=torch.int32, device=self.device)
+            if self._ep_return is not None:
+                k = min(size, self._ep_return.numel())
+                ret[:k].copy_(self._ep_return[:k])
+                length[:k].copy_(self._ep_length[:k])
+            self._ep_return, self._ep_length = ret, length
+        self._bind_episode_desc()
+
+    def _bind_episode_desc(self):
+        """What prism_replay_ingest_tracked takes besides prism_replay_ingest's arguments (made anew when an array moves)."""
+        d = N.EpisodeDesc()
+        d.reward_clip = self._clip
+        if self._ep is not None:
+            d.count_first_step, d.ema = int(self._ep["count_first_step"]), self._ep["ema"]
+            d.ep_return, d.ep_length = self._ep_return.data_ptr(), self._ep_length.data_ptr()
+            d.stats, d.counts = self._ep_stats.data_ptr(), self._ep_counts.data_ptr()
+        self._ep_desc, self._ep_desc_ref = d, ctypes.byref(d)
+
+    def track_episodes(self, ema=0.9, count_first_step=False):
+        """Keep, on the device and inside extend_batch's one launch, what the reference's collector keeps per timestep
+        (collector_process_interface.py:129-133, experience_collector.py:113-118): every stream's episodic return over the
+        RAW rewards, in float64, and the training reward -- the EMA over the returns of finished episodes, folded in row
+        order.  ``count_first_step=False`` is the reference's rule: the first reward of an episode is not counted (a
+        one-step episode reports 0).  Rows that arrive through ``extend()`` are not tracked.  Read with ``episode_stats()``."""
+        ema, count_first_step = float(ema), bool(count_first_step)
+        if not (np.isfinite(ema) and 0.0 <= ema <= 1.0):
+            raise ValueError(f"track_episodes: ema = {ema} must lie in [0, 1]")
+        if self._ep is not None:
+            if self._ep != dict(ema=ema, count_first_step=count_first_step):
+                raise ValueError(f"track_episodes: already tracking with {self._ep}; the parameters cannot change")
+            return
+        N.lib()
+        with torch.cuda.device(self.device):
+            self._ep = dict(ema=ema, count_first_step=count_first_step)
+            # stats (float64 [4]) and counts (int64 [4]) side by side: episode_stats() is ONE device-to-host copy
+            self._ep_words = torch.zeros(8, dtype=torch.int64, device=self.device)
+            self._ep_stats, self._ep_counts = self._ep_words[:4].view(torch.float64), self._ep_words[4:]
+            self._stream_table(1)
+            self._fit_episode_arrays()
+
+    def episode_stats(self):
+        """The finished-episode statistics of the tracked rows so far (one small device-to-host copy: for report time).
+        ``training_reward`` is None until the first episode has ended, as the reference logs it."""
+        if self._ep is None:
+            raise RuntimeError("episode_stats: call track_episodes() first")
+        w = self._ep_words.cpu()
+        stats, counts = w[:4].view(torch.float64).tolist(), w[4:].tolist()
+        n = int(counts[0])
+        some = n > 0
+        return dict(episodes=n, training_reward=stats[0] if some else None, mean_return=stats[1] / n if some else None,
+                    mean_length=counts[1] / n if some else None, last_return=stats[2] if some else None,
+                    rows=int(counts[2]))
+
+    def _close_episodes(self):
+        """No stream has an open episode any more; what finished episodes have added up stays."""
+        if self._ep is not None:
+            self._ep_return.zero_()
+            self._ep_length.zero_()
 
     def reserve_streams(self, n_streams):
         """Size the stream table for ids 0 .. n_streams - 1 ahead of time.  Needed only with DEVICE-side ``stream_ids``:
@@ -404,7 +480,15 @@ class HipReplayBuffer:
         what ``reserve_streams()`` / earlier calls made it).  ``obs`` / ``next_obs`` may be float32 or bool / uint8 (widened
         on the device), both of the same class.
         A stream's row links back to the stream's previous row while the episode goes on (not done, not truncated);
-        ``next_obs`` is kept as the successor observation when truncated or not done.  Returns the first slot."""
+        ``next_obs`` is kept as the successor observation when truncated or not done.  Returns the first slot.
+
+        With ``reward_clipping_type="dopamine_clamp"`` the stored reward is clamped to [-1, 1] on the device (``extend()``
+        never clips: its caller, the reference's collector, already has); after ``track_episodes()`` the same launch keeps
+        the episode returns.  Neither changes anything else the call writes."""
+        if self.reward_clipping_type == "sign":
+            raise ValueError('extend_batch: reward_clipping_type "sign" is r / abs(r) in the reference '
+                             "(collector_process_interface.py:137), a division by zero at the first zero reward; it is not "
+                             "reproduced here")
         if not torch.is_tensor(obs):
             obs = np.asarray(obs)
         n = int(obs.shape[0])
@@ -434,9 +518,16 @@ class HipReplayBuffer:
             v["copies"][k][0].copy_(v["copies"][k][1], non_blocking=True)
         w, smp = self.buffer._writer, self.buffer._sampler
         first, serial = w._cursor, self._serial
-        self._call("prism_replay_ingest", n, first, serial, N.ptr(dev["obs"]), N.ptr(dev["next"]), kind,
+        # neither a clamp nor tracking: the entry point, arguments and launch of before; either: the same launch with one
+        # more workgroup (and the clip), the episode descriptor behind the arguments
+        name, tail = "prism_replay_ingest", ()
+        if self._ep is not None or self._clip != N.CLIP_NONE:
+            if self._ep_desc is None:
+                self._bind_episode_desc()
+            name, tail = "prism_replay_ingest_tracked", (self._ep_desc_ref,)
+        self._call(name, n, first, serial, N.ptr(dev["obs"]), N.ptr(dev["next"]), kind,
                    N.ptr(dev["reward"]), N.ptr(dev["action"]), N.ptr(dev["done"]), N.ptr(dev["trunc"]), N.ptr(dev["ids"]),
-                   N.ptr(tab), tab.numel(), smp._alpha, smp._eps, submit=self._ing if staged else None)
+                   N.ptr(tab), tab.numel(), smp._alpha, smp._eps, *tail, submit=self._ing if staged else None)
         # host mirrors, by arithmetic; the slots get ids from a private (negative) range: no Timestep id matches them
         cap = self.capacity
         own = np.arange(-2 - serial, -2 - serial - n, -1, dtype=np.int64)
@@ -545,13 +636,15 @@ class HipReplayBuffer:
         stored items (sampled, counted by len()), the rest only serve as link targets; the writer goes on at ``cursor``
         (default: behind the items).  ``leaves``: the items' tree leaves, [ns] or [ns, 2] as {sum, min} (default 1);
         ``back``: the inverse of ``link`` if the caller holds it (else derived); ``slot_ids``: the rows' Timestep ids
-        (default 0 .. n - 1).  No stream has an open row, no Timestep a pending predecessor, nothing is staged."""
+        (default 0 .. n - 1).  No stream has an open row (or an open tracked episode), no Timestep a pending predecessor, nothing
+        is staged."""
         ns = n if n_sampleable is None else int(n_sampleable)
         self._size = ns
         self.buffer._writer._cursor = ns % self.capacity if cursor is None else int(cursor)
         self._serial = self.buffer._writer._cursor       # serial % capacity == writer cursor
         if self._stream_tab is not None:
             self._stream_tab.fill_(-1)
+        self._close_episodes()
         self._slot_id[:] = -1
         self._slot_id[:n] = np.arange(n) if slot_ids is None else slot_ids
         self._pending.clear()
@@ -679,6 +772,10 @@ class HipReplayBuffer:
         if self.use_per:
             tc = self.tree_capacity
             part["leaves"] = self.tree[tc:tc + n].cpu()          # {sum, min} of every stored item; the nodes above follow
+        if self._ep is not None:                                 # (tracking off: the part is what it was without it)
+            part["episodes"] = dict(ep_return=self._ep_return.cpu(), ep_length=self._ep_length.cpu(),
+                                    stats=self._ep_stats.cpu(), counts=self._ep_counts.cpu(), ema=float(self._ep["ema"]),
+                                    count_first_step=bool(self._ep["count_first_step"]))
         return part
 
     def _restore_part(self, part, keep_streams=True):
@@ -705,6 +802,22 @@ class HipReplayBuffer:
             self._pending = {int(k): (int(s), int(i)) for k, s, i in part["pending"]}
         elif tab is not None:
             self._stream_tab.fill_(-1)
+        # ... and the episode bookkeeping: a snapshot that holds it turns tracking on as the run had it, one without it
+        # leaves tracking as this buffer has it (open episodes closed by the seal above)
+        eps = part.get("episodes")
+        if eps is not None:
+            self._ep = None
+            self.track_episodes(eps["ema"], eps["count_first_step"])
+            self._ep_return = eps["ep_return"].to(dev, torch.float64).contiguous()
+            self._ep_length = eps["ep_length"].to(dev, torch.int32).contiguous()
+            self._ep_stats.copy_(eps["stats"])
+            self._ep_counts.copy_(eps["counts"])
+            if not keep_streams:
+                self._close_episodes()
+        if self._ep is not None:
+            if self._stream_tab is None:
+                self._stream_table(1)
+            self._fit_episode_arrays()
 
     def save_state(self, path):
         """The live ring as an exact-resume snapshot (part ``replay``): every row, link and tree leaf, the host mirrors, the

@@ -12,4 +12,5 @@ def build_exp_buffer(config, capacity=None):
                            n_step=config.n_step_returns_length, gamma=config.gamma, use_per=config.use_per,
                            alpha=config.per_alpha, beta=config.per_beta_start,
                            mass_rng=getattr(config, "per_mass_rng", "philox"), seed=config.seed,
-                           strict=getattr(config, "per_strict", False))
+                           strict=getattr(config, "per_strict", False),
+                           reward_clipping_type=getattr(config, "reward_clipping_type", None))

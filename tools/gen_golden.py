@@ -17,6 +17,9 @@ What is captured:
                      (prism/experience/timestep_buffer.py:79-238) on hand-built Timestep chains.
   nstep_chain_*.npz  the same at n_step 1, 2, 5 and 15 and other discounts (NSTEP_CHAINS); written by
                      `python tools/gen_golden.py nstep_more`, which never touches nstep_chain.npz.
+  collector_bookkeeping.npz  reward clip, episodic reward and training-reward EMA of the reference's collector
+                     (collector_process_interface.py:129-139, experience_collector.py:113-118), per timestep;
+                     `python tools/gen_golden.py collector`.
 """
 import contextlib
 import io
@@ -461,10 +464,113 @@ def gen_checkpoint_rmsprop():
     print("ref_checkpoint_rmsprop:", sorted(os.listdir(os.path.join(ck, "agent"))))
 
 
+COLLECTOR_STREAMS, COLLECTOR_STEPS, COLLECTOR_EMA = 3, 60, 0.9
+
+
+def collector_script(seed=41):
+    """(reward float32 [streams][steps], done, truncated): fp32-representable rewards -- 0, +-1, their fp32 neighbours on
+    both sides, fractions and values large enough that a float32 sum would differ from the float64 one -- and an episode
+    pattern with a done on a stream's very first step, a truncation, done and truncated together, and one-step episodes."""
+    rng = np.random.default_rng(seed)
+    one = np.float32(1.0)
+    pool = np.array([0.0, 1.0, -1.0, np.nextafter(one, np.float32(0)), np.nextafter(one, np.float32(2)),
+                     np.nextafter(-one, np.float32(0)), np.nextafter(-one, np.float32(-2)), 0.5, -0.25, 3.0, -7.5, 1e6,
+                     -123456.0, 16777216.0, 1e-3, -0.1], np.float32)
+    S, T = COLLECTOR_STREAMS, COLLECTOR_STEPS
+    reward = pool[rng.integers(0, len(pool), (S, T))]
+    done = rng.random((S, T)) < 0.08
+    trunc = rng.random((S, T)) < 0.05
+    done[0, 0], trunc[0, 0] = True, False                      # done on a stream's first step
+    done[1, 5], trunc[1, 5] = False, True                      # a truncation
+    done[1, 11], trunc[1, 11] = True, True                     # both at once ...
+    done[1, 12], trunc[1, 12] = True, False                    # ... and a one-step episode right behind it
+    done[2, 30], trunc[2, 30] = True, False
+    done[2, 31], trunc[2, 31] = False, True                    # a one-step episode ended by a truncation
+    return reward, done, trunc
+
+
+def gen_collector_bookkeeping():
+    """What the reference's collector does to a timestep besides storing it: the live
+    CollectorProcessInterface.receive_env_step (reward clip, episodic_reward) behind a stub memory interface -- no
+    processes -- and ExperienceCollector.collect_timesteps around it for the training-reward EMA.  Three streams in
+    lockstep, so their timesteps reach the buffer interleaved; recorded per timestep, in the order they reach it."""
+    from multiprocessing_experience_collection import CollectorProcessInterface, EnvProcessMemoryInterface as E
+    from multiprocessing_experience_collection import ExperienceCollector
+
+    class StubMemory:
+        def __init__(self, reward, done, trunc):
+            self.reward, self.done, self.trunc, self.k, self.status = reward, done, trunc, 0, E.PROC_STATUS_WROTE_RESET_FLAG
+
+        def set_flag(self, idx, flag):
+            pass
+
+        def get_flag(self, idx):
+            return self.status if idx == E.PROC_STATUS_IDX else E.PROC_STATUS_NULL_FLAG
+
+        def read_reset_obs(self):
+            self.status = E.PROC_STATUS_WAITING_FOR_ACTION_FLAG
+            return np.zeros((1, 2), np.float32), 1
+
+        def read_step_data(self):
+            k = self.k
+            self.k += 1
+            data = self.reward[k:k + 1]                        # a float32 slice, as shared_memory_interface.py:138 reads it
+            o = np.full((1, 2), k, np.float32)
+            return o, [float(r) for r in data], bool(self.done[k]), bool(self.trunc[k]), o + 1, 1, 1
+
+        def write_action(self, action, idx):
+            pass
+
+        def send_actions(self):
+            pass
+
+    class Agent:
+        def forward(self, obs):
+            return torch.zeros(obs.shape[0], dtype=torch.long)
+
+    reward, done, trunc = collector_script()
+    S, T = reward.shape
+    out = dict(ema=COLLECTOR_EMA, n_streams=S, n_steps=T, raw_reward=reward, script_done=done, script_truncated=trunc)
+    for tag, clip in (("none", None), ("clamp", "dopamine_clamp")):
+        col = ExperienceCollector.__new__(ExperienceCollector)         # __init__ without its processes
+        col._device, col._timestep_id, col._inference_buffer_size = "cpu", 0, 1
+        col._training_reward_ema, col._training_reward = COLLECTOR_EMA, None
+        col._waiting_observations, col._waiting_timesteps, col._waiting_pids, col._action_pids = [], [], [], []
+        col._buffer_idx, col._random_agent = 0, None
+        col._running_processes = {e: CollectorProcessInterface(None, StubMemory(reward[e], done[e], trunc[e]), 1,
+                                                               reward_clipping_type=clip) for e in range(S)}
+        rows = []
+
+        class Buffer:
+            def extend(self, t):                                        # called right behind the EMA lines
+                rows.append((t, col._training_reward))
+
+        col.signal_processes_start_collecting(Agent())
+        assert col.collect_timesteps(S * T, Agent(), Buffer()) == S * T
+        ts = [r[0] for r in rows]
+        # the stream of a row: lockstep, one timestep per stream and round, in stream order
+        out[tag + "_stream"] = np.arange(S * T, dtype=np.int32) % S
+        stored = np.array([t.reward for t in ts], np.float64)
+        assert (stored.astype(np.float32).astype(np.float64) == stored).all()
+        out[tag + "_stored_reward"] = stored.astype(np.float32)
+        out[tag + "_episodic_reward"] = np.array([t.episodic_reward for t in ts], np.float64)
+        out[tag + "_done"] = np.array([t.done for t in ts], np.bool_)
+        out[tag + "_truncated"] = np.array([t.truncated for t in ts], np.bool_)
+        out[tag + "_training_valid"] = np.array([r[1] is not None for r in rows], np.bool_)
+        out[tag + "_training_reward"] = np.array([0.0 if r[1] is None else r[1] for r in rows], np.float64)
+        for e in range(S):                                              # the rows are the script, interleaved
+            assert (out[tag + "_done"][e::S] == done[e]).all() and (out[tag + "_truncated"][e::S] == trunc[e]).all()
+    np.savez_compressed(os.path.join(OUT, "collector_bookkeeping.npz"), **out)
+    ends = out["none_done"] | out["none_truncated"]
+    print("collector_bookkeeping:", S * T, "timesteps,", int(ends.sum()), "episode ends, clamped rewards:",
+          int((out["clamp_stored_reward"] != out["none_stored_reward"]).sum()))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     _import_reference()
-    which = sys.argv[1:] or (list(CASES) + ["nstep", "nstep_more", "config", "checkpoint", "checkpoint_rmsprop"])
+    which = sys.argv[1:] or (list(CASES) + ["nstep", "nstep_more", "config", "checkpoint", "checkpoint_rmsprop",
+                                   "collector"])
     for name in which:
         if name == "nstep":
             gen_nstep()
@@ -476,6 +582,8 @@ def main():
             gen_checkpoint_rmsprop()
         elif name == "config":
             gen_config_snapshot()
+        elif name == "collector":
+            gen_collector_bookkeeping()
         else:
             gen_update_case(name, *CASES[name])
 

@@ -3,12 +3,16 @@
     python tools/host_rate.py                      enqueue / total time of Learner.step() + a cProfile of it (c1)
     python tools/host_rate.py --mode ingest        one env step's ingestion for N streams: extend() x N + flush() against
                                                    extend_batch(), host float32 and uint8 arrays, and the whole loop
-                                                   collector -> Agent.forward -> ingest -> Learner.step() both ways
+                                                   collector -> Agent.forward -> ingest -> Learner.step() both ways; where
+                                                   the tree has it, extend_batch() once more with the reward clamp and
+                                                   the episode bookkeeping on (prism_replay_ingest_tracked)
     python tools/host_rate.py --mode snapshot      exact-resume snapshots at the c3 shapes (capacity 100 000, (10, 10, 4), binary
                                                    observations): Learner.save_state / load_state against the reference-format
                                                    HipReplayBuffer.save / load, median seconds of --rounds runs and bytes on disk
     --root DIR    import prism_amd from another checkout (a build of the parent commit: only the per-row path exists there)
     --out FILE    also write the ingest table there
+    --untracked-only   ingest mode without the tracked + clamp column: the process then does exactly what a parent-commit
+                       process does, for comparing the untracked call across trees
 """
 import argparse
 import contextlib
@@ -25,6 +29,7 @@ ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspat
 ap.add_argument("--out", default=None)
 ap.add_argument("--steps", type=int, default=300)
 ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--untracked-only", action="store_true")
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.root))
 import numpy as np
@@ -34,8 +39,8 @@ from prism_amd.learner import Learner
 from prism_amd.synthetic import fill_replay
 
 
-def make_learner(i):
-    cfg = baseline_config(i, device="cuda:0", log_to_wandb=False)
+def make_learner(i, **over):
+    cfg = baseline_config(i, device="cuda:0", log_to_wandb=False, **over)
     ln = Learner()
     with contextlib.redirect_stdout(io.StringIO()):
         ln.configure(cfg, obs_shape=(10, 10, 4), n_actions=6)
@@ -111,18 +116,24 @@ def timed(fn, steps):
 def ingest_mode():
     from prism_amd.experience import HipReplayBuffer
     has_batch = hasattr(HipReplayBuffer, "extend_batch")
+    has_track = hasattr(HipReplayBuffer, "track_episodes") and not args.untracked_only
     lines = [f"# ingestion of one env step of N streams, us per env step (median of {args.rounds} interleaved rounds of "
              f"{args.steps} steps): host enqueue / until the device queue is empty",
              f"# extend_batch in this tree: {'yes' if has_batch else 'no (per-row path only)'}",
-             "N     obs      extend()xN+flush()        extend_batch()           ratio (total)"]
+             f"# tracked + clamp column (track_episodes, reward_clipping_type = dopamine_clamp): {'yes' if has_track else 'no'}",
+             "N     obs      extend()xN+flush()        extend_batch()           ratio (total)" +
+             ("     tracked + clamp          tracked - untracked (total)" if has_track else "")]
     ids = iter(range(10 ** 12))
     for n in (1, 4, 16, 64, 256):
         for dtype in (np.float32, np.uint8):
             row_buf = HipReplayBuffer(100_000, 32, device="cuda:0", use_per=True)
             bat_buf = HipReplayBuffer(100_000, 32, device="cuda:0", use_per=True)
+            if has_track:
+                trk_buf = HipReplayBuffer(100_000, 32, device="cuda:0", use_per=True, reward_clipping_type="dopamine_clamp")
+                trk_buf.track_episodes(0.9)
             stub = VecStub(n, dtype)
-            res = {"row": [], "batch": []}
-            for rnd in range(args.rounds + 1):              # round 0 warms both paths up
+            res = {"row": [], "batch": [], "trk": []}
+            for rnd in range(args.rounds + 1):              # round 0 warms the paths up
                 ts, keep = stub.timesteps(args.steps, ids)
 
                 def per_row(k):
@@ -133,16 +144,24 @@ def ingest_mode():
                 if has_batch:
                     data = [stub.arrays() for _ in range(args.steps)]
                     b = timed(lambda k: bat_buf.extend_batch(*data[k]), args.steps)
+                if has_track:
+                    t = timed(lambda k: trk_buf.extend_batch(*data[k]), args.steps)
                 if rnd:
                     res["row"].append(r)
                     if has_batch:
                         res["batch"].append(b)
+                    if has_track:
+                        res["trk"].append(t)
             med = lambda v, j: statistics.median(x[j] for x in v)
             r0, r1 = med(res["row"], 0), med(res["row"], 1)
             line = f"{n:<5d} {np.dtype(dtype).name:<8s} {r0:9.1f} / {r1:9.1f}"
             if has_batch:
                 b0, b1 = med(res["batch"], 0), med(res["batch"], 1)
                 line += f"     {b0:9.1f} / {b1:9.1f}     {r1 / b1:6.2f}x"
+            if has_track:
+                t0, t1 = med(res["trk"], 0), med(res["trk"], 1)
+                spread = max(x[1] for x in res["batch"]) - min(x[1] for x in res["batch"])
+                line += f"     {t0:9.1f} / {t1:9.1f}     {t1 - b1:+6.1f} (untracked spread {spread:.1f})"
             lines.append(line)
             print(line, flush=True)
     # the whole loop: stub vector collector -> Agent.forward(obs[N]) -> ingestion -> Learner.step(), c3 (IQN + PER)
@@ -152,7 +171,12 @@ def ingest_mode():
         buf, agent = ln.experience_buffer, ln.agent
         fill_replay(buf, min(buf.capacity, 50_000), seed=0)
         stub = VecStub(n, np.float32)
-        res = {"row": [], "batch": []}
+        res = {"row": [], "batch": [], "trk": []}
+        if has_track:
+            ln_t = make_learner(2, reward_clipping_type="dopamine_clamp")
+            buf_t, agent_t = ln_t.experience_buffer, ln_t.agent
+            fill_replay(buf_t, min(buf_t.capacity, 50_000), seed=0)
+            buf_t.track_episodes(0.9)
         for rnd in range(3):
             ts, keep = stub.timesteps(args.steps, ids)
 
@@ -171,13 +195,23 @@ def ingest_mode():
                     buf.extend_batch(obs, nxt, agent.forward(obs), rew, done, trunc)   # actions stay on the device
                     ln.step(n)
                 b = timed(loop_batch, args.steps)
+            if has_track:
+                def loop_tracked(k):
+                    obs, nxt, _, rew, done, trunc = data[k]
+                    buf_t.extend_batch(obs, nxt, agent_t.forward(obs), rew, done, trunc)
+                    ln_t.step(n)
+                t = timed(loop_tracked, args.steps)
             if rnd:
                 res["row"].append(r)
                 if has_batch:
                     res["batch"].append(b)
+                if has_track:
+                    res["trk"].append(t)
         line = f"N = {n:<4d} per-row {statistics.median(x[1] for x in res['row']):9.1f}"
         if has_batch:
             line += f"     extend_batch {statistics.median(x[1] for x in res['batch']):9.1f}"
+        if has_track:
+            line += f"     tracked + clamp {statistics.median(x[1] for x in res['trk']):9.1f}"
         lines.append(line)
         print(line, flush=True)
     if args.out:
