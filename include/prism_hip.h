@@ -476,6 +476,35 @@ int prism_greedy_select(const float *z, const float *q, int32_t n, int32_t n_pad
                         int32_t n_heads, int64_t *out_action, float *out_mean, int64_t *out_action_host,
                         prism_stream_t stream);
 
+/* EGreedyActionSelector (prism/agents/action_selectors.py:24-45) with the coin tossed PER OBSERVATION: the reference (and
+ * the agent's default) tosses one coin for the whole call, which makes N lock-stepped environments explore together or not
+ * at all.  Row b of this launch is row row0 + b of a call of n_call rows (row0 = 0, n_call = n: the whole call in one
+ * launch; a call in pieces hands every piece its row0 and the whole call's n_call, and equals the call in one piece).
+ *   greedy = prism_greedy_select's action on the same buffers, bit for bit (one device routine); out_mean as there
+ *   s0     = steps0 when steps_word is NULL, else steps0 + *steps_word: the rows seen before this call, the selector's
+ *            epsilon.current_step
+ *   eps    = ONE value per call, LinearAnneal.get_value() after epsilon.update(n_call), i.e. at s = s0 + n_call
+ *            (prism/util/annealing_strategies.py:22-33), float64 in the reference's operation order: eps_stop if
+ *            anneal_steps == 0 || s >= anneal_steps, else f = min(1, s / anneal_steps), eps_start * (1 - f) + eps_stop * f
+ *   r      = Philox4x32-10(seed, s0 + row0 + b, "EGRD" = 0x45475244): a stream key apart from "TAU0" + sid, "PERM", "UNIF"
+ *            and "IDSA".  Every row seen has a counter of its own: the ranges [s0, s0 + n_call) of successive calls touch
+ *            and never overlap.
+ *   u      = u_in[row0 + b] (float64, parity input) when u_in is given, else the 53-bit uniform of r[0], r[1]
+ *   action = (uint32)(((uint64)r[2] * n_actions) >> 32) if u < eps (eps = 1 always explores, eps = 0 never), else greedy
+ * steps_word (optional, device): a uint64 count of rows seen that the call ADVANCES by n_call, so that a call captured into a
+ * hipGraph draws fresh at every replay.  Needs the whole call in one launch (row0 == 0, n_call == n < 2^20) and counts
+ * below 2^44: while the launch runs, bits 44 and up hold one ticket per workgroup -- a workgroup's one atomic add is both its
+ * read of the count and its ticket, and the holder of the last ticket takes the tickets off and adds n_call.  No workgroup
+ * reads the word after it has advanced, and its value after the call does not depend on their order.  Calls on one word
+ * must follow each other on the device (one stream, or one hipGraph after another).
+ * out_epsilon (optional) [1] float64; out_explored (optional) [n] 1 / 0; out_action [n]; out_action_host as for
+ * prism_ids_select. */
+int prism_egreedy_select(const float *z, const float *q, int32_t n, int32_t n_pad, int32_t n_tau, int32_t n_actions,
+                         int32_t n_heads, double eps_start, double eps_stop, int64_t anneal_steps, uint64_t seed,
+                         uint64_t steps0, int32_t row0, int32_t n_call, uint64_t *steps_word, const double *u_in,
+                         float *out_mean, double *out_epsilon, uint8_t *out_explored, int64_t *out_action,
+                         int64_t *out_action_host, prism_stream_t stream);
+
 /* Agent.sync_target_model (agent.py:149-152): target := online (device-to-device copy). */
 int prism_sync_target(float *target_params, const float *params, int64_t n_params,
                       prism_stream_t stream);

@@ -391,6 +391,11 @@ class HipAgent:
         # Agent.forward replayed from one hipGraph per (number of observations, selector): H2D of the observations, embed,
         # forward tiles, selector kernel, D2H of the actions (config.act_graph = False: the eager launches)
         self.act_graph = bool(getattr(config, "act_graph", True))
+        # epsilon-greedy with one coin per observation, tossed on the device (prism_egreedy_select), where the default tosses
+        # the reference's one host coin per call.  The position of that stream is the selector's epsilon.current_step; the
+        # device keeps a copy (_eg_word) that captured calls advance, _eg_dev_steps is what the host knows it to hold
+        self.e_greedy_per_env = bool(getattr(config, "e_greedy_per_env", False))
+        self._eg_word, self._eg_dev_steps = None, None
         self._param_epoch, self._act_packed_at = 0, None
         # (the reference's async evaluator loads weights straight into agent.model, async_agent_evaluator.py:29)
         self.model.register_load_state_dict_post_hook(lambda module, incompatible: self._params_replaced())
@@ -447,6 +452,7 @@ class HipAgent:
         self.rng_counters = torch.zeros(3, dtype=torch.int64, device=dev)     # {PER draws, tau draws, acting draws}
         self._rng_ptr = self.rng_counters.data_ptr()
         self._act_graphs, self._act_ptrs, self._act_dev_draws, self._act_packed_at = {}, {}, 0, None
+        self._eg_word, self._eg_dev_steps = torch.zeros(1, dtype=torch.int64, device=dev), None
         # observations one prism_act_forward takes: what the workspace holds, in whole 16-row tiles for two-layer Q heads
         self._act_cap = (B // 16) * 16 if self.dims.n_heads > 0 and self.dims.head_layers == 2 else B
         self._desc, self._B = d, B
@@ -703,11 +709,18 @@ class HipAgent:
     def _selector_key(self, sel):
         """The selector's native kernel and constants: ``("ids", lmbda, epsilon, rho_lower_bound, unsquish id)``,
         ``("ids_sampled", ...)`` with the same constants for ``ids_use_random_samples`` (the action is a Philox draw of the
-        agent's seed: only where the quantile draws are, ``tau_rng == "philox"``), ``("greedy",)``, or None for what has
+        agent's seed: only where the quantile draws are, ``tau_rng == "philox"``), ``("greedy",)``,
+        ``("egreedy", start, stop, max_steps)`` for epsilon-greedy per observation (``e_greedy_per_env``; ``forward`` hands
+        the selector over only in that mode, else its ``greedy`` member), or None for what has
         none (sampled IDS in parity mode -- ``torch.multinomial`` on torch's generator --, an unsquish function the kernel
         does not know, IDS on a model without both estimate arrays, any other selector): the selector's torch code on the
         eager estimates."""
-        from prism_amd.agents.action_selectors import GreedyActionSelector, IDSActionSelector
+        from prism_amd.agents.action_selectors import EGreedyActionSelector, GreedyActionSelector, IDSActionSelector
+        if type(sel) is EGreedyActionSelector and self.e_greedy_per_env:
+            e = sel.epsilon
+            if int(e.max_steps) != e.max_steps or e.max_steps < 0 or e.current_step < 0:
+                raise ValueError("e_greedy_per_env counts rows: the anneal needs a whole, non-negative number of steps")
+            return ("egreedy", float(e.start), float(e.stop), int(e.max_steps))
         if type(sel) is IDSActionSelector:
             from prism_amd.agents.squish_functions import unsquish_id
             usq = unsquish_id(sel.unsquish_function)
@@ -717,13 +730,23 @@ class HipAgent:
                     float(sel.ids_rho_lower_bound), usq)
         return ("greedy",) if type(sel) is GreedyActionSelector else None
 
-    def _select_launch(self, skey, z, qb, n, n_pad, T, act, host_act, scores, draw_offset=0, rng_counters=None):
+    def _select_launch(self, skey, z, qb, n, n_pad, T, act, host_act, scores, draw_offset=0, rng_counters=None,
+                       eg_rows=None, eg_word=None):
         """The selector kernel of ``skey`` (_selector_key) on the current stream: actions to ``act`` (device) and, where
         given, to ``host_act`` (pinned host); ``scores``: the ``(n, A)`` information ratios IDS leaves behind.  Sampled
         IDS draws observation b at Philox counter c0 + b, c0 the acting count at the START of this call's forward: the
         eager call hands it over (``draw_offset``), the graph path binds ``rng_counters``, whose word [2] the forward in
-        front of this launch has advanced by n * T (the kernel takes that off again)."""
+        front of this launch has advanced by n * T (the kernel takes that off again).  Epsilon-greedy per observation
+        draws row b at counter s0 + row0 + b, s0 the rows seen before this call: the eager call hands over
+        ``eg_rows = (s0, row0, rows of the whole call)``, the graph path binds ``eg_word``, the device's own count, which
+        the launch advances."""
         L, dm = N.lib(), self.dims
+        if skey[0] == "egreedy":
+            s0, row0, n_call = eg_rows if eg_word is None else (0, 0, n)
+            N.check(L.prism_egreedy_select(N.ptr(z), N.ptr(qb), n, n_pad, T, dm.n_actions, dm.n_heads, skey[1], skey[2], skey[3],
+                                           self.seed, s0, row0, n_call, eg_word, None, None, None, None, N.ptr(act),
+                                           N.ptr(host_act), N.current_stream_handle()), "prism_egreedy_select")
+            return
         if skey[0] == "ids_sampled":
             N.check(L.prism_ids_sample_select(N.ptr(z), N.ptr(qb), n, n_pad, T, dm.n_actions, dm.n_heads, skey[1], skey[2],
                                               skey[3], skey[4], None, self.seed, draw_offset, rng_counters, N.ptr(scores), None,
@@ -780,7 +803,10 @@ class HipAgent:
         """Agent.forward (agent.py:31-41).  Information-directed sampling, deterministic (``prism_ids_select``) and sampled
         (``ids_use_random_samples``: ``prism_ids_sample_select``, the action a Philox draw of the agent's seed on its own
         stream key), greedy and epsilon-greedy selection (``prism_greedy_select``; the coin and the random actions come from
-        the selector's host generator exactly as in action_selectors.py:35-45) run natively on the estimate buffers.  Only in
+        the selector's host generator exactly as in action_selectors.py:35-45; with ``config.e_greedy_per_env`` every
+        observation has its own coin and random action, Philox draws inside ``prism_egreedy_select``, the selector's
+        ``epsilon.current_step`` the position of that stream and its ``rng`` left alone) run natively on the estimate
+        buffers.  Only in
         parity mode (``tau_rng == "torch"``) sampled IDS runs the selector's torch code: ``torch.multinomial`` on torch's
         generator, as the reference draws."""
         from prism_amd.agents.action_selectors import EGreedyActionSelector
@@ -788,7 +814,8 @@ class HipAgent:
         sel = self.eval_action_selector if self._is_eval else self.action_selector
         obs_in = obs
         n, A = int(np.shape(obs)[0]), self.dims.n_actions
-        if type(sel) is EGreedyActionSelector:
+        per_env = self.e_greedy_per_env and type(sel) is EGreedyActionSelector
+        if type(sel) is EGreedyActionSelector and not per_env:
             if sel.rng.uniform(0, 1) < sel.epsilon.update(n):       # one coin for the whole call (action_selectors.py:38-41)
                 # the reference has ALREADY run the model by the time it tosses the coin (agent.py:33 -> :36): the forward's
                 # quantile samples are drawn whether or not the estimates are used.  The estimates are not needed here, the
@@ -810,8 +837,12 @@ class HipAgent:
                 return out
         obs = _as_tensor(obs, self.device).contiguous()
         if n > cap:          # in pieces: every piece is selected from its own estimate buffers
-            return torch.cat([self._forward_piece(obs[i:i + cap], sel) for i in range(0, n, cap)])
-        return self._forward_piece(obs, sel)
+            out = torch.cat([self._forward_piece(obs[i:i + cap], sel, i, n) for i in range(0, n, cap)])
+        else:
+            out = self._forward_piece(obs, sel, 0, n)
+        if per_env:
+            sel.epsilon.current_step += n          # (the device's count is behind now: the next graph call seeds it)
+        return out
 
     def _forward_graph(self, obs_in, n, sel):
         """One ``Agent.forward`` as ONE hipGraph launch: [observations host -> device] -> prism_act_forward -> selector kernel
@@ -860,6 +891,10 @@ class HipAgent:
         if self._act_dev_draws != self._act_draws:          # eager calls / an explore branch moved the host count on
             self.rng_counters[2] = self._act_draws
             self._act_dev_draws = self._act_draws
+        if skey[0] == "egreedy" and self._eg_dev_steps != sel.epsilon.current_step:
+            # the first call, an eager call, a loaded checkpoint: the selector's count is the position, the device follows
+            self._eg_word[0] = int(sel.epsilon.current_step)
+            self._eg_dev_steps = sel.epsilon.current_step
         k = st["calls"] & 3
         if on_host:
             if st["calls"] >= 4:
@@ -878,7 +913,8 @@ class HipAgent:
                              rng_counters=self.rng_counters.data_ptr(),
                              act_flags=N.ACT_WEIGHTS_CURRENT if current else 0)
             self._select_launch(skey, st["z"], st["qb"], n, st["n_pad"], st["T"], st["act"][slot], st["pin_out"][slot],
-                                st["scores"], rng_counters=self.rng_counters.data_ptr())
+                                st["scores"], rng_counters=self.rng_counters.data_ptr(),
+                                eg_word=self._eg_word.data_ptr())
 
         with torch.cuda.device(self.device):
             if st["g"] is None and st["calls"] == 0:
@@ -900,11 +936,15 @@ class HipAgent:
         st["calls"] += 1
         self._act_draws += st["T"] * n
         self._act_dev_draws = self._act_draws
+        if skey[0] == "egreedy":          # (by arithmetic: the launch has added n to the device's count)
+            sel.epsilon.current_step += n
+            self._eg_dev_steps = sel.epsilon.current_step
         self._act_raw = (st["z"], st["qb"], n, st["n_pad"], st["T"])
         self._act_scores = st["scores"]
         return _Actions.wrap(st["act"][k], st["pin_out"][k], st["ev"][k])
 
-    def _forward_piece(self, obs, sel):
+    def _forward_piece(self, obs, sel, row0, n_call):
+        """Rows ``row0 ..`` of an eager call of ``n_call`` observations: estimates, then the selector on them."""
         self._act_raw = None
         c0 = self._act_draws          # (the acting count this piece's forward starts from: the sampled selector's counter)
         q, dist = self.act_estimates(obs)
@@ -915,7 +955,8 @@ class HipAgent:
         action = torch.empty(n, dtype=torch.int64, device=self.device)
         scores = torch.empty((n, self.dims.n_actions), device=self.device) if skey[0] in ("ids", "ids_sampled") else None
         with torch.cuda.device(self.device):
-            self._select_launch(skey, z, qb, n, n_pad, T, action, None, scores, draw_offset=c0)
+            self._select_launch(skey, z, qb, n, n_pad, T, action, None, scores, draw_offset=c0,
+                                eg_rows=(int(sel.epsilon.current_step), row0, n_call) if skey[0] == "egreedy" else None)
         if scores is not None:
             self._act_scores = scores
         return action
@@ -1024,6 +1065,7 @@ class HipAgent:
         with open(os.path.join(path, "state.pkl"), "rb") as f:
             state = ref_pickle.load(f)         # reference-written files name prism.agents.action_selectors.*
         self._graphs = {}                      # captured graphs bake the hyper-parameters restored here
+        self._eg_dev_steps = None              # (the selector loaded below carries its own epsilon.current_step)
         self._param_epoch += 1
         self._target_changed()
         self.action_selector = state["action_selector"]
@@ -1057,6 +1099,7 @@ class HipAgent:
         self._draw_offset, self._fused_tau = int(part["tau_draws"]), 0
         # the device's acting word is seeded from the host count by the next graph call (_forward_graph)
         self._act_draws, self._act_dev_draws = int(part["act_draws"]), 0
+        self._eg_dev_steps = None          # likewise the rows epsilon-greedy per observation has seen (state.pkl has them)
         self._act_raw = None
         self._graphs, self._act_graphs, self._act_ptrs, self._act_packed_at = {}, {}, {}, None
         if self._B is not None:

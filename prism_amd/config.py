@@ -14,6 +14,9 @@ constructing unchanged); they are read with ``getattr(config, name, default)``:
                       seeded reference run; costs one D2H sync per sample)
     tau_rng           "philox" (in-kernel, default)  | "torch" (torch.rand on the model device)
     hip_graph         bool, capture Learner.step() into a hipGraph (default True on GPU)
+    e_greedy_per_env  bool, epsilon-greedy tosses one coin per observation, on the device (Philox,
+                      inside the acting hipGraph), instead of the reference's one host coin per
+                      Agent.forward call (default False); for vector collectors under use_e_greedy
 """
 import dataclasses
 import json

@@ -93,7 +93,51 @@ __device__ __forceinline__ float ids_score_wave(const IdsArgs &k, const float *z
     return score;
 }
 
-#ifndef PRISM_ACT_NO_KERNELS          // (act_sample.hip takes the routines above alone: the kernels below live in learner.hip)
+// Greedy arg-max of the mean action values (GreedyActionSelector, /root/reference/prism/agents/action_selectors.py:70-83:
+// q_estimates.mean(dim=-1).argmax(dim=-1)): the ensemble mean over the heads when the model has Q heads, else the mean of
+// the T quantile samples (composite_model.py:66-68: q_estimates = return_distribution.mean(dim=0)).  One wave per
+// observation, lane = action, sums in index order, first maximum wins (torch.argmax).
+struct GreedyArgs {
+    const float *z;      // [n][T][A] or NULL
+    const float *q;      // [heads][n_pad][A] or NULL
+    int n, n_pad, T, A, heads;
+    int64_t *action;     // [n]
+    float *mean;         // optional [n][A]
+    int64_t *action2;    // optional second copy of the actions (pinned host memory)
+    int stage;           // as IdsArgs.stage
+};
+
+// The greedy action of observation b on wave 0 of the workgroup (every lane of the wave calls it; zb: what act_stage
+// returned, unused with k.q), wave-uniform; the means go to k.mean.  The one statement of the arg-max: greedy_select_kernel
+// stores it, egreedy_select_kernel (act_egreedy.hip) stores it for the rows that do not explore.
+__device__ __forceinline__ int greedy_argmax_wave(const GreedyArgs &k, const float *zb, int b, int lane) {
+    const int A = k.A;
+    float m = -INFINITY;
+    if (lane < A) {
+        float s = 0.f;
+        if (k.q) {
+            for (int h = 0; h < k.heads; ++h) s += k.q[((int64_t)h * k.n_pad + b) * A + lane];
+            m = s / (float)k.heads;
+        } else {
+#pragma unroll 8
+            for (int t = 0; t < k.T; ++t) s += zb[t * A + lane];            // (index order, as before: same bits)
+            m = s / (float)k.T;
+        }
+        if (k.mean) k.mean[(int64_t)b * A + lane] = m;
+    }
+    int best = 0;
+    float bv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(m), 0));
+    for (int a = 1; a < A; ++a) {
+        const float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(m), a));
+        if (v > bv) {
+            bv = v;
+            best = a;
+        }
+    }
+    return best;
+}
+
+#ifndef PRISM_ACT_NO_KERNELS          // (act_sample.hip and act_egreedy.hip take the routines above alone: the kernels below live in learner.hip)
 __global__ __launch_bounds__(ACT_THREADS) void ids_score_kernel(IdsArgs k) {
     extern __shared__ __attribute__((aligned(16))) float s_act[];
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -117,47 +161,12 @@ __global__ __launch_bounds__(ACT_THREADS) void ids_score_kernel(IdsArgs k) {
     }
 }
 
-// Greedy arg-max of the mean action values (GreedyActionSelector, /root/reference/prism/agents/action_selectors.py:70-83:
-// q_estimates.mean(dim=-1).argmax(dim=-1)): the ensemble mean over the heads when the model has Q heads, else the mean of
-// the T quantile samples (composite_model.py:66-68: q_estimates = return_distribution.mean(dim=0)).  One wave per
-// observation, lane = action, sums in index order, first maximum wins (torch.argmax).
-struct GreedyArgs {
-    const float *z;      // [n][T][A] or NULL
-    const float *q;      // [heads][n_pad][A] or NULL
-    int n, n_pad, T, A, heads;
-    int64_t *action;     // [n]
-    float *mean;         // optional [n][A]
-    int64_t *action2;    // optional second copy of the actions (pinned host memory)
-    int stage;           // as IdsArgs.stage
-};
-
 __global__ __launch_bounds__(ACT_THREADS) void greedy_select_kernel(GreedyArgs k) {
     extern __shared__ __attribute__((aligned(16))) float s_act[];
-    const int b = blockIdx.x, lane = threadIdx.x, A = k.A;
-    const float *zb = k.q ? nullptr : act_stage(k.z, b, k.T, A, s_act, k.stage != 0);
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const float *zb = k.q ? nullptr : act_stage(k.z, b, k.T, k.A, s_act, k.stage != 0);
     if (lane >= 64) return;
-    float m = -INFINITY;
-    if (lane < A) {
-        float s = 0.f;
-        if (k.q) {
-            for (int h = 0; h < k.heads; ++h) s += k.q[((int64_t)h * k.n_pad + b) * A + lane];
-            m = s / (float)k.heads;
-        } else {
-#pragma unroll 8
-            for (int t = 0; t < k.T; ++t) s += zb[t * A + lane];            // (index order, as before: same bits)
-            m = s / (float)k.T;
-        }
-        if (k.mean) k.mean[(int64_t)b * A + lane] = m;
-    }
-    int best = 0;
-    float bv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(m), 0));
-    for (int a = 1; a < A; ++a) {
-        const float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(m), a));
-        if (v > bv) {
-            bv = v;
-            best = a;
-        }
-    }
+    const int best = greedy_argmax_wave(k, zb, b, lane);
     if (lane == 0) {
         k.action[b] = best;
         if (k.action2) k.action2[b] = best;

@@ -4,6 +4,9 @@ host -> actions on the host, per call, for the hipGraph form (default) and the e
   device in     the reference collector's pattern: one persistent device inference buffer in, .cpu().numpy() out
                 (multiprocessing_experience_collection/experience_collector.py:77-78,127)
 --rows ids      only the ten-head IDS configuration, deterministic and sampled (ids_use_random_samples), hipGraph form
+--rows egreedy  the DQN configuration configs[1], hipGraph form: the greedy selector (use_e_greedy off) before and after the
+                per-observation epsilon-greedy mode (e_greedy_per_env; epsilon pinned to 0 and to 1: every row greedy, every
+                row a random action) -- the two greedy rows give the run-to-run spread of one visit
 --sizes 1,16    observation counts;  --reps 300   calls per median;  --tag NAME   prefix of every printed row (two trees
                 measured alternately in one visit)"""
 import argparse, contextlib, io, json, os, sys, time
@@ -45,7 +48,7 @@ def measure(cfg_i, graph, reps=400, sizes=(1, 4, 16), **over):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", default="all", choices=["all", "ids"])
+    ap.add_argument("--rows", default="all", choices=["all", "ids", "egreedy"])
     ap.add_argument("--sizes", default="1,4,16")
     ap.add_argument("--reps", type=int, default=400)
     ap.add_argument("--tag", default="")
@@ -56,11 +59,19 @@ if __name__ == "__main__":
             (3, "IDS + IQN, ten heads, sampled", sampled)]
     if args.rows == "ids":
         rows = rows[1:]
+    if args.rows == "egreedy":
+        greedy = dict(use_e_greedy=False)
+        per_env = dict(e_greedy_per_env=True, e_greedy_decay_timesteps=0)
+        rows = [(1, "DQN, greedy", greedy),
+                (1, "DQN, e-greedy per env, eps 0", dict(per_env, e_greedy_final_epsilon=0.0)),
+                (1, "DQN, e-greedy per env, eps 1", dict(per_env, e_greedy_final_epsilon=1.0)),
+                (1, "DQN, greedy (again)", greedy)]
     res = {}
     for cfg_i, name, over in rows:
-        for graph in ((True,) if args.rows == "ids" else (True, False)):
+        for graph in ((True,) if args.rows != "all" else (True, False)):
             r = measure(cfg_i, graph, args.reps, sizes, **over)
-            res[f"{args.tag}configs[{cfg_i}]{' sampled' if over else ''} {'graph' if graph else 'eager'}"] = r
+            what = f" {name}" if args.rows == "egreedy" else " sampled" if over else ""
+            res[f"{args.tag}configs[{cfg_i}]{what} {'graph' if graph else 'eager'}"] = r
             for k, v in r.items():
                 print(f"{args.tag}{name:36s} {'hipGraph' if graph else 'eager   '} {k:18s}: {v:7.1f} us per Agent.forward (host -> actions on the host)",
                       flush=True)
