@@ -160,6 +160,40 @@ int prism_replay_ingest_tracked(const prism_replay_desc *rp, int32_t n, int64_t 
                                 const int32_t *stream_ids, int64_t *stream_tab, int32_t n_streams,
                                 float alpha, float eps, const prism_episode_desc *ep, prism_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Evaluation bookkeeping -- SyncAgentEvaluator.evaluate_agent (prism/evals/sync_agent_evaluator.py:37-59) for n_streams
+ * environments stepped in lockstep: episode returns, the list of finished episodes and the loop's own stopping rule, on
+ * the device in one launch per environment step, without a host read.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct prism_eval_desc {
+    int32_t n_streams;      /* 1 .. 65536 */
+    int32_t log_capacity;   /* >= 0: finished episodes kept one by one */
+    int64_t budget;         /* evaluation_timestep_horizon, >= 0 */
+    double  *ep_return;     /* [n_streams] return of the open episode */
+    int32_t *ep_length;     /* [n_streams] its steps so far */
+    double  *log_return;    /* [log_capacity] finished returns, in (call, row) order */
+    int32_t *log_length;    /* [log_capacity] */
+    double  *stats;         /* [4] sum | sum of squares | min | max of finished returns */
+    int64_t *counts;        /* [4] episodes | sum of their lengths | rows taken | calls taken */
+    int64_t *host_counts;   /* optional, pinned host [2]: counts[0], counts[2] after this call */
+} prism_eval_desc;
+
+/* One environment step of an evaluation: row i is stream i, 1 <= n <= n_streams; reward [n] fp32, done / truncated [n].
+ * The call first reads closed = counts[2] >= budget && counts[0] >= 1 -- the reference's loop condition
+ * `collected_ts < n_ts or len(ep_rews) == 0` (sync_agent_evaluator.py:42), evaluated before the step.  A closed
+ * evaluation takes nothing: every array stays bit for bit as it was and only host_counts is rewritten, so a host that
+ * runs ahead of the device cannot spoil the result.  Otherwise, per row, in float64 on the widened reward:
+ * len = ep_length[i] + 1; ret = reward[i] + ep_return[i] (an episode's first reward counts: the evaluator's rule, not
+ * the collector's); done | truncated: an episode end (ret, len), both accumulators of i return to 0; else they are
+ * stored back.  Ends are folded in row order: if counts[0] < log_capacity the pair goes to log slot counts[0];
+ * stats[0] += ret; stats[1] += ret * ret (the product and the sum each rounded); stats[2] / stats[3] = min / max by
+ * plain < / > compares, the first episode setting both; counts[0] += 1; counts[1] += len.  After the rows
+ * counts[2] += n and counts[3] += 1.  The whole call is taken or none of it: the rule is not read again between rows.
+ * host_counts, when given, receives counts[0] and counts[2] as the call leaves them (plain stores, visible to the host
+ * once the launch has ended).  log_return / log_length may be NULL only with log_capacity == 0. */
+int prism_eval_track(const prism_eval_desc *ev, int32_t n, const float *reward, const uint8_t *done,
+                     const uint8_t *truncated, prism_stream_t stream);
+
 /* PrioritizedSampler.sample (called at timestep_buffer.py:37): p_sum/p_min = query(0,size);
  * index[i] = min(scan_lower_bound(mass[i]), size-1); weight[i] = (leaf/p_min) ** -beta.
  * mass == NULL: masses are drawn on the device, U(0,p_sum) in float64 narrowed to fp32, from

@@ -45,6 +45,11 @@ class EpisodeDesc(ctypes.Structure):
                 ("ep_length", c_vp), ("stats", c_vp), ("counts", c_vp)]
 
 
+class EvalDesc(ctypes.Structure):
+    _fields_ = [("n_streams", c_i32), ("log_capacity", c_i32), ("budget", c_i64), ("ep_return", c_vp), ("ep_length", c_vp),
+                ("log_return", c_vp), ("log_length", c_vp), ("stats", c_vp), ("counts", c_vp), ("host_counts", c_vp)]
+
+
 class ModelDims(ctypes.Structure):
     _fields_ = [(n, c_i32) for n in (
         "in_channels", "n_actions", "embed_dim", "use_iqn", "n_basis", "iqn_layers", "iqn_width", "n_tau",
@@ -109,6 +114,7 @@ SIGNATURES = {
                                             c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_vp]),
     "prism_replay_ingest_tracked": (ctypes.c_int, [_P(ReplayDesc), c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
                                                     c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, _P(EpisodeDesc), c_vp]),
+    "prism_eval_track": (ctypes.c_int, [_P(EvalDesc), c_i32, c_vp, c_vp, c_vp, c_vp]),
     "prism_per_sample": (ctypes.c_int, [_P(ReplayDesc), c_i64, c_i32, c_vp, c_u64, c_u64, c_f32, c_vp, c_vp,
                                          c_vp]),
     "prism_uniform_sample": (ctypes.c_int, [c_i64, c_i32, c_u64, c_u64, c_vp, c_vp]),

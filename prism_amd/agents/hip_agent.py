@@ -329,6 +329,13 @@ class _Actions(torch.Tensor):
         return self.cpu().item()
 
 
+class _DrawCount:
+    """What ``HipAgent.acting_stream`` hands back: ``count``, the acting draw count its block reached."""
+
+    def __init__(self, count):
+        self.count = count
+
+
 class HipAgent:
     def __init__(self, model, action_selector, eval_action_selector, target_model, config, in_channels,
                  n_actions, process_group=None):
@@ -678,6 +685,25 @@ class HipAgent:
     def _act_T(self):
         """Quantile samples per action of one acting forward (composite_model.py:57): its draws are ``T * n``."""
         return int(self.model.distribution_model.n_quantile_samples_per_action) if self.dims.use_iqn else 0
+
+    @contextlib.contextmanager
+    def acting_stream(self, offset):
+        """The calls inside draw their acting samples (quantile draws, the sampled selector's draw: key ``TAU_KEY + TAU_ACT``
+        and ``"IDSA"``) at draw count ``offset`` onwards instead of the agent's own; afterwards the count is what it was, so
+        the calls that follow draw what they would have drawn without the block (the device's word follows at the next
+        graph call, as after any eager call: ``_forward_graph``).  Hands back an object whose ``count`` is the count the
+        block reached -- where a later block goes on.  An evaluation runs in one (prism_amd/evals.py)."""
+        offset = int(offset)
+        if not 0 <= offset < 2 ** 63:
+            raise ValueError("acting_stream: the offset is a draw count in [0, 2^63)")
+        reached = _DrawCount(offset)
+        keep = self._act_draws
+        self._act_draws = offset
+        try:
+            yield reached
+        finally:
+            reached.count = self._act_draws
+            self._act_draws = keep
 
     def _act_buffers(self, n):
         """``(z, qb, n_pad, T)``: the estimate arrays ``prism_act_forward`` fills for ``n`` observations and the selector

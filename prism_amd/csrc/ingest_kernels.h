@@ -65,6 +65,25 @@ static __device__ __forceinline__ bool ingest_mark_streams(const int32_t *ids, i
     return flag;
 }
 
+// The row-order compaction of one pass, shared with the evaluation tracker (eval_kernels.h): `flagged` = __ballot(flag)
+// of the caller's wave.  Every thread of the workgroup calls it; it holds ONE workgroup barrier (what lane 0 of a wave
+// wrote in front of the call is visible behind it).  Returns the position of a flagged row among the pass's flagged
+// rows in row order (only meaningful where flag is set) and their number in `total`.  s_wcnt: n_waves ints, free again
+// after the caller's next barrier.
+static __device__ __forceinline__ int pass_compact(unsigned long long flagged, int *s_wcnt, int lane, int wave,
+                                                   int n_waves, int &total) {
+    if (lane == 0) s_wcnt[wave] = __popcll(flagged);
+    __syncthreads();
+    int before = 0;
+    total = 0;
+    for (int w = 0; w < n_waves; ++w) {
+        const int c = s_wcnt[w];
+        before += w < wave ? c : 0;
+        total += c;
+    }
+    return before + __popcll(flagged & ((1ull << lane) - 1ull));
+}
+
 // ---- episode role: one workgroup, the last of the tracked launch.  It reads the call's arguments and its own four
 // arrays only -- nothing the other roles write -- and rebuilds the id bitmaps for itself, so it waits on nobody.
 // Passes of blockDim.x rows.  Per row in parallel (the ids of a call are distinct): the stream's running return and
@@ -133,19 +152,10 @@ static __device__ __forceinline__ void ingest_episode_role(const IngestArgs &a, 
             }
         }
         const unsigned long long ends = __ballot(end), trk = __ballot(tracked);
-        if (lane == 0) {
-            s_wcnt[wave] = __popcll(ends);
-            if (trk) atomicAdd(&s_tracked, __popcll(trk));
-        }
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int w = 0; w < n_waves; ++w) {
-            const int c = s_wcnt[w];
-            before += w < wave ? c : 0;
-            total += c;
-        }
+        if (lane == 0 && trk) atomicAdd(&s_tracked, __popcll(trk));
+        int total;
+        const int pos = pass_compact(ends, s_wcnt, lane, wave, n_waves, total);
         if (end) {
-            const int pos = before + __popcll(ends & ((1ull << lane) - 1ull));
             s_ret[pos] = ret;
             s_len[pos] = len;
         }

@@ -20,6 +20,7 @@ _TIMER_KEYS = ("Component Update Time", "Iteration Time", "Agent Update Time", "
 class Learner:
     def __init__(self):
         self.agent = self.timestep_collector = self.experience_buffer = self.logger = self.checkpointer = None
+        self.evaluator = None
         self.cumulative_timesteps = 0
         self.cumulative_model_updates = 0
         self.timesteps_since_report = 0
@@ -33,7 +34,10 @@ class Learner:
         self.hip_graph = True
         self._resumed = False
 
-    def configure(self, config, collector=None, obs_shape=None, n_actions=None, process_group=None):
+    def configure(self, config, collector=None, obs_shape=None, n_actions=None, process_group=None, eval_envs=None):
+        """``eval_envs`` (the ``VectorCollector`` protocol, prism_amd/collectors.py): evaluate the agent on them every
+        ``config.timesteps_between_evaluations`` timesteps for ``config.evaluation_timestep_horizon`` timesteps
+        (``VectorEvaluator``, prism_amd/evals.py); None: no evaluator, nothing else changes."""
         (self.agent, self.timestep_collector, self.experience_buffer, self.logger,
          self.checkpointer) = algorithm_factory.build_algorithm(config, collector, obs_shape, n_actions,
                                                                 process_group)
@@ -58,6 +62,11 @@ class Learner:
         self.hip_graph = bool(getattr(config, "hip_graph", True))
         self._resumed = False
         self.checkpointer.attach(self, config)              # config.backup_checkpoints: the hourly exact-resume snapshot
+        self.evaluator = None
+        if eval_envs is not None:
+            from prism_amd.evals import VectorEvaluator
+            self.evaluator = VectorEvaluator(self.agent, eval_envs, config.timesteps_between_evaluations,
+                                             config.evaluation_timestep_horizon)
 
     # ------------------------------------------------------------------ the hot path
     def step(self, timesteps_this_iteration=0, eager=False):
@@ -125,6 +134,11 @@ class Learner:
                     self.collected_steps_per_second_ema * 0.9 + 0.1 * sps
             self.step(n)
             self.checkpointer.checkpoint(self.cumulative_timesteps)
+            if self.evaluator is not None and \
+                    self.evaluator.maybe_evaluate_agent(n, self.cumulative_timesteps) is not None:
+                last = self.evaluator.last
+                self.logger.log_data(last["mean"], "Report/Rewards", "Eval Reward")
+                self.logger.log_data(last["episodes"], "Report/Rewards", "Eval Episodes")
             if self.timesteps_since_report >= self.timesteps_per_report:
                 self.report()
             it = time.perf_counter() - loop_start
@@ -179,6 +193,8 @@ class Learner:
             finally:
                 self.experience_buffer.empty()
                 self.timestep_collector.close()
+                if self.evaluator is not None:
+                    self.evaluator.close()
                 self.logger.close()
 
     # ------------------------------------------------------------------ exact resume (prism_amd/util/snapshot.py)
@@ -198,8 +214,9 @@ class Learner:
         opt = lambda x: None if x is None else float(x)
         hold = getattr(self.logger, "holdout_data", None)
         col = self.timestep_collector
+        ev = {} if self.evaluator is None else dict(evaluator=self.evaluator.state_dict())      # (the key exists only then)
         return dict(
-            cumulative_timesteps=int(self.cumulative_timesteps), cumulative_model_updates=int(self.cumulative_model_updates),
+            **ev, cumulative_timesteps=int(self.cumulative_timesteps), cumulative_model_updates=int(self.cumulative_model_updates),
             timesteps_since_report=int(self.timesteps_since_report),
             timesteps_since_target_model_update=int(self.timesteps_since_target_model_update),
             collected_steps_per_second_ema=opt(self.collected_steps_per_second_ema),
@@ -215,7 +232,7 @@ class Learner:
         """One exact-resume snapshot of the whole run: the replay ring (part ``replay``), the agent (``agent/`` in the
         reference's layout + part ``agent_resume``) and the loop (part ``learner``: counters, target-sync timer, PER anneal,
         holdout batch, checkpoint mark, the global NumPy / Python / torch generators, the collector's ``state_dict()`` where
-        it has one).  Wall-clock timers are not part of it."""
+        it has one, the evaluator's where there is an evaluator).  Wall-clock timers are not part of it."""
         from prism_amd.util import snapshot
         agent, buf = self.agent, self.experience_buffer
         parts = {"replay": buf._state_part(), "agent_resume": agent._state_part(), "learner": self._state_part()}
@@ -254,6 +271,8 @@ class Learner:
         col = self.timestep_collector
         if st["collector"] is not None and hasattr(col, "load_state_dict"):
             col.load_state_dict(st["collector"])
+        if self.evaluator is not None and st.get("evaluator") is not None:
+            self.evaluator.load_state_dict(st["evaluator"])
         # last: nothing above may draw from them
         snapshot.set_numpy_rng_state(st["numpy_rng"])
         snapshot.set_python_rng_state(st["python_rng"])

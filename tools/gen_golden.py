@@ -20,6 +20,9 @@ What is captured:
   collector_bookkeeping.npz  reward clip, episodic reward and training-reward EMA of the reference's collector
                      (collector_process_interface.py:129-139, experience_collector.py:113-118), per timestep;
                      `python tools/gen_golden.py collector`.
+  evaluator_runs.npz SyncAgentEvaluator.evaluate_agent (prism/evals/sync_agent_evaluator.py:25-62) over scripted
+                     single-environment runs: rewards, end kinds, horizon, the returned ep_rews as float64 bits and the
+                     timesteps consumed; `python tools/gen_golden.py evaluator`.
 """
 import contextlib
 import io
@@ -566,11 +569,105 @@ def gen_collector_bookkeeping():
           int((out["clamp_stored_reward"] != out["none_stored_reward"]).sum()))
 
 
+def evaluator_scripts(seed=53):
+    """name -> (reward float64 [steps] of float32-exact values, kind uint8 [steps]: 0 goes on | 1 done | 2 truncated |
+    3 both, horizon).  Every script is longer than the evaluator can consume."""
+    rng = np.random.default_rng(seed)
+    pool = np.array([0.0, 1.0, -1.0, 0.5, -0.25, 3.0, -7.5, 0.1, -0.1, 1e-3, 1e6, -123456.0, 0.7, -2.59], np.float32)
+
+    def script(lengths, kinds=None, steps=None, values=pool):
+        steps = sum(lengths) if steps is None else steps
+        kind = np.zeros(steps, np.uint8)
+        ends = np.cumsum(lengths) - 1
+        kind[ends[ends < steps]] = 1 if kinds is None else np.asarray(kinds, np.uint8)[:int((ends < steps).sum())]
+        return values[rng.integers(0, len(values), steps)].astype(np.float64), kind
+
+    runs = {}
+    runs["horizon_zero"] = script([7, 3, 5]) + (0,)                        # at least one episode is still collected
+    runs["on_an_end"] = script([5, 4, 6, 5]) + (9,)                        # the horizon falls on the second episode's end
+    runs["before_an_end"] = script([5, 4, 6, 5]) + (8,)
+    runs["after_an_end"] = script([5, 4, 6, 5]) + (10,)
+    runs["long_first_episode"] = script([50, 6, 6]) + (20,)                # goes on until the first episode ends
+    runs["one_step_episodes"] = script([1] * 16) + (12,)
+    runs["done_and_truncated"] = script([3, 1, 4, 2, 6, 1, 5, 3, 7, 4, 6, 8],
+                                        [1, 2, 3, 2, 1, 1, 2, 3, 1, 2, 1, 1]) + (40,)
+    small = np.array([-0.1, 0.1, 0.7, -2.59, 1e-3, -0.25, 0.5, -7.5], np.float32)
+    lengths = [int(x) for x in rng.integers(1, 30, 40)]
+    runs["negative_and_fractional"] = script(lengths, [int(x) for x in rng.integers(1, 4, 40)], values=small) + (250,)
+    return runs
+
+
+def gen_evaluator():
+    """The live SyncAgentEvaluator, loaded file-wise (the package import pulls in wandb and the environment factories),
+    with a stub agent over scripted single-environment runs.  The reward arrays are float64 whose values are
+    float32-exact: the evaluator's `current_ep_rew += rew[0]` then sums in float64 (with float32 arrays NumPy 2 keeps
+    the sum in float32)."""
+    import importlib.util
+    names = ("prism", "prism.util", "prism.util.observation_stacker")
+    saved = {n: sys.modules.get(n) for n in names}
+
+    def load(name, path):
+        spec = importlib.util.spec_from_file_location(name, os.path.join(REF, path))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        return mod
+    try:
+        for n in names[:2]:
+            sys.modules[n] = types.ModuleType(n)
+            sys.modules[n].__path__ = []
+        sys.modules[names[2]] = load(names[2], "prism/util/observation_stacker.py")
+        SyncAgentEvaluator = load("_ref_sync_agent_evaluator", "prism/evals/sync_agent_evaluator.py").SyncAgentEvaluator
+    finally:
+        for n, m in saved.items():
+            if m is None:
+                sys.modules.pop(n, None)
+            else:
+                sys.modules[n] = m
+
+    class Env:
+        def __init__(self, reward, kind):
+            self.reward, self.kind, self.k, self.resets = reward, kind, 0, 0
+
+        def reset(self):
+            self.resets += 1
+            return np.zeros((1, 2), np.float32), {}
+
+        def step(self, action):
+            k = self.k
+            self.k += 1
+            return (np.full((1, 2), k, np.float32), self.reward[k:k + 1], bool(self.kind[k] & 1), bool(self.kind[k] & 2), {})
+
+    class Agent:
+        model = types.SimpleNamespace(device="cpu")
+
+        def forward(self, obs):
+            return torch.zeros(obs.shape[0], dtype=torch.long)
+
+        def eval(self):
+            pass
+
+        def train(self):
+            pass
+
+    out, runs = {}, evaluator_scripts()
+    for name, (reward, kind, horizon) in runs.items():
+        assert reward.dtype == np.float64 and (reward.astype(np.float32).astype(np.float64) == reward).all()
+        env = Env(reward, kind)
+        ep = SyncAgentEvaluator(Agent(), env, 0, horizon).evaluate_agent()
+        assert env.resets == 1 + len(ep) and len(ep) >= 1 and env.k <= len(reward)
+        out[name + "_reward"], out[name + "_kind"], out[name + "_horizon"] = reward, kind, np.int64(horizon)
+        out[name + "_ep_rews_bits"] = np.array([float(r) for r in ep], np.float64).view(np.uint64)
+        out[name + "_timesteps"] = np.int64(env.k)
+        print("evaluator:", name, "horizon", horizon, "->", len(ep), "episodes in", env.k, "timesteps")
+    out["names"] = np.array(list(runs))
+    np.savez_compressed(os.path.join(OUT, "evaluator_runs.npz"), **out)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     _import_reference()
     which = sys.argv[1:] or (list(CASES) + ["nstep", "nstep_more", "config", "checkpoint", "checkpoint_rmsprop",
-                                   "collector"])
+                                   "collector", "evaluator"])
     for name in which:
         if name == "nstep":
             gen_nstep()
@@ -584,6 +681,8 @@ def main():
             gen_config_snapshot()
         elif name == "collector":
             gen_collector_bookkeeping()
+        elif name == "evaluator":
+            gen_evaluator()
         else:
             gen_update_case(name, *CASES[name])
 
