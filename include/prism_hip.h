@@ -52,10 +52,24 @@ extern "C" {
 #define PRISM_STATUS_NONPOSITIVE_PSUM 1
 #define PRISM_STATUS_NONPOSITIVE_PMIN 2
 #define PRISM_STATUS_INGEST_DUP_STREAM 4   /* prism_replay_ingest: a stream id repeated in one call or outside the table */
+#define PRISM_STATUS_OBS_INEXACT 8         /* byte ring: a float that is not byte-exact was narrowed (stored as 0) */
 
 /* prism_replay_ingest obs_kind */
 #define PRISM_OBS_F32 0
 #define PRISM_OBS_U8 1     /* uint8 / bool observations, widened to fp32 on the device */
+
+/* Storage kind of the ring's two observation arrays (prism_replay_desc.obs / succ_obs), the `ring_kind` argument of the
+ * prism_*_ring entry points.  The descriptor is the same for both kinds: a byte ring holds its two uint8
+ * [capacity][obs_elems] arrays in `obs` / `succ_obs`.  The entry points without the argument are the fp32 kind.
+ *   byte-exact   a float whose bit pattern is that of (float)b for a b in 0..255: +0.0, 1.0 .. 255.0 (not -0.0, NaN,
+ *                +-inf, fractions, negatives, values above 255)
+ *   narrowing    a byte-exact float is stored as b; every other float is stored as 0 and the sticky bit
+ *                PRISM_STATUS_OBS_INEXACT is set in rp->status (the call never reads device memory on the host)
+ *   widening     (float)b, exact: a byte ring fed byte-exact rows yields bit for bit what the fp32 ring yields
+ * Entry points that never touch observation rows (prism_per_*, prism_step_back*, prism_replay_init) take a byte ring's
+ * descriptor as it is.  An unknown ring_kind is PRISM_ERR_INVALID, the message names the entry point. */
+#define PRISM_RING_F32 0
+#define PRISM_RING_U8 1
 
 typedef void *prism_stream_t;
 
@@ -105,6 +119,13 @@ int prism_replay_insert(const prism_replay_desc *rp, int32_t n, const int32_t *s
                         const float *obs, const float *succ_obs, const float *reward,
                         const int32_t *action, const uint8_t *flags, const int32_t *prev_slot,
                         float alpha, float eps, prism_stream_t stream);
+
+/* prism_replay_insert for a ring of either storage kind.  A byte ring takes uint8 staging rows (obs_kind PRISM_OBS_U8,
+ * copied) or fp32 ones (PRISM_OBS_F32, narrowed); an fp32 ring takes fp32 rows only, and is prism_replay_insert. */
+int prism_replay_insert_ring(const prism_replay_desc *rp, int32_t ring_kind, int32_t n, const int32_t *slots,
+                             const void *obs, const void *succ_obs, int32_t obs_kind, const float *reward,
+                             const int32_t *action, const uint8_t *flags, const int32_t *prev_slot,
+                             float alpha, float eps, prism_stream_t stream);
 
 /* One step of a vectorised collector: n transitions of n DISTINCT environment streams, applied in
  * order i = 0..n-1 with exactly the result of n one-row prism_replay_insert calls -- in one launch and
@@ -159,6 +180,15 @@ int prism_replay_ingest_tracked(const prism_replay_desc *rp, int32_t n, int64_t 
                                 const int32_t *action, const uint8_t *done, const uint8_t *truncated,
                                 const int32_t *stream_ids, int64_t *stream_tab, int32_t n_streams,
                                 float alpha, float eps, const prism_episode_desc *ep, prism_stream_t stream);
+
+/* prism_replay_ingest (ep == NULL) / prism_replay_ingest_tracked (ep != NULL) for a ring of either storage kind.  Into a
+ * byte ring uint8 / bool rows are copied and fp32 rows narrowed (a row without successor stores zeros, as ever). */
+int prism_replay_ingest_ring(const prism_replay_desc *rp, int32_t ring_kind, int32_t n, int64_t first_slot,
+                             int64_t serial0, const void *obs, const void *next_obs, int32_t obs_kind,
+                             const float *reward, const int32_t *action, const uint8_t *done,
+                             const uint8_t *truncated, const int32_t *stream_ids, int64_t *stream_tab,
+                             int32_t n_streams, float alpha, float eps, const prism_episode_desc *ep,
+                             prism_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Evaluation bookkeeping -- SyncAgentEvaluator.evaluate_agent (prism/evals/sync_agent_evaluator.py:37-59) for n_streams
@@ -215,6 +245,12 @@ int prism_replay_gather(const prism_replay_desc *rp, const int64_t *index, int32
                         float *out_obs, float *out_next_obs, float *out_reward,
                         uint8_t *out_nonterminal, float *out_gamma, int64_t *out_action,
                         prism_stream_t stream);
+
+/* prism_replay_gather from a ring of either storage kind (the outputs are fp32 either way: bytes are widened). */
+int prism_replay_gather_ring(const prism_replay_desc *rp, int32_t ring_kind, const int64_t *index, int32_t batch,
+                             float *out_obs, float *out_next_obs, float *out_reward,
+                             uint8_t *out_nonterminal, float *out_gamma, int64_t *out_action,
+                             prism_stream_t stream);
 
 /* PrioritizedSampler.update_priority (timestep_buffer.py:53-54 <- learner.py:120):
  * max_priority = max(max_priority, max(priority)); leaf = (priority + eps) ** alpha in both
@@ -412,6 +448,13 @@ int prism_learner_clip_adam(const prism_learner_desc *ld, prism_stream_t stream)
 int prism_step_front(const prism_learner_desc *ld, const prism_replay_desc *rp, int64_t size,
                      const float *mass, uint64_t seed, uint64_t offset, float beta,
                      int64_t *out_index, float *out_weight, prism_stream_t stream);
+
+/* prism_step_front sampling from a ring of either storage kind: the three observation-row reads of the launch take
+ * one 32-bit word per thread from a byte ring and widen it; the static batch it writes stays fp32, so nothing behind
+ * this launch (prism_learner_fwd_bwd, prism_step_back*) knows the kind. */
+int prism_step_front_ring(const prism_learner_desc *ld, const prism_replay_desc *rp, int32_t ring_kind, int64_t size,
+                          const float *mass, uint64_t seed, uint64_t offset, float beta,
+                          int64_t *out_index, float *out_weight, prism_stream_t stream);
 
 /* prism_learner_clip_adam + prism_per_update(index, |ld->out_td|) in one launch. */
 int prism_step_back(const prism_learner_desc *ld, const prism_replay_desc *rp, const int64_t *index,

@@ -14,8 +14,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "prism_hip.h")
 PRISM_OK, PRISM_ERR_INVALID, PRISM_ERR_HIP, PRISM_ERR_UNSUPPORTED = 0, -1, -2, -3
 PRISM_MAX_NSTEP = 15
 FLAG_DONE, FLAG_TRUNC, FLAG_HAS_NEXT = 1, 2, 4
-STATUS_NONPOSITIVE_PSUM, STATUS_NONPOSITIVE_PMIN, STATUS_INGEST_DUP_STREAM = 1, 2, 4
+STATUS_NONPOSITIVE_PSUM, STATUS_NONPOSITIVE_PMIN, STATUS_INGEST_DUP_STREAM, STATUS_OBS_INEXACT = 1, 2, 4, 8
 OBS_F32, OBS_U8 = 0, 1
+RING_F32, RING_U8 = 0, 1          # storage kind of the ring's observation arrays (the prism_*_ring entry points)
 CLIP_NONE, CLIP_CLAMP = 0, 1
 INGEST_MAX_STREAMS = 65536
 WS_STATUS_WORD, WS_STATUS_BARRIER_TIMEOUT, WS_STATUS_COLLECTIVE_TIMEOUT = 7, 1, 2
@@ -110,16 +111,22 @@ SIGNATURES = {
     "prism_replay_init": (ctypes.c_int, [_P(ReplayDesc), c_vp]),
     "prism_replay_insert": (ctypes.c_int, [_P(ReplayDesc), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                             c_f32, c_f32, c_vp]),
+    "prism_replay_insert_ring": (ctypes.c_int, [_P(ReplayDesc), c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                                 c_f32, c_f32, c_vp]),
     "prism_replay_ingest": (ctypes.c_int, [_P(ReplayDesc), c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
                                             c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_vp]),
     "prism_replay_ingest_tracked": (ctypes.c_int, [_P(ReplayDesc), c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
                                                     c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, _P(EpisodeDesc), c_vp]),
+    "prism_replay_ingest_ring": (ctypes.c_int, [_P(ReplayDesc), c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                                 c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, _P(EpisodeDesc), c_vp]),
     "prism_eval_track": (ctypes.c_int, [_P(EvalDesc), c_i32, c_vp, c_vp, c_vp, c_vp]),
     "prism_per_sample": (ctypes.c_int, [_P(ReplayDesc), c_i64, c_i32, c_vp, c_u64, c_u64, c_f32, c_vp, c_vp,
                                          c_vp]),
     "prism_uniform_sample": (ctypes.c_int, [c_i64, c_i32, c_u64, c_u64, c_vp, c_vp]),
     "prism_replay_gather": (ctypes.c_int, [_P(ReplayDesc), c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                             c_vp]),
+    "prism_replay_gather_ring": (ctypes.c_int, [_P(ReplayDesc), c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                 c_vp]),
     "prism_per_update": (ctypes.c_int, [_P(ReplayDesc), c_vp, c_vp, c_i32, c_f32, c_f32, c_i32, c_vp]),
     "prism_per_rebuild": (ctypes.c_int, [_P(ReplayDesc), c_vp]),
     "prism_per_query": (ctypes.c_int, [_P(ReplayDesc), c_i64, c_vp, c_vp]),
@@ -131,6 +138,8 @@ SIGNATURES = {
     "prism_step_back_opt": (ctypes.c_int, [_P(LearnerDesc), _P(OptHyper), _P(ReplayDesc), c_vp, c_f32, c_f32, c_vp]),
     "prism_step_front": (ctypes.c_int, [_P(LearnerDesc), _P(ReplayDesc), c_i64, c_vp, c_u64, c_u64, c_f32, c_vp, c_vp,
                                          c_vp]),
+    "prism_step_front_ring": (ctypes.c_int, [_P(LearnerDesc), _P(ReplayDesc), c_i32, c_i64, c_vp, c_u64, c_u64, c_f32, c_vp,
+                                              c_vp, c_vp]),
     "prism_step_back": (ctypes.c_int, [_P(LearnerDesc), _P(ReplayDesc), c_vp, c_f32, c_f32, c_vp]),
     "prism_act_forward": (ctypes.c_int, [_P(LearnerDesc), c_vp, c_i32, c_i32, c_vp, c_u64, c_u64, c_vp, c_vp, c_vp]),
     "prism_ids_select": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_i32, c_vp, c_vp,

@@ -585,9 +585,14 @@ class HipAgent:
         d.fuse_tail = int(part == "all" and self.world == 1 and self.fuse_tail and self._opt_key is None)
         if part in ("all", "front"):
             d.embed_done = 1
-            N.check(L.prism_step_front(ctypes.byref(d), rp, buf._size, None, buf.seed, buf._draws,
-                                       buf.buffer._sampler._beta, N.ptr(buf._index), N.ptr(buf._weight), st()),
-                    "prism_step_front")
+            if buf._ring_kind:                             # a byte ring: the same launch, its row loads a word per thread
+                N.check(L.prism_step_front_ring(ctypes.byref(d), rp, buf._ring_kind, buf._size, None, buf.seed, buf._draws,
+                                                buf.buffer._sampler._beta, N.ptr(buf._index), N.ptr(buf._weight), st()),
+                        "prism_step_front_ring")
+            else:
+                N.check(L.prism_step_front(ctypes.byref(d), rp, buf._size, None, buf.seed, buf._draws,
+                                           buf.buffer._sampler._beta, N.ptr(buf._index), N.ptr(buf._weight), st()),
+                        "prism_step_front")
             N.check(L.prism_learner_fwd_bwd(ctypes.byref(d), st()), "prism_learner_fwd_bwd")
             d.embed_done = 0
         if part == "all" and self.world > 1:

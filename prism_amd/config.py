@@ -17,6 +17,11 @@ constructing unchanged); they are read with ``getattr(config, name, default)``:
     e_greedy_per_env  bool, epsilon-greedy tosses one coin per observation, on the device (Philox,
                       inside the acting hipGraph), instead of the reference's one host coin per
                       Agent.forward call (default False); for vector collectors under use_e_greedy
+    replay_obs_storage
+                      "float32" (default, the reference layout) | "uint8": the replay ring keeps its two
+                      observation arrays as one byte per element -- a quarter of the HBM -- for byte-exact
+                      observations (integers 0..255 such as MinAtar's boolean planes); results are bit for bit
+                      those of the fp32 ring, any other observation is refused (HipReplayBuffer obs_storage)
 """
 import dataclasses
 import json

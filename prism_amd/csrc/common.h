@@ -95,6 +95,26 @@ __device__ __forceinline__ void kernarg_prefetch() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::"s"(t0), "s"(t1), "s"(t2), "s"(t3) : "memory");
 }
 
+// ---- byte observation ring (PRISM_RING_U8): one uint8 per element of obs / succ_obs -----------------------------------
+// A float is BYTE-EXACT iff its bit pattern is that of (float)b for a b in 0..255: +0.0, 1.0 .. 255.0 -- not -0.0, NaN,
+// +-inf, fractions, negatives, values above 255.  Narrowing stores b for a byte-exact float and 0 (with `inexact` raised)
+// for every other; widening is (float)b, exact -- so a byte ring fed byte-exact data equals the fp32 ring bit for bit.
+// Every path that narrows (row stores of insert / ingest here, the host's checks restate it) goes through this function.
+__host__ __device__ inline uint32_t obs_narrow(float x, bool &inexact) {
+    const uint32_t b = (x >= 0.f && x <= 255.f) ? (uint32_t)x : 0u;               // (NaN fails both compares)
+    const bool same = __builtin_bit_cast(uint32_t, (float)b) == __builtin_bit_cast(uint32_t, x);
+    inexact = inexact || !same;
+    return same ? b : 0u;
+}
+// four elements <-> one 32-bit word of a row (element j in byte j: the row's own byte order)
+__host__ __device__ inline uint32_t obs_narrow4(const float4 &v, bool &inexact) {
+    return obs_narrow(v.x, inexact) | (obs_narrow(v.y, inexact) << 8) | (obs_narrow(v.z, inexact) << 16) |
+           (obs_narrow(v.w, inexact) << 24);
+}
+__host__ __device__ inline float4 obs_widen4(uint32_t w) {
+    return make_float4((float)(w & 255u), (float)((w >> 8) & 255u), (float)((w >> 16) & 255u), (float)(w >> 24));
+}
+
 // ---- LDS carve-ups, checked at compile time ------------------------------------------------------------------------
 // Every kernel that splits one LDS allocation into regions states them in ONE constexpr table -- offset, size (in the unit
 // the kernel indexes by) and the phases of the kernel in which somebody may still read or write the region -- takes its

@@ -25,6 +25,18 @@ using namespace prism;
                         "stream_ids NULL (row i is stream i) needs n <= n_streams");                                    \
     } while (0)
 
+// ... and what the tracked launch adds on its episode descriptor
+#define INGEST_CHECK_EPISODES()                                                                                         \
+    do {                                                                                                                \
+        PRISM_CHECK_ARG(ep->reward_clip == PRISM_CLIP_NONE || ep->reward_clip == PRISM_CLIP_CLAMP,                      \
+                        "reward_clip must be PRISM_CLIP_NONE or PRISM_CLIP_CLAMP");                                     \
+        PRISM_CHECK_ARG(std::isfinite(ep->ema) && ep->ema >= 0.0 && ep->ema <= 1.0, "ema must be finite and in [0, 1]"); \
+        const int set = (ep->ep_return != nullptr) + (ep->ep_length != nullptr) + (ep->stats != nullptr) +              \
+                        (ep->counts != nullptr);                                                                        \
+        PRISM_CHECK_ARG(set == 0 || set == 4, "ep_return, ep_length, stats and counts must be all set or all NULL");    \
+        PRISM_CHECK_ARG(ep->count_first_step == 0 || ep->count_first_step == 1, "count_first_step must be 0 or 1");     \
+    } while (0)
+
 namespace {
 
 struct IngestLaunch {
@@ -35,7 +47,7 @@ struct IngestLaunch {
 IngestLaunch ingest_plan(const prism_replay_desc *rp, int32_t n, int64_t first_slot, int64_t serial0, const void *obs,
                          const void *next_obs, int32_t obs_kind, const float *reward, const int32_t *action,
                          const uint8_t *done, const uint8_t *truncated, const int32_t *stream_ids, int64_t *stream_tab,
-                         int32_t n_streams, float alpha, float eps) {
+                         int32_t n_streams, float alpha, float eps, int32_t ring_kind = PRISM_RING_F32) {
     IngestLaunch L;
     IngestArgs &a = L.a;
     a.n = n;
@@ -43,7 +55,8 @@ IngestLaunch ingest_plan(const prism_replay_desc *rp, int32_t n, int64_t first_s
     a.obs_kind = obs_kind;
     const uintptr_t src = reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(next_obs);
     const uintptr_t dst = reinterpret_cast<uintptr_t>(rp->obs) | reinterpret_cast<uintptr_t>(rp->succ_obs);
-    a.vec = (rp->obs_elems & 3) == 0 && (dst & 15) == 0 && (src & (obs_kind == PRISM_OBS_F32 ? 15 : 3)) == 0;
+    a.vec = (rp->obs_elems & 3) == 0 && (dst & (ring_kind == PRISM_RING_F32 ? 15 : 3)) == 0 &&
+            (src & (obs_kind == PRISM_OBS_F32 ? 15 : 3)) == 0;
     a.first_slot = first_slot;
     a.serial0 = serial0;
     a.obs = obs;
@@ -85,17 +98,37 @@ extern "C" int prism_replay_ingest_tracked(const prism_replay_desc *rp, int32_t 
                                            float eps, const prism_episode_desc *ep, prism_stream_t stream) {
     INGEST_CHECK_ARGS();
     PRISM_CHECK_ARG(ep != nullptr, "null episode descriptor");
-    PRISM_CHECK_ARG(ep->reward_clip == PRISM_CLIP_NONE || ep->reward_clip == PRISM_CLIP_CLAMP,
-                    "reward_clip must be PRISM_CLIP_NONE or PRISM_CLIP_CLAMP");
-    PRISM_CHECK_ARG(std::isfinite(ep->ema) && ep->ema >= 0.0 && ep->ema <= 1.0, "ema must be finite and in [0, 1]");
-    const int set = (ep->ep_return != nullptr) + (ep->ep_length != nullptr) + (ep->stats != nullptr) + (ep->counts != nullptr);
-    PRISM_CHECK_ARG(set == 0 || set == 4, "ep_return, ep_length, stats and counts must be all set or all NULL");
-    PRISM_CHECK_ARG(ep->count_first_step == 0 || ep->count_first_step == 1, "count_first_step must be 0 or 1");
+    INGEST_CHECK_EPISODES();
     const IngestLaunch L = ingest_plan(rp, n, first_slot, serial0, obs, next_obs, obs_kind, reward, action, done, truncated,
                                        stream_ids, stream_tab, n_streams, alpha, eps);
     // workgroup 0 and the row stores keep their indices; the episode role is the last workgroup
     hipLaunchKernelGGL(replay_ingest_tracked_kernel, dim3(2 + L.row_wgs), dim3(L.threads), 0, (hipStream_t)stream, *rp, L.a,
                        *ep);
+    PRISM_CHECK_LAUNCH();
+    return PRISM_OK;
+}
+
+// Either storage kind, plain (ep == NULL) or tracked: the fp32 kind launches the kernels of the two entry points above.
+extern "C" int prism_replay_ingest_ring(const prism_replay_desc *rp, int32_t ring_kind, int32_t n, int64_t first_slot,
+                                        int64_t serial0, const void *obs, const void *next_obs, int32_t obs_kind,
+                                        const float *reward, const int32_t *action, const uint8_t *done,
+                                        const uint8_t *truncated, const int32_t *stream_ids, int64_t *stream_tab,
+                                        int32_t n_streams, float alpha, float eps, const prism_episode_desc *ep,
+                                        prism_stream_t stream) {
+    INGEST_CHECK_ARGS();
+    PRISM_CHECK_RING_KIND(rp, ring_kind);
+    if (ep) INGEST_CHECK_EPISODES();
+    const IngestLaunch L = ingest_plan(rp, n, first_slot, serial0, obs, next_obs, obs_kind, reward, action, done, truncated,
+                                       stream_ids, stream_tab, n_streams, alpha, eps, ring_kind);
+    const dim3 grid((ep ? 2 : 1) + L.row_wgs), block(L.threads);
+    hipStream_t st = (hipStream_t)stream;
+    if (ring_kind == PRISM_RING_U8) {
+        if (ep) hipLaunchKernelGGL(byte_ring_ingest_tracked_kernel, grid, block, 0, st, *rp, L.a, *ep);
+        else hipLaunchKernelGGL(byte_ring_ingest_kernel, grid, block, 0, st, *rp, L.a);
+    } else {
+        if (ep) hipLaunchKernelGGL(replay_ingest_tracked_kernel, grid, block, 0, st, *rp, L.a, *ep);
+        else hipLaunchKernelGGL(replay_ingest_kernel, grid, block, 0, st, *rp, L.a);
+    }
     PRISM_CHECK_LAUNCH();
     return PRISM_OK;
 }

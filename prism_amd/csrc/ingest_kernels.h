@@ -27,7 +27,7 @@ constexpr LdsRegion IG_REGIONS[] = {TW_SORTED, TW_VAL, TW_PART, TW_KEYS, TW_REC,
 static_assert(lds_layout_ok(IG_REGIONS, TREE_WRITE_LDS_BYTES), "ingest: the bitmaps do not fit the tree writer's pool");
 
 struct IngestArgs {
-    int32_t n, n_streams, obs_kind, vec;            // vec: 16-byte (fp32) / 4-byte (uint8) row accesses are aligned
+    int32_t n, n_streams, obs_kind, vec;            // vec: 16-byte (fp32) / 4-byte (uint8) row accesses are aligned, both sides
     int64_t first_slot, serial0;
     const void *obs, *next_obs;                     // [n][obs_elems] fp32 (obs_kind 0) or uint8 (obs_kind 1)
     const float *reward;
@@ -183,7 +183,8 @@ static __device__ __forceinline__ void ingest_episode_role(const IngestArgs &a, 
 }
 
 // TRACKED: the launch of prism_replay_ingest_tracked -- one more workgroup behind the row stores, a reward clip in them.
-template <bool TRACKED>
+// RING: the storage kind of rp.obs / rp.succ_obs (prism_replay_ingest_ring); only the row-store role knows it.
+template <bool TRACKED, int RING = PRISM_RING_F32>
 static __device__ __forceinline__ void replay_ingest_body(const prism_replay_desc &rp, const IngestArgs &a,
                                                           const prism_episode_desc &ep, const int tid, const int bd,
                                                           const unsigned wg, const unsigned n_wgs) {
@@ -204,12 +205,53 @@ static __device__ __forceinline__ void replay_ingest_body(const prism_replay_des
         const int O = rp.obs_elems;
         const int per_wg = bd / INGEST_ROW_THREADS, lane = tid % INGEST_ROW_THREADS;
         const int64_t stride = (int64_t)(row_wgs)*per_wg;
+        [[maybe_unused]] bool inexact = false;                       // (byte ring: a float that was not byte-exact)
         for (int64_t i = (int64_t)(wg - 1) * per_wg + tid / INGEST_ROW_THREADS; i < n; i += stride) {
             const int64_t s = (first + i) % cap;
             const bool done = a.done[i] != 0, trunc = a.truncated[i] != 0;
             const bool has_next = trunc || !done;
-            float *d0 = rp.obs + s * O, *d1 = rp.succ_obs + s * O;
-            if (a.obs_kind == 0) {
+            if constexpr (RING == PRISM_RING_F32) {
+                float *d0 = rp.obs + s * O, *d1 = rp.succ_obs + s * O;
+                if (a.obs_kind == 0) {
+                    const float *s0 = static_cast<const float *>(a.obs) + i * O;
+                    const float *s1 = static_cast<const float *>(a.next_obs) + i * O;
+                    if (a.vec) {
+                        for (int k = lane; k < O / 4; k += INGEST_ROW_THREADS) {
+                            const float4 v0 = reinterpret_cast<const float4 *>(s0)[k];
+                            float4 v1 = make_float4(0.f, 0.f, 0.f, 0.f);
+                            if (has_next) v1 = reinterpret_cast<const float4 *>(s1)[k];
+                            reinterpret_cast<float4 *>(d0)[k] = v0;
+                            reinterpret_cast<float4 *>(d1)[k] = v1;
+                        }
+                    } else {
+                        for (int k = lane; k < O; k += INGEST_ROW_THREADS) {
+                            d0[k] = s0[k];
+                            d1[k] = has_next ? s1[k] : 0.f;
+                        }
+                    }
+                } else {
+                    const uint8_t *s0 = static_cast<const uint8_t *>(a.obs) + i * O;
+                    const uint8_t *s1 = static_cast<const uint8_t *>(a.next_obs) + i * O;
+                    if (a.vec) {
+                        for (int k = lane; k < O / 4; k += INGEST_ROW_THREADS) {
+                            const uint32_t w0 = reinterpret_cast<const uint32_t *>(s0)[k];
+                            uint32_t w1 = 0u;
+                            if (has_next) w1 = reinterpret_cast<const uint32_t *>(s1)[k];
+                            reinterpret_cast<float4 *>(d0)[k] = make_float4((float)(w0 & 255u), (float)((w0 >> 8) & 255u),
+                                                                            (float)((w0 >> 16) & 255u), (float)(w0 >> 24));
+                            reinterpret_cast<float4 *>(d1)[k] = make_float4((float)(w1 & 255u), (float)((w1 >> 8) & 255u),
+                                                                            (float)((w1 >> 16) & 255u), (float)(w1 >> 24));
+                        }
+                    } else {
+                        for (int k = lane; k < O; k += INGEST_ROW_THREADS) {
+                            d0[k] = (float)s0[k];
+                            d1[k] = has_next ? (float)s1[k] : 0.f;
+                        }
+                    }
+                }
+            } else if (a.obs_kind == 0) {
+                // fp32 rows into a byte ring: narrowed (obs_narrow; a float that is not byte-exact is stored as 0)
+                uint8_t *d0 = reinterpret_cast<uint8_t *>(rp.obs) + s * O, *d1 = reinterpret_cast<uint8_t *>(rp.succ_obs) + s * O;
                 const float *s0 = static_cast<const float *>(a.obs) + i * O;
                 const float *s1 = static_cast<const float *>(a.next_obs) + i * O;
                 if (a.vec) {
@@ -217,16 +259,18 @@ static __device__ __forceinline__ void replay_ingest_body(const prism_replay_des
                         const float4 v0 = reinterpret_cast<const float4 *>(s0)[k];
                         float4 v1 = make_float4(0.f, 0.f, 0.f, 0.f);
                         if (has_next) v1 = reinterpret_cast<const float4 *>(s1)[k];
-                        reinterpret_cast<float4 *>(d0)[k] = v0;
-                        reinterpret_cast<float4 *>(d1)[k] = v1;
+                        reinterpret_cast<uint32_t *>(d0)[k] = obs_narrow4(v0, inexact);
+                        reinterpret_cast<uint32_t *>(d1)[k] = obs_narrow4(v1, inexact);
                     }
                 } else {
                     for (int k = lane; k < O; k += INGEST_ROW_THREADS) {
-                        d0[k] = s0[k];
-                        d1[k] = has_next ? s1[k] : 0.f;
+                        d0[k] = (uint8_t)obs_narrow(s0[k], inexact);
+                        d1[k] = (uint8_t)obs_narrow(has_next ? s1[k] : 0.f, inexact);
                     }
                 }
             } else {
+                // uint8 / bool rows into a byte ring: copied, a 32-bit word per thread where the rows start on words
+                uint8_t *d0 = reinterpret_cast<uint8_t *>(rp.obs) + s * O, *d1 = reinterpret_cast<uint8_t *>(rp.succ_obs) + s * O;
                 const uint8_t *s0 = static_cast<const uint8_t *>(a.obs) + i * O;
                 const uint8_t *s1 = static_cast<const uint8_t *>(a.next_obs) + i * O;
                 if (a.vec) {
@@ -234,15 +278,13 @@ static __device__ __forceinline__ void replay_ingest_body(const prism_replay_des
                         const uint32_t w0 = reinterpret_cast<const uint32_t *>(s0)[k];
                         uint32_t w1 = 0u;
                         if (has_next) w1 = reinterpret_cast<const uint32_t *>(s1)[k];
-                        reinterpret_cast<float4 *>(d0)[k] = make_float4((float)(w0 & 255u), (float)((w0 >> 8) & 255u),
-                                                                        (float)((w0 >> 16) & 255u), (float)(w0 >> 24));
-                        reinterpret_cast<float4 *>(d1)[k] = make_float4((float)(w1 & 255u), (float)((w1 >> 8) & 255u),
-                                                                        (float)((w1 >> 16) & 255u), (float)(w1 >> 24));
+                        reinterpret_cast<uint32_t *>(d0)[k] = w0;
+                        reinterpret_cast<uint32_t *>(d1)[k] = w1;
                     }
                 } else {
                     for (int k = lane; k < O; k += INGEST_ROW_THREADS) {
-                        d0[k] = (float)s0[k];
-                        d1[k] = has_next ? (float)s1[k] : 0.f;
+                        d0[k] = s0[k];
+                        d1[k] = has_next ? s1[k] : (uint8_t)0;
                     }
                 }
             }
@@ -256,6 +298,9 @@ static __device__ __forceinline__ void replay_ingest_body(const prism_replay_des
                 rp.flags[s] = (uint8_t)((done ? PRISM_FLAG_DONE : 0u) | (trunc ? PRISM_FLAG_TRUNC : 0u) |
                                         (has_next ? PRISM_FLAG_HAS_NEXT : 0u));
             }
+        }
+        if constexpr (RING == PRISM_RING_U8) {
+            if (inexact) atomicOr(rp.status, PRISM_STATUS_OBS_INEXACT);
         }
         return;
     }
@@ -368,6 +413,16 @@ static __global__ __launch_bounds__(1024) void replay_ingest_kernel(prism_replay
 static __global__ __launch_bounds__(1024) void replay_ingest_tracked_kernel(prism_replay_desc rp, IngestArgs a,
                                                                             prism_episode_desc ep) {
     replay_ingest_body<true>(rp, a, ep, threadIdx.x, blockDim.x, blockIdx.x, gridDim.x);
+}
+
+// The two launches for a byte ring (prism_replay_ingest_ring with PRISM_RING_U8): the same roles, the row stores byte-wide.
+static __global__ __launch_bounds__(1024) void byte_ring_ingest_kernel(prism_replay_desc rp, IngestArgs a) {
+    replay_ingest_body<false, PRISM_RING_U8>(rp, a, prism_episode_desc{}, threadIdx.x, blockDim.x, blockIdx.x, gridDim.x);
+}
+
+static __global__ __launch_bounds__(1024) void byte_ring_ingest_tracked_kernel(prism_replay_desc rp, IngestArgs a,
+                                                                               prism_episode_desc ep) {
+    replay_ingest_body<true, PRISM_RING_U8>(rp, a, ep, threadIdx.x, blockDim.x, blockIdx.x, gridDim.x);
 }
 
 }  // namespace prism

@@ -747,9 +747,10 @@ static int check_replay_for_step(const prism_learner_desc *ld, const prism_repla
     return PRISM_OK;
 }
 
-extern "C" int prism_step_front(const prism_learner_desc *ld, const prism_replay_desc *rp, int64_t size,
-                                const float *mass, uint64_t seed, uint64_t offset, float beta, int64_t *out_index,
-                                float *out_weight, prism_stream_t stream_) {
+// the launch of prism_step_front / prism_step_front_ring
+static int step_front(const prism_learner_desc *ld, const prism_replay_desc *rp, int32_t ring_kind, int64_t size,
+                      const float *mass, uint64_t seed, uint64_t offset, float beta, int64_t *out_index, float *out_weight,
+                      prism_stream_t stream_) {
     LearnerPlan pl;
     int rc = check_learner(ld, pl);
     if (rc) return rc;
@@ -780,10 +781,30 @@ extern "C" int prism_step_front(const prism_learner_desc *ld, const prism_replay
         ProfileScope ps_(K_FRONT, stream);
         const IqnArgs af = front_args(a);
         const int extra = front_extra_blocks(extra_dims(af));
-        hipLaunchKernelGGL(step_front_kernel, dim3(ld->batch + extra), dim3(256), 0, stream, af, *rp, f);
+        if (ring_kind == PRISM_RING_U8)
+            hipLaunchKernelGGL(step_front_byte_ring_kernel, dim3(ld->batch + extra), dim3(256), 0, stream, af, *rp, f);
+        else
+            hipLaunchKernelGGL(step_front_kernel, dim3(ld->batch + extra), dim3(256), 0, stream, af, *rp, f);
         PRISM_CHECK_LAUNCH();
     }
     return PRISM_OK;
+}
+
+extern "C" int prism_step_front(const prism_learner_desc *ld, const prism_replay_desc *rp, int64_t size,
+                                const float *mass, uint64_t seed, uint64_t offset, float beta, int64_t *out_index,
+                                float *out_weight, prism_stream_t stream_) {
+    return step_front(ld, rp, PRISM_RING_F32, size, mass, seed, offset, beta, out_index, out_weight, stream_);
+}
+
+extern "C" int prism_step_front_ring(const prism_learner_desc *ld, const prism_replay_desc *rp, int32_t ring_kind, int64_t size,
+                                     const float *mass, uint64_t seed, uint64_t offset, float beta, int64_t *out_index,
+                                     float *out_weight, prism_stream_t stream_) {
+    PRISM_CHECK_ARG(ring_kind == PRISM_RING_F32 || ring_kind == PRISM_RING_U8,
+                    "ring_kind must be PRISM_RING_F32 or PRISM_RING_U8");
+    PRISM_CHECK_ARG(ring_kind != PRISM_RING_U8 || rp == nullptr ||
+                        ((reinterpret_cast<uintptr_t>(rp->obs) | reinterpret_cast<uintptr_t>(rp->succ_obs)) & 3) == 0,
+                    "a byte ring's obs / succ_obs must be 4-byte aligned");
+    return step_front(ld, rp, ring_kind, size, mass, seed, offset, beta, out_index, out_weight, stream_);
 }
 
 static int step_back(const prism_learner_desc *ld, const prism_opt_hyper *opt, const prism_replay_desc *rp, const int64_t *index,

@@ -9,6 +9,8 @@
 #pragma once
 #include <float.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace prism {
@@ -635,6 +637,53 @@ static __global__ void replay_store_rows_kernel(prism_replay_desc rp, int n, con
     }
 }
 
+// The same into a byte ring (PRISM_RING_U8): uint8 staging rows are copied (a 32-bit word per thread where `vec`:
+// obs_elems % 4 == 0 and every base 4- / 16-byte aligned, so that every word / float4 of a row is aligned), fp32 staging rows
+// narrowed (obs_narrow: a float that is not byte-exact is stored as 0 and raises PRISM_STATUS_OBS_INEXACT).
+template <int SRC>
+static __global__ void replay_store_rows_byte_ring_kernel(prism_replay_desc rp, int n, int vec, const int32_t *__restrict__ slots,
+                                                          const void *__restrict__ obs, const void *__restrict__ succ_obs,
+                                                          const float *__restrict__ reward, const int32_t *__restrict__ action,
+                                                          const uint8_t *__restrict__ flags) {
+    using src_t = typename std::conditional<SRC == PRISM_OBS_U8, uint8_t, float>::type;
+    const int O = rp.obs_elems;
+    bool inexact = false;
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        const int64_t s = slots[i];
+        uint8_t *d0 = reinterpret_cast<uint8_t *>(rp.obs) + s * O, *d1 = reinterpret_cast<uint8_t *>(rp.succ_obs) + s * O;
+        const src_t *s0 = static_cast<const src_t *>(obs) + (int64_t)i * O;
+        const src_t *s1 = static_cast<const src_t *>(succ_obs) + (int64_t)i * O;
+        if (vec) {
+            for (int k = threadIdx.x; k < O / 4; k += blockDim.x) {
+                if constexpr (SRC == PRISM_OBS_U8) {
+                    reinterpret_cast<uint32_t *>(d0)[k] = reinterpret_cast<const uint32_t *>(s0)[k];
+                    reinterpret_cast<uint32_t *>(d1)[k] = reinterpret_cast<const uint32_t *>(s1)[k];
+                } else {
+                    const float4 v0 = reinterpret_cast<const float4 *>(s0)[k], v1 = reinterpret_cast<const float4 *>(s1)[k];
+                    reinterpret_cast<uint32_t *>(d0)[k] = obs_narrow4(v0, inexact);
+                    reinterpret_cast<uint32_t *>(d1)[k] = obs_narrow4(v1, inexact);
+                }
+            }
+        } else {
+            for (int k = threadIdx.x; k < O; k += blockDim.x) {
+                if constexpr (SRC == PRISM_OBS_U8) {
+                    d0[k] = s0[k];
+                    d1[k] = s1[k];
+                } else {
+                    d0[k] = (uint8_t)obs_narrow(s0[k], inexact);
+                    d1[k] = (uint8_t)obs_narrow(s1[k], inexact);
+                }
+            }
+        }
+        if (threadIdx.x == 0) {
+            rp.reward[s] = reward[i];
+            rp.action[s] = action[i];
+            rp.flags[s] = flags[i];
+        }
+    }
+    if (inexact) atomicOr(rp.status, PRISM_STATUS_OBS_INEXACT);
+}
+
 // links + default priority.  The reference applies the rows one after the other; for a batch of
 // consecutive ring slots (what a writer cursor produces) whose predecessors are not overwritten later
 // in the same batch, three parallel phases give the same final state:
@@ -979,6 +1028,9 @@ static __global__ void uniform_sample_kernel(int64_t size, int batch, uint64_t s
 }
 
 // ---- n-step walk + row gather: one workgroup (128 lanes) per sampled slot ----------------------
+// RING: the storage kind of rp.obs / rp.succ_obs.  A byte ring's rows are widened on the way ((float)b, exact): a 32-bit
+// word per thread and trip where obs_elems % 4 == 0 (every row then starts on a word), a byte per thread otherwise.
+template <int RING>
 static __global__ __launch_bounds__(128) void replay_gather_kernel(prism_replay_desc rp, const int64_t *__restrict__ index,
                                                            int batch, float *__restrict__ out_obs,
                                                            float *__restrict__ out_next_obs,
@@ -994,20 +1046,38 @@ static __global__ __launch_bounds__(128) void replay_gather_kernel(prism_replay_
     const uint32_t fl = ns.flags;
     const double ret = ns.ret, gamma = ns.gamma;
     const int O = rp.obs_elems;
-    const float *src_obs = rp.obs + first * O;
-    const float *src_next = (fl & PRISM_FLAG_HAS_NEXT) ? rp.succ_obs + cur * O : src_obs;
     float *d0 = out_obs + (int64_t)b * O, *d1 = out_next_obs + (int64_t)b * O;
-    if ((O & 3) == 0) {
-        for (int k = threadIdx.x; k < O / 4; k += blockDim.x) {
-            const float4 a = reinterpret_cast<const float4 *>(src_obs)[k];
-            const float4 c = reinterpret_cast<const float4 *>(src_next)[k];
-            reinterpret_cast<float4 *>(d0)[k] = a;
-            reinterpret_cast<float4 *>(d1)[k] = c;
+    if constexpr (RING == PRISM_RING_F32) {
+        const float *src_obs = rp.obs + first * O;
+        const float *src_next = (fl & PRISM_FLAG_HAS_NEXT) ? rp.succ_obs + cur * O : src_obs;
+        if ((O & 3) == 0) {
+            for (int k = threadIdx.x; k < O / 4; k += blockDim.x) {
+                const float4 a = reinterpret_cast<const float4 *>(src_obs)[k];
+                const float4 c = reinterpret_cast<const float4 *>(src_next)[k];
+                reinterpret_cast<float4 *>(d0)[k] = a;
+                reinterpret_cast<float4 *>(d1)[k] = c;
+            }
+        } else {
+            for (int k = threadIdx.x; k < O; k += blockDim.x) {
+                d0[k] = src_obs[k];
+                d1[k] = src_next[k];
+            }
         }
     } else {
-        for (int k = threadIdx.x; k < O; k += blockDim.x) {
-            d0[k] = src_obs[k];
-            d1[k] = src_next[k];
+        const uint8_t *src_obs = reinterpret_cast<const uint8_t *>(rp.obs) + first * O;
+        const uint8_t *src_next = (fl & PRISM_FLAG_HAS_NEXT) ? reinterpret_cast<const uint8_t *>(rp.succ_obs) + cur * O : src_obs;
+        if ((O & 3) == 0) {
+            for (int k = threadIdx.x; k < O / 4; k += blockDim.x) {
+                const uint32_t a = reinterpret_cast<const uint32_t *>(src_obs)[k];
+                const uint32_t c = reinterpret_cast<const uint32_t *>(src_next)[k];
+                reinterpret_cast<float4 *>(d0)[k] = obs_widen4(a);
+                reinterpret_cast<float4 *>(d1)[k] = obs_widen4(c);
+            }
+        } else {
+            for (int k = threadIdx.x; k < O; k += blockDim.x) {
+                d0[k] = (float)src_obs[k];
+                d1[k] = (float)src_next[k];
+            }
         }
     }
     if (threadIdx.x == 0) {
@@ -1035,5 +1105,16 @@ static inline int check_ring(const prism_replay_desc *rp, bool need_tree) {
     PRISM_CHECK_ARG((reinterpret_cast<uintptr_t>(rp->tree) & 15) == 0, "tree must be 16-byte aligned");
     return PRISM_OK;
 }
+
+// host: the `ring_kind` argument of the prism_*_ring entry points (a macro: the message names the entry point called).
+// A byte ring's arrays must start on a 32-bit word: its rows are read and written a word at a time.
+#define PRISM_CHECK_RING_KIND(rp, ring_kind)                                                                           \
+    do {                                                                                                               \
+        PRISM_CHECK_ARG((ring_kind) == PRISM_RING_F32 || (ring_kind) == PRISM_RING_U8,                                 \
+                        "ring_kind must be PRISM_RING_F32 or PRISM_RING_U8");                                          \
+        PRISM_CHECK_ARG((ring_kind) != PRISM_RING_U8 ||                                                                \
+                            ((reinterpret_cast<uintptr_t>((rp)->obs) | reinterpret_cast<uintptr_t>((rp)->succ_obs)) & 3) == 0, \
+                        "a byte ring's obs / succ_obs must be 4-byte aligned");                                        \
+    } while (0)
 
 }  // namespace prism

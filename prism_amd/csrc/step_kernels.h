@@ -200,7 +200,35 @@ struct FrontArgs {
 // 256 threads: wave 0 samples, waves 1-3 stage the conv weights; the convolutions run on the matrix core, one 16-position
 // tile per wave (conv_embed_rows).  (An eight-wave form that convolved with fmaf chains beside the n-step walk was the
 // round-3 intermediate: the MFMA convolution is shorter on four waves than that one was on eight.)
-__global__ __launch_bounds__(256) void step_front_kernel(IqnArgs a, prism_replay_desc rp, FrontArgs f) {
+//
+// RING, the storage kind of rp.obs / rp.succ_obs, decides only how a thread's piece of an observation row -- four
+// elements, thread t < O / 4 -- is loaded: a float4 from an fp32 ring (the loaded registers ARE the values), one 32-bit
+// word from a byte ring (rows are 100 C bytes, so every word is aligned), widened to the same float4 once it has landed.
+// obs_to_lds, stream_store4 and the convolution see the float4 either way and keep their thread mapping.
+template <int RING>
+struct RowPiece {
+    typedef float4 raw;
+    static __device__ __forceinline__ raw zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+    static __device__ __forceinline__ raw load(const float *ring, int64_t row, int O, int t) {
+        return reinterpret_cast<const float4 *>(ring + row * O)[t];
+    }
+    static __device__ __forceinline__ float4 widen(const raw &r) { return r; }
+};
+template <>
+struct RowPiece<PRISM_RING_U8> {
+    typedef uint32_t raw;
+    static __device__ __forceinline__ raw zero() { return 0u; }
+    static __device__ __forceinline__ raw load(const float *ring, int64_t row, int O, int t) {
+        return reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(ring) + row * O)[t];
+    }
+    static __device__ __forceinline__ float4 widen(const raw &r) { return obs_widen4(r); }
+};
+
+// (the launch's body, shared by the two kernels below: tid and b are read in the kernels and handed down)
+template <int RING>
+__device__ __forceinline__ void step_front_body(const IqnArgs &a, const prism_replay_desc &rp, const FrontArgs &f, const int tid,
+                                                const int b) {
+    typedef RowPiece<RING> Row;
     kernarg_prefetch<sizeof(IqnArgs) + sizeof(prism_replay_desc) + sizeof(FrontArgs)>();
     __shared__ __attribute__((aligned(16))) float s_scratch[256];
     __shared__ __attribute__((aligned(16))) float s_obs[2][1000];
@@ -211,8 +239,7 @@ __global__ __launch_bounds__(256) void step_front_kernel(IqnArgs a, prism_replay
     __shared__ float s_out_w;
     __shared__ unsigned int s_rec_state, s_rec_state2;
     __shared__ uint32_t s_flags;
-    const int B = a.B, C = a.C, tid = threadIdx.x;
-    const int b = blockIdx.x;
+    const int B = a.B, C = a.C;
     if (b >= B) {
         PRISM_STAMP(27);
         front_extra_block(a, b - B, s_scratch);
@@ -303,10 +330,10 @@ __global__ __launch_bounds__(256) void step_front_kernel(IqnArgs a, prism_replay
     PRISM_STAMP2(2);
     const int O = rp.obs_elems;     // == 100 * C
     const int64_t idx0 = s_i64[0];
-    const float *src_obs = rp.obs + idx0 * O;
     float *d0 = f.obs + (int64_t)b * O, *d1 = f.next_obs + (int64_t)b * O;
     const int n_step = rp.n_step;
-    float4 xc = make_float4(0.f, 0.f, 0.f, 0.f), xs = xc;
+    typename Row::raw rc = Row::zero(), rs = rc;
+    float4 xc;
     float crw = 0.f;
     int32_t cnx = -1, act0 = 0;
     uint32_t cfl = 0;
@@ -318,7 +345,7 @@ __global__ __launch_bounds__(256) void step_front_kernel(IqnArgs a, prism_replay
     int64_t dlt = 0;
     double g_lane = 0.0;
     {
-        if (tid < O / 4) xc = reinterpret_cast<const float4 *>(src_obs)[tid];
+        if (tid < O / 4) rc = Row::load(rp.obs, idx0, O, tid);
         {   // gamma ** lane, read from the argument segment with a per-lane index (indexing the by-value struct at run time
             // would move it to scratch; one scalar load per hop put ~200 cycles into every step of the walk)
             typedef const double __attribute__((address_space(4))) *cdp;
@@ -334,13 +361,14 @@ __global__ __launch_bounds__(256) void step_front_kernel(IqnArgs a, prism_replay
         if (tid == 0) act0 = rp.action[idx0];
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         PRISM_STAMP2(3);
+        xc = Row::widen(rc);
         const bool go = (f0 & PRISM_FLAG_HAS_NEXT) && !(f0 & PRISM_FLAG_TRUNC) && n_step > 1 && nx0 >= 0;
         dlt = (int64_t)nx0 - idx0;
         pred = go ? idx0 + (int64_t)(n_step - 1) * dlt : idx0;
         pred_ok = pred >= 0 && pred < rp.capacity;
         if (tid < O / 4) {
             obs_to_lds(s_obs[0], xc, tid, C);
-            if (pred_ok) xs = reinterpret_cast<const float4 *>(rp.succ_obs + pred * O)[tid];
+            if (pred_ok) rs = Row::load(rp.succ_obs, pred, O, tid);
         }
         if (go && tid < n_step - 1) {                 // (wave 0: n_step <= PRISM_MAX_NSTEP < 64)
             const int64_t c = (int64_t)nx0 + (int64_t)tid * dlt;
@@ -413,12 +441,13 @@ __global__ __launch_bounds__(256) void step_front_kernel(IqnArgs a, prism_replay
         // the sibling record goes out from lanes that have nothing else to do (level s from lane 64 + s)
         reinterpret_cast<float2 *>(a.ws.sib)[(int64_t)(tid - 64) * B + b] = s_sibrec[tid - 64];
     }
+    float4 xs = Row::widen(rs);
     if (tid < O / 4) obs_to_lds(s_obs[1], xs, tid, C);
     PRISM_STAMP(30);
     lds_barrier();
     const unsigned int spec = __builtin_amdgcn_readfirstlane(s_rec_state2);
     if (spec != 1u) {
-        if (spec == 0u && tid < O / 4) xs = reinterpret_cast<const float4 *>(rp.succ_obs + s_i64[1] * O)[tid];
+        if (spec == 0u && tid < O / 4) xs = Row::widen(Row::load(rp.succ_obs, s_i64[1], O, tid));
         if (spec == 2u) xs = xc;
         if (tid < O / 4) obs_to_lds(s_obs[1], xs, tid, C);
         lds_barrier();
@@ -426,6 +455,15 @@ __global__ __launch_bounds__(256) void step_front_kernel(IqnArgs a, prism_replay
     if (tid < O / 4) stream_store4(reinterpret_cast<float4 *>(d1) + tid, xs);
     conv_embed_rows(s_obs[1], s_w[1], s_b[1], C, a.ws.e_next + (int64_t)b * E_DIM, tid);
     PRISM_STAMP(31);
+}
+
+__global__ __launch_bounds__(256) void step_front_kernel(IqnArgs a, prism_replay_desc rp, FrontArgs f) {
+    step_front_body<PRISM_RING_F32>(a, rp, f, threadIdx.x, blockIdx.x);
+}
+
+// the same launch sampling from a byte ring (prism_step_front_ring with PRISM_RING_U8)
+__global__ __launch_bounds__(256) void step_front_byte_ring_kernel(IqnArgs a, prism_replay_desc rp, FrontArgs f) {
+    step_front_body<PRISM_RING_U8>(a, rp, f, threadIdx.x, blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------

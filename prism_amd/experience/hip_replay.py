@@ -4,6 +4,7 @@ buffer it wraps (``prism/factory/exp_buffer_factory.py:22-33``).
 
 Data layout (all device memory, allocated once, sized for 288 GB of HBM3E):
     obs, succ_obs  fp32 [capacity, O]     reward fp32 [capacity]      action int32 [capacity]
+                   (``obs_storage="uint8"``: uint8 [capacity, O], a quarter of the bytes, for byte-exact observations)
     flags uint8 [capacity]                link/back int32 [capacity]
     tree fp32 [2 * tree_capacity][2]  ({sum, min} per node; sum_tree / min_tree are views)
 Python ``Timestep`` objects are consumed at ``extend()`` and not kept.  ``sample()`` runs two
@@ -92,6 +93,33 @@ class _Staging:
 
 
 _SMALL_INT = {True: (torch.bool, torch.uint8), False: (np.bool_, np.uint8)}       # observation dtypes stored as uint8
+# obs_storage -> (ring kind of the prism_*_ring entry points, dtype of obs / succ_obs)
+_OBS_STORAGE = {"float32": (N.RING_F32, torch.float32), "uint8": (N.RING_U8, torch.uint8)}
+
+
+def _as_u8(x):
+    return x.clamp(0, 255).to(torch.uint8)
+
+
+def _byte_exact(x):
+    """Every value of the float32 tensor is BYTE-EXACT -- the bit pattern of float(b) for a b in 0..255 (so not -0.0, NaN,
+    a fraction, a negative, above 255): a 0-d bool tensor, compared in bit space (common.h obs_narrow)."""
+    x = x.contiguous()
+    return (_as_u8(x).to(torch.float32).view(torch.int32) == x.view(torch.int32)).all()
+
+
+def _narrow_host(x, what):
+    """A host observation array as the bytes a uint8 ring stores; a value that is not byte-exact is a ValueError."""
+    x = np.asarray(x)
+    if x.dtype in _SMALL_INT[False]:
+        return x.astype(np.uint8, copy=False)
+    f = np.ascontiguousarray(x, dtype=np.float32)
+    with np.errstate(invalid="ignore"):
+        b = np.where((f >= 0) & (f <= 255), f, np.float32(0)).astype(np.uint8)
+    if not np.array_equal(b.astype(np.float32).view(np.uint32), f.view(np.uint32)):
+        raise ValueError(f"{what}: obs_storage='uint8' holds only byte-exact observations (+0.0, 1.0 .. 255.0); "
+                         "nothing was written")
+    return b
 
 
 def _is_dev(x):
@@ -149,7 +177,10 @@ class HipReplayBuffer:
     STAGE_ROWS = 1024
 
     def __init__(self, capacity, batch_size, device="cuda:0", frame_stack=1, n_step=3, gamma=0.99,
-                 use_per=True, alpha=0.5, beta=0.5, mass_rng="philox", seed=123, strict=False, reward_clipping_type=None):
+                 use_per=True, alpha=0.5, beta=0.5, mass_rng="philox", seed=123, strict=False, reward_clipping_type=None,
+                 obs_storage="float32"):
+        if obs_storage not in _OBS_STORAGE:
+            raise ValueError(f"obs_storage = {obs_storage!r} must be one of {sorted(_OBS_STORAGE)}")
         if frame_stack != 1:
             raise NotImplementedError("prism_amd replay: frame_stack_size > 1 is not implemented")
         if not str(device).startswith("cuda"):
@@ -167,6 +198,10 @@ class HipReplayBuffer:
         self.use_per = bool(use_per)
         self.mass_rng, self.seed, self.strict = mass_rng, int(seed), bool(strict)
         self.buffer = _RingShim(self, batch_size, alpha, beta)
+        # storage kind of obs / succ_obs: fp32 (the reference layout), or one byte per element for byte-exact observations
+        # (MinAtar's boolean planes): a uint8 ring fed them is bit for bit the fp32 ring at a quarter of the HBM
+        self.obs_storage = obs_storage
+        self._ring_kind, self._obs_dtype = _OBS_STORAGE[obs_storage]
         self._size = 0
         self._draws = 0            # Philox counters consumed by sample() (host-issued offsets)
         self._fused_draws = 0      # ... and by fused steps (device counter; mirrored here so the two never overlap)
@@ -203,8 +238,8 @@ class HipReplayBuffer:
         self._obs_shape = tuple(int(s) for s in obs_shape)
         O = int(np.prod(self._obs_shape))
         self.obs_elems = O
-        self.obs = torch.zeros(cap, O, dtype=torch.float32, device=dev)
-        self.succ_obs = torch.zeros(cap, O, dtype=torch.float32, device=dev)
+        self.obs = torch.zeros(cap, O, dtype=self._obs_dtype, device=dev)
+        self.succ_obs = torch.zeros(cap, O, dtype=self._obs_dtype, device=dev)
         self.reward = torch.zeros(cap, dtype=torch.float32, device=dev)
         self.action = torch.zeros(cap, dtype=torch.int32, device=dev)
         self.flags = torch.zeros(cap, dtype=torch.uint8, device=dev)
@@ -241,7 +276,7 @@ class HipReplayBuffer:
             w = lambda k: small[4 * S * k:4 * S * (k + 1)]
             return dict(small=small, slots=w(0).view(torch.int32), reward=w(1).view(torch.float32),
                         action=w(2).view(torch.int32), prev=w(3).view(torch.int32), flags=small[16 * S:],
-                        obs=torch.zeros(S, O, **kw), succ=torch.zeros(S, O, **kw))
+                        obs=torch.zeros(S, O, dtype=self._obs_dtype, **kw), succ=torch.zeros(S, O, dtype=self._obs_dtype, **kw))
 
         def _set():
             h, d = _blocks(pin_memory=True), _blocks(device=dev)
@@ -288,6 +323,12 @@ class HipReplayBuffer:
 
     def extend(self, timestep):
         """TimestepBuffer.extend (timestep_buffer.py:32-33): one completed timestep."""
+        rows = None
+        if self._ring_kind:                            # byte ring: an inexact observation is refused before anything changes
+            nxt = timestep.next
+            node = (nxt() if isinstance(nxt, weakref.ReferenceType) else nxt) if nxt is not None else None
+            rows = (_narrow_host(timestep.obs, "extend").reshape(-1),
+                    0 if node is None else _narrow_host(node.obs, "extend").reshape(-1))
         if self._desc is None:
             self._allocate(tuple(timestep.obs.shape))
         if self._n_staged == self.STAGE_ROWS:
@@ -314,11 +355,14 @@ class HipReplayBuffer:
 
         i, h = self._n_staged, self._hn
         h["slots"][i] = s
-        h["obs"][i] = np.asarray(timestep.obs, dtype=np.float32).reshape(-1)
-        if node is not None:
-            h["succ"][i] = np.asarray(node.obs, dtype=np.float32).reshape(-1)
+        if rows is not None:
+            h["obs"][i], h["succ"][i] = rows
         else:
-            h["succ"][i] = 0.0
+            h["obs"][i] = np.asarray(timestep.obs, dtype=np.float32).reshape(-1)
+            if node is not None:
+                h["succ"][i] = np.asarray(node.obs, dtype=np.float32).reshape(-1)
+            else:
+                h["succ"][i] = 0.0
         h["reward"][i] = timestep.reward
         h["action"][i] = timestep.action
         h["flags"][i] = flags
@@ -335,7 +379,12 @@ class HipReplayBuffer:
         d["small"].copy_(h["small"], non_blocking=True)
         d["obs"][:n].copy_(h["obs"][:n], non_blocking=True)
         d["succ"][:n].copy_(h["succ"][:n], non_blocking=True)
-        self._call("prism_replay_insert", n, *self._insert_args, smp._alpha, smp._eps, submit=self._row_stage)
+        if self._ring_kind:                            # (uint8 row staging, copied into the byte ring)
+            a = self._insert_args
+            self._call("prism_replay_insert_ring", self._ring_kind, n, *a[:3], N.OBS_U8, *a[3:], smp._alpha, smp._eps,
+                       submit=self._row_stage)
+        else:
+            self._call("prism_replay_insert", n, *self._insert_args, smp._alpha, smp._eps, submit=self._row_stage)
         self._bind_row_stage()         # the other set takes the next rows; it was submitted a whole batch ago
         self._n_staged = 0
 
@@ -497,6 +546,13 @@ class HipReplayBuffer:
         if not torch.is_tensor(next_obs):
             next_obs = np.asarray(next_obs)
         kind = _obs_kind(obs, next_obs)
+        if self._ring_kind and kind == N.OBS_F32:
+            # floats into a byte ring: what the host can see is checked here (and, where both arrays are the host's, sent
+            # as the bytes themselves); a device tensor is narrowed by the kernel, which can only raise the status bit
+            on_host = [not _is_dev(x) for x in (obs, next_obs)]
+            as_bytes = [_narrow_host(_host(x), "extend_batch") if h else x for x, h in zip((obs, next_obs), on_host)]
+            if all(on_host):
+                (obs, next_obs), kind = as_bytes, N.OBS_U8
         ids_host, need = _check_stream_ids(stream_ids, n, 0 if self._stream_tab is None else self._stream_tab.numel())
         if self._desc is None:
             self._allocate(tuple(obs.shape[1:]))
@@ -525,7 +581,10 @@ class HipReplayBuffer:
             if self._ep_desc is None:
                 self._bind_episode_desc()
             name, tail = "prism_replay_ingest_tracked", (self._ep_desc_ref,)
-        self._call(name, n, first, serial, N.ptr(dev["obs"]), N.ptr(dev["next"]), kind,
+        head = ()
+        if self._ring_kind:                            # one entry point for both launches: the descriptor, or NULL
+            name, head, tail = "prism_replay_ingest_ring", (self._ring_kind,), tail or (None,)
+        self._call(name, *head, n, first, serial, N.ptr(dev["obs"]), N.ptr(dev["next"]), kind,
                    N.ptr(dev["reward"]), N.ptr(dev["action"]), N.ptr(dev["done"]), N.ptr(dev["trunc"]), N.ptr(dev["ids"]),
                    N.ptr(tab), tab.numel(), smp._alpha, smp._eps, *tail, submit=self._ing if staged else None)
         # host mirrors, by arithmetic; the slots get ids from a private (negative) range: no Timestep id matches them
@@ -580,7 +639,8 @@ class HipReplayBuffer:
 
     def _gather_into_batch(self, B):
         """n-step walk + row gather of the slots in ``_index`` into the static batch."""
-        self._call("prism_replay_gather", N.ptr(self._index), B, N.ptr(self._obs), N.ptr(self._next_obs),
+        name, head = ("prism_replay_gather_ring", (self._ring_kind,)) if self._ring_kind else ("prism_replay_gather", ())
+        self._call(name, *head, N.ptr(self._index), B, N.ptr(self._obs), N.ptr(self._next_obs),
                    N.ptr(self._reward), N.ptr(self._nonterminal), N.ptr(self._gamma), N.ptr(self._action))
 
     @torch.no_grad()
@@ -601,6 +661,9 @@ class HipReplayBuffer:
         if bits & N.STATUS_INGEST_DUP_STREAM:
             raise RuntimeError("extend_batch: a device-side stream_ids array held a repeated or out-of-range id "
                                "(its rows were stored unlinked)")
+        if bits & N.STATUS_OBS_INEXACT:
+            raise RuntimeError("extend_batch: a device-side float observation was not byte-exact (+0.0, 1.0 .. 255.0); "
+                               "obs_storage='uint8' stored it as 0")
 
     def update_priority(self, indices, priorities, take_abs=False):
         if not self.use_per:
@@ -663,6 +726,27 @@ class HipReplayBuffer:
             self.tree[tc:tc + ns].copy_(p if p.dim() == 2 else p.unsqueeze(1))
             self._call("prism_per_rebuild")
 
+    def _ring_rows(self, what, *arrays):
+        """Observation arrays (host or device, bool / uint8 or floating point) as tensors a bulk install copies into the ring.
+        A byte ring takes small-int arrays as they are and floats narrowed, after ONE reduction over all of them (one sync):
+        a value that is not byte-exact is a ValueError, raised before the caller has touched the ring."""
+        ts = [torch.as_tensor(x) for x in arrays]
+        if not self._ring_kind:
+            return ts
+        out, ok = [], None
+        for t in ts:
+            if t.dtype in _SMALL_INT[True]:
+                out.append(t.to(torch.uint8))
+                continue
+            t = t.to(torch.float32)
+            e = _byte_exact(t).to(self.device)
+            ok = e if ok is None else ok & e
+            out.append(_as_u8(t))
+        if ok is not None and not bool(ok.item()):
+            raise ValueError(f"{what}: obs_storage='uint8' holds only byte-exact observations (+0.0, 1.0 .. 255.0); "
+                             "nothing was written")
+        return out
+
     def load_arrays(self, obs, succ_obs, reward, action, flags, link, priorities=None, n_sampleable=None, cursor=None,
                     slot_ids=None):
         """Replace the buffer's contents by n rows from device/host arrays, with the trees rebuilt from the given leaf
@@ -671,10 +755,11 @@ class HipReplayBuffer:
         ``slot_ids``: where the writer goes on and the rows' Timestep ids, when a saved directory holds them (``_seal``).
         Nothing of what the buffer held before survives: the result is that of loading into a fresh buffer."""
         n = int(obs.shape[0])
+        obs, succ_obs = self._ring_rows("load_arrays", obs, succ_obs)
         self._allocate(tuple(obs.shape[1:]))
         O = self.obs_elems
-        self.obs[:n].copy_(torch.as_tensor(obs).reshape(n, O))
-        self.succ_obs[:n].copy_(torch.as_tensor(succ_obs).reshape(n, O))
+        self.obs[:n].copy_(obs.reshape(n, O))
+        self.succ_obs[:n].copy_(succ_obs.reshape(n, O))
         self.reward[:n].copy_(torch.as_tensor(reward))
         self.action[:n].copy_(torch.as_tensor(action))
         self.flags[:n].copy_(torch.as_tensor(flags))
@@ -690,7 +775,8 @@ class HipReplayBuffer:
         d = os.path.join(path, "experience_buffer")
         os.makedirs(d, exist_ok=True)
         n = self._size
-        flat = ref_format.serialize_ring(self.obs[:n].cpu().numpy(), self.succ_obs[:n].cpu().numpy(),
+        # (a byte ring widens: the file is byte for byte what the fp32 ring holding the same rows writes)
+        flat = ref_format.serialize_ring(self.obs[:n].cpu().float().numpy(), self.succ_obs[:n].cpu().float().numpy(),
                                          self.reward[:n].cpu().numpy(), self.action[:n].cpu().numpy(),
                                          self.flags[:n].cpu().numpy(), self.link[:n].cpu().numpy(),
                                          self.back[:n].cpu().numpy(), self._slot_id[:n], self._obs_shape)
@@ -754,10 +840,9 @@ class HipReplayBuffer:
         rows, n = self._valid_rows(), self._size
         obs, succ = self.obs[:rows], self.succ_obs[:rows]
         # exact as uint8? compared in bit space (-0.0 is not 0), both arrays in one reduction, one D2H sync
-        as_u8 = lambda x: x.clamp(0, 255).to(torch.uint8)
-        exact = lambda x: (as_u8(x).to(torch.float32).view(torch.int32) == x.view(torch.int32)).all()
-        small = rows > 0 and bool((exact(obs) & exact(succ)).item())
-        pack = (lambda x: as_u8(x).cpu()) if small else (lambda x: x.cpu())
+        # (a byte ring is that by construction: no scan)
+        small = rows > 0 and (bool(self._ring_kind) or bool((_byte_exact(obs) & _byte_exact(succ)).item()))
+        pack = (lambda x: _as_u8(x).cpu()) if small and not self._ring_kind else (lambda x: x.cpu())
         smp = self.buffer._sampler
         part = dict(rows=rows, size=n, obs_shape=list(self._obs_shape), cursor=int(self.buffer._writer._cursor),
                     serial=int(self._serial),
@@ -780,10 +865,12 @@ class HipReplayBuffer:
 
     def _restore_part(self, part, keep_streams=True):
         rows, dev = int(part["rows"]), self.device
+        # (a byte ring refuses an fp32 snapshot that holds a value it cannot store -- here, before anything is touched)
+        src = dict(zip(("obs", "succ_obs"), self._ring_rows("load_state", part["obs"], part["succ_obs"])))
         self._allocate(tuple(int(s) for s in part["obs_shape"]))
         O = self.obs_elems
         for name in ("obs", "succ_obs"):
-            getattr(self, name)[:rows].copy_(part[name].to(dev).reshape(rows, O))          # (uint8 widens here)
+            getattr(self, name)[:rows].copy_(src[name].to(dev).reshape(rows, O))           # (uint8 into fp32 widens here)
         for name in ("reward", "action", "flags", "link"):
             getattr(self, name)[:rows].copy_(part[name].to(dev))
         self._seal(rows, part["size"], part["cursor"], part.get("leaves"), part["back"].to(dev), part["slot_id"].numpy())
@@ -838,7 +925,9 @@ class HipReplayBuffer:
         """Restore a ``save_state`` snapshot into a freshly constructed buffer of the same configuration: what follows is
         bit-identical to the run that wrote it.  ``keep_streams=False`` closes every open chain (a collector that restarts
         its environments): the first row of every stream is then stored unlinked.  A snapshot of another capacity,
-        observation shape, ``n_step``, gammas, ``use_per`` or ``mass_rng`` is refused before anything is touched."""
+        observation shape, ``n_step``, gammas, ``use_per`` or ``mass_rng`` is refused before anything is touched.  ``obs_storage``
+        is not part of that record: snapshots interchange between the two kinds whenever the observations are byte-exact
+        (a uint8 ring refuses any other, also before anything is touched)."""
         from prism_amd.util import snapshot
         self._check_snapshot(snapshot.read_manifest(path))
         parts, _ = snapshot.read_snapshot(path, ["replay"])

@@ -13,4 +13,5 @@ def build_exp_buffer(config, capacity=None):
                            alpha=config.per_alpha, beta=config.per_beta_start,
                            mass_rng=getattr(config, "per_mass_rng", "philox"), seed=config.seed,
                            strict=getattr(config, "per_strict", False),
-                           reward_clipping_type=getattr(config, "reward_clipping_type", None))
+                           reward_clipping_type=getattr(config, "reward_clipping_type", None),
+                           obs_storage=getattr(config, "replay_obs_storage", "float32"))

@@ -1,5 +1,5 @@
 """Synthetic MinAtar-shaped replay contents for benchmarks and smoke tests:
-binary observations ~ Bernoulli(0.1) stored fp32 (reference layout), per-step rewards ~ N(0,1),
+binary observations ~ Bernoulli(0.1) stored fp32 (reference layout; as bytes in a uint8 ring), per-step rewards ~ N(0,1),
 episode ends so that ~5 % of 3-step bootstraps are terminal, actions ~ U{0..A-1}, initial
 priorities |N(0,1)|**alpha + 1e-8.  Transitions form linked chains (slot i -> i + n_streams) as
 interleaved env streams would (experience_collector.py:94-120), so the gather kernel really walks
@@ -23,12 +23,12 @@ def fill_replay(buffer, n, obs_shape=(10, 10, 4), n_actions=6, seed=0, n_streams
     flags = (done.to(torch.uint8) * 1 + has_next.to(torch.uint8) * 4)
     for s in range(0, n, chunk):
         e = min(n, s + chunk)
-        buffer.obs[s:e] = (torch.rand(e - s, O, device=dev, generator=gen) < 0.1).float()
+        buffer.obs[s:e] = (torch.rand(e - s, O, device=dev, generator=gen) < 0.1).to(buffer.obs.dtype)
     # successor observation = the linked row's observation (random where the chain is still open)
     for s in range(0, n, chunk):
         e = min(n, s + chunk)
         lk = link[s:e]
-        rnd = (torch.rand(e - s, O, device=dev, generator=gen) < 0.1).float()
+        rnd = (torch.rand(e - s, O, device=dev, generator=gen) < 0.1).to(buffer.obs.dtype)
         src = buffer.obs[lk.clamp(min=0)]
         buffer.succ_obs[s:e] = torch.where((lk >= 0).unsqueeze(1), src, rnd)
     buffer.reward[:n] = torch.randn(n, device=dev, generator=gen)
