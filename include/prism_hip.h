@@ -553,6 +553,38 @@ int prism_greedy_select(const float *z, const float *q, int32_t n, int32_t n_pad
                         int32_t n_heads, int64_t *out_action, float *out_mean, int64_t *out_action_host,
                         prism_stream_t stream);
 
+/* MinRegretActionSelector.generate_action_probs + select_action (prism/agents/action_selectors.py:85-111): act on the
+ * ensemble's pessimistic bound.  q: the [n_heads][n_pad][A] ensemble estimates prism_act_forward left in out_q, the only
+ * input; rows n .. n_pad - 1 are never read.  Per observation and action, fp32, sums in head order, unsquish_fn
+ * (PRISM_SQUISH_*, :93-94) applied to every estimate first:
+ *   mean   = (q_0 + ... + q_(H-1)) / H                        spread = sqrt(sum_h (q_h - mean)^2 / (H - 1))   (:96-97,
+ *            torch.std, unbiased; "variance" there)           sd     = sqrt(spread)                            (:99)
+ *   regret = max_a(mean + lmbda * sd) - (mean - lmbda * sd)   score  = regret^2                               (:101-103)
+ *   action = first arg-min of the scores                                                                      (:104)
+ * mean and spread are prism_ids_select's, bit for bit.  n_heads 2..16: one head has no spread (NaN in the reference).
+ * out_scores (optional) [n][A]: regret^2; out_aux (optional) [n][2][A]: mean | spread; out_action [n]; out_action_host as
+ * for prism_ids_select. */
+int prism_min_regret_select(const float *q, int32_t n, int32_t n_pad, int32_t n_actions, int32_t n_heads, float lmbda,
+                            int32_t unsquish_fn, float *out_scores, float *out_aux, int64_t *out_action,
+                            int64_t *out_action_host, prism_stream_t stream);
+
+/* SimpleIDSActionSelector.generate_action_probs + select_action for random_sample = False
+ * (prism/agents/action_selectors.py:195-286), q_estimates read as the class is written: a sequence over heads of [n, A]
+ * estimates.  q as for prism_min_regret_select.  Per observation and action, fp32, unsquish_fn applied to every estimate
+ * first (:215-216):
+ *   mean     = (q_0 + ... + q_(H-1)) / H, summed in head order                                                (:213-218)
+ *   max_diff = max_h q_h - min_h q_h: the reference's max over pairs i < j of |q_i - q_j| (:226-230) exactly, fp32
+ *              rounding being monotone; 0 with one head
+ *   q_values = mean - (mean_0 + ... + mean_(A-1)) / A, summed in action order                                 (:247)
+ *   scaled   = (float)(1 - beta) * max_diff + q_values * (float)beta, 1 - beta formed in double               (:250)
+ *   action   = first arg-max of the scaled values                                                             (:252)
+ * The quantile_difference of :244-245 is computed there and never used: not here.  n_heads 1..16.
+ * out_scores (optional) [n][A]: scaled; out_aux (optional) [n][3][A]: mean | max_diff | q_values; out_action [n];
+ * out_action_host as for prism_ids_select. */
+int prism_simple_ids_select(const float *q, int32_t n, int32_t n_pad, int32_t n_actions, int32_t n_heads, double beta,
+                            int32_t unsquish_fn, float *out_scores, float *out_aux, int64_t *out_action,
+                            int64_t *out_action_host, prism_stream_t stream);
+
 /* EGreedyActionSelector (prism/agents/action_selectors.py:24-45) with the coin tossed PER OBSERVATION: the reference (and
  * the agent's default) tosses one coin for the whole call, which makes N lock-stepped environments explore together or not
  * at all.  Row b of this launch is row row0 + b of a call of n_call rows (row0 = 0, n_call = n: the whole call in one

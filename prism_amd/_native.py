@@ -149,6 +149,9 @@ SIGNATURES = {
     "prism_greedy_select": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "prism_egreedy_select": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_double, ctypes.c_double,
                                             c_i64, c_u64, c_u64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "prism_min_regret_select": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "prism_simple_ids_select": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.c_double, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                               c_vp]),
     "prism_sync_target": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp]),
     "prism_direct_reduce_scatter": (ctypes.c_int, [_P(DirectDesc), c_i32, c_vp]),
     "prism_direct_all_gather": (ctypes.c_int, [_P(DirectDesc), c_i32, c_vp]),

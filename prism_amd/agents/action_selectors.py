@@ -1,6 +1,7 @@
 """Acting-time action selection (OUT of the HIP hot path; plain torch on whatever device the model
 lives on).  Behaviour follows ``/root/reference/prism/agents/action_selectors.py``: greedy
-(:70-83), epsilon-greedy with linear anneal (:24-67) and information-directed sampling (:114-192).
+(:70-83), epsilon-greedy with linear anneal (:24-67), minimum regret (:85-111), information-directed sampling (:114-192)
+and its simple form (:195-286).
 Kept only so ``Agent.forward`` / checkpoints keep working when the learner is swapped in.
 """
 import numpy as np
@@ -131,4 +132,72 @@ class IDSActionSelector(ActionSelector):
         self.generate_action_probs(action_value_distribution, q_estimates, for_log=True)
         for key, value in self.loggables.items():
             logger.log_data(data=[[round(x, 4) for x in row] for row in value.tolist()], group_name="Debug/IDS",
+                            var_name=key)
+
+
+class MinRegretActionSelector(ActionSelector):
+    """action_selectors.py:85-111: the action whose regret against the ensemble's optimistic bound is least -- the regret
+    half of the IDS score.  Needs two heads or more: one head has no spread (NaN in the reference)."""
+
+    def __init__(self, lmbda, unsquish_function=None):
+        super().__init__()
+        self.lmbda, self.unsquish_function = lmbda, unsquish_function
+
+    def regret_squared(self, q_estimates):
+        if q_estimates.shape[-1] < 2:
+            raise ValueError("MinRegretActionSelector needs an ensemble of two heads or more")
+        if self.unsquish_function is not None:
+            q_estimates = self.unsquish_function(q_estimates)
+        mean, spread = q_estimates.mean(dim=-1), q_estimates.std(dim=-1)
+        sd = spread.sqrt()
+        upper = (mean + self.lmbda * sd).max(dim=-1).values.view(-1, 1)
+        regret = upper - (mean - self.lmbda * sd)
+        return regret.square()
+
+    def generate_action_probs(self, action_value_distribution, q_estimates):
+        regret_sq = self.regret_squared(q_estimates)
+        return torch.nn.functional.one_hot(regret_sq.argmin(dim=-1), regret_sq.shape[-1])
+
+
+class SimpleIDSActionSelector(ActionSelector):
+    """action_selectors.py:195-286: (1 - beta) * the widest gap between two heads + beta * the centred ensemble mean,
+    arg-max.  ``q_estimates``: the reference's sequence over heads of ``[n, A]`` estimates, or the ``(n, A, heads)``
+    tensor ``act_estimates`` returns (unbound along its last axis); never written to.  ``random_sample`` is kept as an
+    attribute and refused where it would be used: the reference's own sampled branch raises."""
+
+    def __init__(self, lmbda, random_sample, epsilon, ids_rho_lower_bound, beta, unsquish_function=None):
+        super().__init__()
+        self.lmbda, self.random_sample, self.epsilon = lmbda, random_sample, epsilon
+        self.ids_rho_lower_bound, self.beta, self.unsquish_function = ids_rho_lower_bound, beta, unsquish_function
+        self.softmax = torch.nn.Softmax(dim=-1)
+
+    def generate_action_probs(self, action_value_distribution, q_estimates, for_log=False):
+        heads = list(q_estimates.unbind(dim=-1)) if torch.is_tensor(q_estimates) else list(q_estimates)
+        if self.unsquish_function is not None:
+            heads = [self.unsquish_function(q) for q in heads]
+        mean = torch.zeros_like(heads[0])
+        for q in heads:
+            mean = mean + q
+        mean = mean / len(heads)
+        max_diff = torch.zeros_like(mean)
+        for i in range(len(heads)):
+            for j in range(i + 1, len(heads)):
+                max_diff = torch.max(max_diff, (heads[i] - heads[j]).abs())
+        q_values = mean - mean.mean(dim=-1).view(-1, 1)
+        scaled = (1 - self.beta) * max_diff + q_values * self.beta
+        probs = torch.nn.functional.one_hot(scaled.argmax(dim=-1), scaled.shape[-1])
+        if for_log:
+            self.loggables = {"Q Estimate Max Difference": max_diff, "Q Estimate Ensemble Mean": mean,
+                              "Action Uncertainty": max_diff, "Scaled Q Values": scaled, "Action Probs": probs}
+        return probs
+
+    def select_action(self, action_probs):
+        if self.random_sample:
+            raise ValueError("SimpleIDSActionSelector has no sampled form (the reference's raises in torch.multinomial)")
+        return action_probs.argmax(dim=-1).long().view(-1)
+
+    def log(self, logger, action_value_distribution, q_estimates):
+        self.generate_action_probs(action_value_distribution, q_estimates, for_log=True)
+        for key, value in self.loggables.items():
+            logger.log_data(data=[[round(x, 4) for x in row] for row in value.tolist()], group_name="Debug/SimpleIDS",
                             var_name=key)

@@ -737,16 +737,21 @@ class HipAgent:
         finally:
             d.rng_counters, d.act_flags = keep
 
+    _SCORED = ("ids", "ids_sampled", "min_regret", "simple_ids")          # selector kernels that leave (n, A) scores behind
+
     def _selector_key(self, sel):
         """The selector's native kernel and constants: ``("ids", lmbda, epsilon, rho_lower_bound, unsquish id)``,
         ``("ids_sampled", ...)`` with the same constants for ``ids_use_random_samples`` (the action is a Philox draw of the
         agent's seed: only where the quantile draws are, ``tau_rng == "philox"``), ``("greedy",)``,
+        ``("min_regret", lmbda, unsquish id)`` and ``("simple_ids", beta, unsquish id)`` for the two selectors that read the
+        ensemble alone (``prism_min_regret_select`` / ``prism_simple_ids_select``; a model with Q heads),
         ``("egreedy", start, stop, max_steps)`` for epsilon-greedy per observation (``e_greedy_per_env``; ``forward`` hands
         the selector over only in that mode, else its ``greedy`` member), or None for what has
         none (sampled IDS in parity mode -- ``torch.multinomial`` on torch's generator --, an unsquish function the kernel
         does not know, IDS on a model without both estimate arrays, any other selector): the selector's torch code on the
         eager estimates."""
-        from prism_amd.agents.action_selectors import EGreedyActionSelector, GreedyActionSelector, IDSActionSelector
+        from prism_amd.agents.action_selectors import (EGreedyActionSelector, GreedyActionSelector, IDSActionSelector,
+                                                       MinRegretActionSelector, SimpleIDSActionSelector)
         if type(sel) is EGreedyActionSelector and self.e_greedy_per_env:
             e = sel.epsilon
             if int(e.max_steps) != e.max_steps or e.max_steps < 0 or e.current_step < 0:
@@ -759,12 +764,21 @@ class HipAgent:
                 return None
             return ("ids_sampled" if sel.random_sample else "ids", float(sel.lmbda), float(sel.epsilon),
                     float(sel.ids_rho_lower_bound), usq)
+        if type(sel) in (MinRegretActionSelector, SimpleIDSActionSelector):
+            from prism_amd.agents.squish_functions import unsquish_id
+            usq = unsquish_id(sel.unsquish_function)
+            if usq is None or not self._act_q or self.dims.n_heads > 16:
+                return None
+            if type(sel) is MinRegretActionSelector:
+                return None if self.dims.n_heads < 2 else ("min_regret", float(sel.lmbda), usq)
+            return None if sel.random_sample else ("simple_ids", float(sel.beta), usq)
         return ("greedy",) if type(sel) is GreedyActionSelector else None
 
     def _select_launch(self, skey, z, qb, n, n_pad, T, act, host_act, scores, draw_offset=0, rng_counters=None,
                        eg_rows=None, eg_word=None):
         """The selector kernel of ``skey`` (_selector_key) on the current stream: actions to ``act`` (device) and, where
-        given, to ``host_act`` (pinned host); ``scores``: the ``(n, A)`` information ratios IDS leaves behind.  Sampled
+        given, to ``host_act`` (pinned host); ``scores``: the ``(n, A)`` information ratios IDS leaves behind (MinRegret: the
+        squared regrets, SimpleIDS: the scaled values).  Sampled
         IDS draws observation b at Philox counter c0 + b, c0 the acting count at the START of this call's forward: the
         eager call hands it over (``draw_offset``), the graph path binds ``rng_counters``, whose word [2] the forward in
         front of this launch has advanced by n * T (the kernel takes that off again).  Epsilon-greedy per observation
@@ -777,6 +791,16 @@ class HipAgent:
             N.check(L.prism_egreedy_select(N.ptr(z), N.ptr(qb), n, n_pad, T, dm.n_actions, dm.n_heads, skey[1], skey[2], skey[3],
                                            self.seed, s0, row0, n_call, eg_word, None, None, None, None, N.ptr(act),
                                            N.ptr(host_act), N.current_stream_handle()), "prism_egreedy_select")
+            return
+        if skey[0] == "min_regret":
+            N.check(L.prism_min_regret_select(N.ptr(qb), n, n_pad, dm.n_actions, dm.n_heads, skey[1], skey[2], N.ptr(scores),
+                                              None, N.ptr(act), N.ptr(host_act), N.current_stream_handle()),
+                    "prism_min_regret_select")
+            return
+        if skey[0] == "simple_ids":
+            N.check(L.prism_simple_ids_select(N.ptr(qb), n, n_pad, dm.n_actions, dm.n_heads, skey[1], skey[2], N.ptr(scores),
+                                              None, N.ptr(act), N.ptr(host_act), N.current_stream_handle()),
+                    "prism_simple_ids_select")
             return
         if skey[0] == "ids_sampled":
             N.check(L.prism_ids_sample_select(N.ptr(z), N.ptr(qb), n, n_pad, T, dm.n_actions, dm.n_heads, skey[1], skey[2],
@@ -831,7 +855,9 @@ class HipAgent:
 
     @torch.no_grad()
     def forward(self, obs):
-        """Agent.forward (agent.py:31-41).  Information-directed sampling, deterministic (``prism_ids_select``) and sampled
+        """Agent.forward (agent.py:31-41).  Minimum-regret and simple-IDS selection on the ensemble
+        (``prism_min_regret_select``, ``prism_simple_ids_select``), information-directed sampling, deterministic
+        (``prism_ids_select``) and sampled
         (``ids_use_random_samples``: ``prism_ids_sample_select``, the action a Philox draw of the agent's seed on its own
         stream key), greedy and epsilon-greedy selection (``prism_greedy_select``; the coin and the random actions come from
         the selector's host generator exactly as in action_selectors.py:35-45; with ``config.e_greedy_per_env`` every
@@ -912,7 +938,7 @@ class HipAgent:
             st = dict(T=T, n_pad=n_pad, z=z, qb=qb, calls=0, g=None,
                       pin_in=[torch.zeros(shape, dtype=torch.float32).pin_memory() for _ in range(4)] if on_host else None,
                       obs=obs_in if mode == "ptr" else (None if on_host else torch.empty(shape, dtype=torch.float32, device=dev)),
-                      scores=torch.empty((n, dm.n_actions), device=dev) if skey[0] in ("ids", "ids_sampled") else None,
+                      scores=torch.empty((n, dm.n_actions), device=dev) if skey[0] in self._SCORED else None,
                       act=[torch.empty(n, dtype=torch.int64, device=dev) for _ in range(4)],
                       pin_out=[torch.zeros(n, dtype=torch.int64).pin_memory() for _ in range(4)],
                       ev=[torch.cuda.Event() for _ in range(4)])
@@ -984,7 +1010,7 @@ class HipAgent:
             return sel.select_action(sel.generate_action_probs(dist, q))
         z, qb, n, n_pad, T = self._act_raw
         action = torch.empty(n, dtype=torch.int64, device=self.device)
-        scores = torch.empty((n, self.dims.n_actions), device=self.device) if skey[0] in ("ids", "ids_sampled") else None
+        scores = torch.empty((n, self.dims.n_actions), device=self.device) if skey[0] in self._SCORED else None
         with torch.cuda.device(self.device):
             self._select_launch(skey, z, qb, n, n_pad, T, action, None, scores, draw_offset=c0,
                                 eg_rows=(int(sel.epsilon.current_step), row0, n_call) if skey[0] == "egreedy" else None)

@@ -17,6 +17,13 @@ constructing unchanged); they are read with ``getattr(config, name, default)``:
     e_greedy_per_env  bool, epsilon-greedy tosses one coin per observation, on the device (Philox,
                       inside the acting hipGraph), instead of the reference's one host coin per
                       Agent.forward call (default False); for vector collectors under use_e_greedy
+    ids_action_selector
+                      "ids" (default, IDSActionSelector) | "simple_ids": under use_ids the training selector is the
+                      reference's SimpleIDSActionSelector, the one consumer of ids_beta; deterministic only
+                      (ids_use_random_samples must be off)
+    eval_action_selector
+                      "greedy" (default) | "min_regret": under use_ids the evaluation selector is the reference's
+                      MinRegretActionSelector(ids_lambda, unsquish) -- the ensemble's pessimistic bound, not its mean
     replay_obs_storage
                       "float32" (default, the reference layout) | "uint8": the replay ring keeps its two
                       observation arrays as one byte per element -- a quarter of the HBM -- for byte-exact

@@ -13,7 +13,8 @@ import pickle
 
 _OURS = "prism_amd.agents.action_selectors"
 _MAP = {("prism.agents.action_selectors", n): (_OURS, n)
-        for n in ("ActionSelector", "GreedyActionSelector", "EGreedyActionSelector", "IDSActionSelector")}
+        for n in ("ActionSelector", "GreedyActionSelector", "EGreedyActionSelector", "IDSActionSelector",
+                  "MinRegretActionSelector", "SimpleIDSActionSelector")}
 _MAP[("prism.util.annealing_strategies", "LinearAnneal")] = (_OURS, "LinearAnneal")
 # the IDS selector keeps its unsquish FUNCTION (action_selectors.py:123): pickled by module path like a class
 _SQ = "prism_amd.agents.squish_functions"
@@ -23,7 +24,7 @@ for _n in _SQ_NAMES:
 
 
 # What a ``state.pkl`` legitimately names besides the selector classes: the NumPy generator of the epsilon-greedy
-# selector (action_selectors.py:33), the ``torch.nn.Softmax`` of the IDS selector (:123) and the containers pickle itself
+# selector (action_selectors.py:33), the ``torch.nn.Softmax`` of the IDS selectors (:122, :203) and the containers pickle itself
 # uses.  Anything else is refused: a checkpoint directory is data, not code.
 _ALLOWED = {
     ("builtins", "set"), ("__builtin__", "set"), ("builtins", "frozenset"), ("builtins", "object"), ("__builtin__", "object"),
@@ -40,7 +41,8 @@ _ALLOWED = {
     # tensors a selector kept for logging (IDSActionSelector.loggables, action_selectors.py:178-192) travel as a nested
     # torch.save blob: the outer rebuild function is harmless, the blob is opened with weights_only (_safe_storage)
     ("torch._utils", "_rebuild_tensor_v2"),
-} | {(_OURS, n) for n in ("ActionSelector", "GreedyActionSelector", "EGreedyActionSelector", "IDSActionSelector", "LinearAnneal")} \
+} | {(_OURS, n) for n in ("ActionSelector", "GreedyActionSelector", "EGreedyActionSelector", "IDSActionSelector",
+                          "MinRegretActionSelector", "SimpleIDSActionSelector", "LinearAnneal")} \
   | {(_SQ, n) for n in _SQ_NAMES}
 
 

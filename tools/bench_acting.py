@@ -7,6 +7,9 @@ host -> actions on the host, per call, for the hipGraph form (default) and the e
 --rows egreedy  the DQN configuration configs[1], hipGraph form: the greedy selector (use_e_greedy off) before and after the
                 per-observation epsilon-greedy mode (e_greedy_per_env; epsilon pinned to 0 and to 1: every row greedy, every
                 row a random action) -- the two greedy rows give the run-to-run spread of one visit
+--rows eval     the ten-head IDS configuration in eval mode (agent.eval()), hipGraph form: the greedy evaluation selector,
+                the MinRegret one (eval_action_selector = "min_regret"; skipped with --no-min-regret, for a tree without it)
+                and greedy again -- the two greedy rows give the run-to-run spread of one visit
 --sizes 1,16    observation counts;  --reps 300   calls per median;  --tag NAME   prefix of every printed row (two trees
                 measured alternately in one visit)"""
 import argparse, contextlib, io, json, os, sys, time
@@ -16,12 +19,14 @@ from prism_amd.config import baseline_config
 from prism_amd.learner import Learner
 
 
-def measure(cfg_i, graph, reps=400, sizes=(1, 4, 16), **over):
+def measure(cfg_i, graph, reps=400, sizes=(1, 4, 16), eval_mode=False, **over):
     cfg = baseline_config(cfg_i, device="cuda:0", log_to_wandb=False, act_graph=graph, **over)
     ln = Learner()
     with contextlib.redirect_stdout(io.StringIO()):
         ln.configure(cfg, obs_shape=(10, 10, 4), n_actions=6)
     ag = ln.agent
+    if eval_mode:
+        ag.eval()
     rng = np.random.default_rng(0)
     out = {}
     for n in sizes:
@@ -48,7 +53,8 @@ def measure(cfg_i, graph, reps=400, sizes=(1, 4, 16), **over):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", default="all", choices=["all", "ids", "egreedy"])
+    ap.add_argument("--rows", default="all", choices=["all", "ids", "egreedy", "eval"])
+    ap.add_argument("--no-min-regret", action="store_true")
     ap.add_argument("--sizes", default="1,4,16")
     ap.add_argument("--reps", type=int, default=400)
     ap.add_argument("--tag", default="")
@@ -66,11 +72,16 @@ if __name__ == "__main__":
                 (1, "DQN, e-greedy per env, eps 0", dict(per_env, e_greedy_final_epsilon=0.0)),
                 (1, "DQN, e-greedy per env, eps 1", dict(per_env, e_greedy_final_epsilon=1.0)),
                 (1, "DQN, greedy (again)", greedy)]
+    if args.rows == "eval":
+        rows = [(3, "IDS + IQN, eval: greedy", {}), (3, "IDS + IQN, eval: min_regret", dict(eval_action_selector="min_regret")),
+                (3, "IDS + IQN, eval: greedy (again)", {})]
+        if args.no_min_regret:
+            del rows[1]
     res = {}
     for cfg_i, name, over in rows:
         for graph in ((True,) if args.rows != "all" else (True, False)):
-            r = measure(cfg_i, graph, args.reps, sizes, **over)
-            what = f" {name}" if args.rows == "egreedy" else " sampled" if over else ""
+            r = measure(cfg_i, graph, args.reps, sizes, eval_mode=args.rows == "eval", **over)
+            what = f" {name}" if args.rows in ("egreedy", "eval") else " sampled" if over else ""
             res[f"{args.tag}configs[{cfg_i}]{what} {'graph' if graph else 'eager'}"] = r
             for k, v in r.items():
                 print(f"{args.tag}{name:36s} {'hipGraph' if graph else 'eager   '} {k:18s}: {v:7.1f} us per Agent.forward (host -> actions on the host)",
