@@ -614,6 +614,51 @@ int prism_egreedy_select(const float *z, const float *q, int32_t n, int32_t n_pa
                          float *out_mean, double *out_epsilon, uint8_t *out_explored, int64_t *out_action,
                          int64_t *out_action_host, prism_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * MinAtar Breakout on the device: n_envs environments stepped in lockstep, one launch per step (DESIGN.md 7.3 has the
+ * rules: a restatement of MinAtar v1, not checked against the `minatar` package).  Observations are [n_envs][10][10][4],
+ * values 0 / 1, fp32 (PRISM_OBS_F32) or uint8 (PRISM_OBS_U8); channel 0 paddle, 1 ball, 2 the ball's last cell, 3 bricks.
+ *
+ * State block: PRISM_ENV_STATE_WORDS uint32 per environment,
+ *   [0] bricks, bit 10 (y - 1) + x for rows y = 1..3 (no other row ever holds one)
+ *   [1] pos (bits 0-3) | ball_x (4-7) | ball_y (8-11) | ball_dir (12-13) | last_x (16-19) | last_y (20-23) | strike (24) |
+ *       last_action (25-27; the game's action 0..5 after the 3-action map)
+ *   [2] ep_steps   [4], [5] t, the environment's lifetime step count (low, high)   [3], [6], [7] zero
+ * obs[2] are the two ping-pong buffers of the observation to act on: a reset writes obs[0]; a step with `parity` p -- the
+ * buffer that holds the current acting observation -- writes obs[p ^ 1] and does not touch obs[p], which the caller may
+ * still hand to the replay ingestion.  A step also writes next_obs (the image after the step, BEFORE any reset; obs[p ^ 1]
+ * is the same image unless the episode ended, then that of the fresh episode), reward (0 or 1), done, truncated.
+ * Draws: r = Philox4x32-10(seed, t, (env << 32) | "ENVB" = 0x454E5642) with t the count BEFORE the step; the sticky coin is
+ * the 53-bit uniform of r[0], r[1], r[2] & 1 the side of the episode that begins if this step ends one; the first episode's
+ * side is r[3] & 1 of the draw at counter 2^64 - 1.  u_in / side_in / first_side_in (optional, device, [n_envs]) replace
+ * them: the parity path.
+ * actions: [n_envs] int64 on the device, read in place.  n_actions 6: n, l, u, r, d, f (only l = 1 and r = 3 act);
+ * n_actions 3: 0 -> n, 1 -> l, 2 -> r.  An action outside [0, n_actions) acts as no-op and ORs
+ * PRISM_ENV_STATUS_BAD_ACTION into *status (sticky; the host reads it when it likes, never per step).
+ * Neither launch takes a host value that changes from step to step except `parity`: a captured step replays as is and
+ * writes the buffer it wrote at capture.  Calls on one descriptor must follow each other on the device.
+ * ------------------------------------------------------------------------------------------ */
+#define PRISM_ENV_STATE_WORDS 8
+#define PRISM_ENV_MAX 65536
+#define PRISM_ENV_STATUS_BAD_ACTION 1u
+typedef struct prism_env_desc {
+    int32_t n_envs, n_actions;      /* n_envs in [1, PRISM_ENV_MAX]; n_actions 6 or 3 */
+    int32_t step_limit;             /* > 0: truncate an episode after that many steps; 0: never */
+    int32_t obs_kind;               /* PRISM_OBS_F32 | PRISM_OBS_U8 */
+    double sticky_p;                /* in [0, 1]: probability that a step repeats the action before it */
+    uint64_t seed;
+    uint32_t *state;                /* [n_envs][PRISM_ENV_STATE_WORDS], 16-byte aligned */
+    uint32_t *status;               /* [1] */
+    void *obs[2];                   /* 16-byte aligned */
+    void *next_obs;                 /* 16-byte aligned */
+    float *reward;                  /* [n_envs] */
+    uint8_t *done, *truncated;      /* [n_envs] 1 / 0 */
+} prism_env_desc;
+/* every environment: a fresh first episode, t = 0, last_action = 0, the acting observation in obs[0] */
+int prism_env_breakout_reset(const prism_env_desc *d, const uint8_t *first_side_in, prism_stream_t stream);
+int prism_env_breakout_step(const prism_env_desc *d, const int64_t *actions, const double *u_in, const uint8_t *side_in,
+                            int32_t parity, prism_stream_t stream);
+
 /* Agent.sync_target_model (agent.py:149-152): target := online (device-to-device copy). */
 int prism_sync_target(float *target_params, const float *params, int64_t n_params,
                       prism_stream_t stream);

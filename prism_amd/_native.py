@@ -51,6 +51,15 @@ class EvalDesc(ctypes.Structure):
                 ("log_return", c_vp), ("log_length", c_vp), ("stats", c_vp), ("counts", c_vp), ("host_counts", c_vp)]
 
 
+ENV_STATE_WORDS, ENV_MAX, ENV_STATUS_BAD_ACTION = 8, 65536, 1
+
+
+class EnvDesc(ctypes.Structure):
+    _fields_ = [("n_envs", c_i32), ("n_actions", c_i32), ("step_limit", c_i32), ("obs_kind", c_i32),
+                ("sticky_p", ctypes.c_double), ("seed", c_u64), ("state", c_vp), ("status", c_vp), ("obs", c_vp * 2),
+                ("next_obs", c_vp), ("reward", c_vp), ("done", c_vp), ("truncated", c_vp)]
+
+
 class ModelDims(ctypes.Structure):
     _fields_ = [(n, c_i32) for n in (
         "in_channels", "n_actions", "embed_dim", "use_iqn", "n_basis", "iqn_layers", "iqn_width", "n_tau",
@@ -152,6 +161,8 @@ SIGNATURES = {
     "prism_min_regret_select": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "prism_simple_ids_select": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.c_double, c_i32, c_vp, c_vp, c_vp, c_vp,
                                                c_vp]),
+    "prism_env_breakout_reset": (ctypes.c_int, [_P(EnvDesc), c_vp, c_vp]),
+    "prism_env_breakout_step": (ctypes.c_int, [_P(EnvDesc), c_vp, c_vp, c_vp, c_i32, c_vp]),
     "prism_sync_target": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp]),
     "prism_direct_reduce_scatter": (ctypes.c_int, [_P(DirectDesc), c_i32, c_vp]),
     "prism_direct_all_gather": (ctypes.c_int, [_P(DirectDesc), c_i32, c_vp]),

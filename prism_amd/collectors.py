@@ -67,16 +67,22 @@ class VectorCollector:
         logger.log_data(data=st["episodes"], group_name="Report/Rewards", var_name="Episodes")
 
     def state_dict(self):
-        """Plain data for an exact-resume snapshot: the action generator and the row count.  The state of the environments
-        is the environments' own business (as it is for the reference's environment processes): a caller that can restore
-        it gets a bit-identical continuation, the collector goes on from ``envs.observe()``; one that cannot restores the
-        ring with ``keep_streams=False``."""
-        return dict(rng=_plain(self.rng.bit_generator.state), rows=int(self.rows), started=bool(self._started))
+        """Plain data for an exact-resume snapshot: the action generator and the row count, and under ``envs`` the
+        environments' own ``state_dict()`` where they have one (prism_amd/envs.py).  The state of any other environments is
+        their own business (as it is for the reference's environment processes): a caller that can restore it gets a
+        bit-identical continuation, the collector goes on from ``envs.observe()``; one that cannot restores the ring with
+        ``keep_streams=False``."""
+        state = dict(rng=_plain(self.rng.bit_generator.state), rows=int(self.rows), started=bool(self._started))
+        if hasattr(self.envs, "state_dict"):          # (the key exists only then: environments that restore themselves)
+            state["envs"] = self.envs.state_dict()
+        return state
 
     def load_state_dict(self, state):
         self.rng.bit_generator.state = state["rng"]
         self.rows, self._started = int(state["rows"]), bool(state["started"])
         self._obs = None
+        if "envs" in state and hasattr(self.envs, "load_state_dict"):
+            self.envs.load_state_dict(state["envs"])
 
     def close(self):
         close = getattr(self.envs, "close", None)
