@@ -113,8 +113,9 @@ def iqn_forward(p, spec, e, taus):
     return z
 
 
-def iqn_loss(p, p_tgt, spec, e_cur, e_next, acts, returns, dg, taus):
-    """Returns per-sample quantile-Huber loss (B,).  taus: list in draw order."""
+def iqn_loss(p, p_tgt, spec, e_cur, e_next, acts, returns, dg, taus, aux=None):
+    """Returns per-sample quantile-Huber loss (B,).  taus: list in draw order.  `aux`, if given, receives "quad_share":
+    the share of (sample, j, t) pairs on the quadratic branch |delta| <= kappa."""
     B = acts.shape[0]
     T, Tn, k = spec.n_tau, spec.n_tau_next, spec.huber_k
     taus = list(taus)
@@ -142,6 +143,8 @@ def iqn_loss(p, p_tgt, spec, e_cur, e_next, acts, returns, dg, taus):
     q = torch.gather(z_cur, 1, torch.tile(acts.view(-1, 1), [T, 1])).view(T, B, 1).transpose(1, 0)
     delta = y[:, :, None] - q[:, None, :]                             # (B, T', T, 1)
     le = torch.le(delta.abs(), k).float()
+    if aux is not None:
+        aux["quad_share"] = float(le.mean())
     hub = le * 0.5 * delta.square() + (1 - le) * k * (delta.abs() - 0.5 * k)
     tq = tau_cur.view(T, B, 1).transpose(1, 0)
     tq = torch.tile(tq[:, None, :, :], [1, Tn, 1, 1]).float()
@@ -245,7 +248,7 @@ def composite_losses(p, p_tgt, spec, batch, taus):
     dl = ql = td = None
     aux = {}
     if spec.use_iqn:
-        dl = iqn_loss(p, p_tgt, spec, e_cur, e_next, acts, R, dg, taus)
+        dl = iqn_loss(p, p_tgt, spec, e_cur, e_next, acts, R, dg, taus, aux)
     if spec.n_heads > 0:
         ql, aux["theil"] = qens_loss(p, p_tgt, spec, e_cur, e_next, acts, R, dg)
     if dl is not None and ql is not None:

@@ -26,8 +26,9 @@ TARGET_DQ = dict(use_target_network=True, use_double_q_learning=True)
 RMSPROP, SGD = dict(use_adam=False, use_rmsprop=True), dict(use_adam=False, use_rmsprop=False)
 
 
-def _case(A, C, B, over, steps=2, modes=("fp32", "bf16x3"), check_params=True, patterns=None):
-    return dict(A=A, C=C, B=B, over=over, steps=steps, modes=modes, check_params=check_params, patterns=patterns)
+def _case(A, C, B, over, steps=2, modes=("fp32", "bf16x3"), check_params=True, patterns=None, mixed_gamma=False):
+    return dict(A=A, C=C, B=B, over=over, steps=steps, modes=modes, check_params=check_params, patterns=patterns,
+                mixed_gamma=mixed_gamma)
 
 
 UPDATE_CASES = {}
@@ -71,6 +72,8 @@ UPDATE_CASES["r8_dqn1_b4096"] = _case(6, 4, 4096, dict(DQN1, use_layer_norm=Fals
 for _A in (3, 5):
     UPDATE_CASES[f"r9_rmsprop_a{_A}"] = _case(_A, 4, 32, dict(RMSPROP))
     UPDATE_CASES[f"r9_sgd_a{_A}"] = _case(_A, 4, 32, dict(SGD))
+# 10: a discount per sample, drawn from {0.99, 0.99**2, 0.99**3} (every other row gives all samples 0.99**3)
+UPDATE_CASES["r10_iqn_gammas_a5"] = _case(5, 4, 32, {}, mixed_gamma=True)
 
 # Minibatch-generator seeds that are not 1 (chosen as the module docstring says)
 BATCH_SEEDS = {}
@@ -114,7 +117,7 @@ def batch_of(rng, case, cfg):
     `patterns`)."""
     A, C, B, P = case["A"], case["C"], case["B"], case["patterns"]
     if P is None:
-        return H.random_batch(rng, B, C, A, cfg)
+        return H.random_batch(rng, B, C, A, cfg, mixed_gamma=True) if case.get("mixed_gamma") else H.random_batch(rng, B, C, A, cfg)
     pat, _, ptaus = H.random_batch(rng, P, C, A, cfg)
     batch, w, _ = H.random_batch(rng, B, C, A, cfg)
     pid = torch.from_numpy(rng.integers(0, P, B))

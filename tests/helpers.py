@@ -17,6 +17,12 @@ UPDATE_CASES = ["iqn_small", "iqn_c3", "dqn_c2", "dqn_ln", "dqn_target_c2", "ful
                 # value squish of the TD target (loss_squish_fn_id): symlog / obs_look_further
                 "iqn_symlog", "full_olf", "dqn_symlog"]
 
+# away from the presets' scalars (tools/gen_golden.py CASES): Huber kappa 0.37 / 1.6, loss weights, Theil coefficient 0.5 on
+# heads of unequal norm, propagate_grad off, clip thresholds below the gradient norm, other Adam hyper-parameters.  The
+# centered-RMSprop one, dqn_rmsprop_scalars, is held where the RMSprop oracle lives (tests/test_optimizers.py NEW_CASES).
+SCALAR_CASES = ["iqn_scalars", "iqn_t16_scalars", "iqn_l0_scalars", "full_scalars", "full_nodistgrad", "abl_scalars"]
+UPDATE_CASES += SCALAR_CASES
+
 # n-step chains recorded from the live reference (tools/gen_golden.py gen_nstep / NSTEP_CHAINS): whatever lies in the fixture
 # directory, nstep_chain (n_step 3) first; tests/test_oracle_replay.py asserts which lengths and discounts they cover
 NSTEP_CHAINS = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(GOLDEN, "nstep_chain*.npz")))
@@ -42,6 +48,22 @@ def case_config(g, device="cpu", **extra):
     kw.update(case_overrides(g))
     kw.update(extra)
     return C.derive(base, **kw)
+
+
+def case_head_scale(g):
+    """(a, b) of a fixture recorded with Q head h scaled by a + b * h after construction, or None."""
+    return tuple(float(x) for x in g["head_scale"]) if "head_scale" in g.files else None
+
+
+def scale_heads(named, head_scale):
+    """Multiply every tensor of Q head h by a + b * h in place; `named`: (state_dict key, tensor) pairs.  None: nothing."""
+    if head_scale is None:
+        return
+    a, b = head_scale
+    with torch.no_grad():
+        for k, v in named:
+            if k.startswith("q_function_model.q_heads."):
+                v.mul_(a + b * int(k.split(".")[2]))
 
 
 def case_batch(g, step):
@@ -81,14 +103,15 @@ def spec_from_config(cfg, C=4, A=6):
                      adam_eps=cfg.adam_epsilon)
 
 
-def build_init_state(cfg, seed, C=4, A=6):
+def build_init_state(cfg, seed, C=4, A=6, head_scale=None):
     """Initial weights by construction (same seed, same layer creation order as the reference);
-    returns (state_dict, target_state_dict or None)."""
+    returns (state_dict, target_state_dict or None).  `head_scale`: case_head_scale of the fixture."""
     from prism_amd.factory.model_factory import create_model
     torch.manual_seed(seed)
     with contextlib.redirect_stdout(io.StringIO()):
         m = create_model((10, 10, C), A, cfg)
         sd = {k: v.clone() for k, v in m.state_dict().items()}
+        scale_heads(sd.items(), head_scale)
         tgt = None
         if cfg.use_target_network:
             create_model((10, 10, C), A, cfg)      # advances the RNG like agent_factory.py:15-18
@@ -121,8 +144,11 @@ def variant_config(device, over):
     return derive(MINATAR_CONFIG, **kw)
 
 
-def random_batch(rng, B, C, A, cfg):
-    """A seeded random minibatch, PER weights and the quantile samples of one update in the reference's draw order."""
+def random_batch(rng, B, C, A, cfg, mixed_gamma=False):
+    """A seeded random minibatch, PER weights and the quantile samples of one update in the reference's draw order.
+    `mixed_gamma`: a per-sample discount from {0.99, 0.99**2, 0.99**3} (n-step walks cut short), drawn last -- every other
+    draw stays what it is without the keyword, which existing callers do not pass: their seeds were chosen on the one-gamma
+    draw."""
     T, Tn = cfg.iqn_n_current_state_quantile_samples, cfg.iqn_n_next_state_quantile_samples
     batch = dict(obs=torch.from_numpy((rng.random((B, 10, 10, C)) < 0.15).astype(np.float32)),
                  next_obs=torch.from_numpy((rng.random((B, 10, 10, C)) < 0.15).astype(np.float32)),
@@ -134,6 +160,8 @@ def random_batch(rng, B, C, A, cfg):
     n_next = 2 if (cfg.use_target_network and cfg.use_double_q_learning) else 1
     taus = [torch.from_numpy(rng.random((B * T, 1)).astype(np.float32))]
     taus += [torch.from_numpy(rng.random((B * Tn, 1)).astype(np.float32)) for _ in range(n_next)]
+    if mixed_gamma:
+        batch["gamma"] = torch.from_numpy((0.99 ** rng.integers(1, 4, B)).astype(np.float32))
     return batch, w, taus
 
 
@@ -230,7 +258,8 @@ def oracle_ring(buf, cfg):
     """ReplayOracle over the device ring's small arrays; observation rows are filled lazily (calloc'ed, only the sampled
     slots' pages ever become resident: the 1.25 M-slot ring would be 4 GB of host memory otherwise)."""
     from oracle import per_ref
-    orc = per_ref.ReplayOracle(buf.capacity, buf.obs_elems, cfg.n_step_returns_length, cfg.gamma, cfg.per_alpha, 0.5)
+    orc = per_ref.ReplayOracle(buf.capacity, buf.obs_elems, cfg.n_step_returns_length, cfg.gamma, cfg.per_alpha,
+                               buf.buffer._sampler._beta)          # (the beta the sampling launches read)
     orc.reward[:] = buf.reward.cpu().numpy()
     orc.action[:] = buf.action.cpu().numpy()
     orc.flags[:] = buf.flags.cpu().numpy()

@@ -32,7 +32,7 @@ def updated_agent(name, dev, with_oracle=False, **extra):
     if with_oracle:
         from oracle.learner_ref import LearnerOracle
         cpu_cfg = H.case_config(g)
-        sd, tgt = H.build_init_state(cpu_cfg, int(g["seed"]), C=int(g["C"]), A=int(g["A"]))
+        sd, tgt = H.build_init_state(cpu_cfg, int(g["seed"]), C=int(g["C"]), A=int(g["A"]), head_scale=H.case_head_scale(g))
         orc = LearnerOracle(sd, H.spec_from_config(cpu_cfg, C=int(g["C"]), A=int(g["A"])), tgt)
     for step in range(int(g["steps"])):
         batch, w, taus = H.case_batch(g, step)
@@ -134,12 +134,13 @@ def test_agent_forward_in_pieces_and_with_device_draws(dev, name):
 
 
 def test_ids_select_against_oracle_on_random_estimates(dev):
+    """The selector's scalars (lambda, epsilon, rho_min) at the preset's values and away from them, on the same estimates.
+    Rows whose two smallest oracle scores lie within the score tolerance of each other have two correct answers and are left
+    out of the action comparison: tests/test_scalar_case_inputs.py caps them at 5 % per triple on the CPU."""
     from oracle.learner_ref import ids_scores
     from prism_amd import _native as N
-    rng = np.random.default_rng(11)
-    for n, T, A, heads in ((1, 200, 6, 10), (7, 32, 3, 2), (33, 200, 16, 10), (4, 1, 6, 1)):
-        dist = torch.from_numpy(rng.standard_normal((T, n, A)).astype(np.float32) * 2.0 + 1.0)
-        q = torch.from_numpy(rng.standard_normal((n, A, heads)).astype(np.float32))
+    from tests import scalar_cases as S
+    for (lam, eps, rho), (n, T, A, heads, dist, q) in ((s, e) for s in S.IDS_SELECT_SCALARS for e in S.ids_select_estimates()):
         n_pad = (n + 15) // 16 * 16
         z = dist.permute(1, 0, 2).contiguous().to(dev)
         qb = torch.zeros((heads, n_pad, A))
@@ -147,14 +148,15 @@ def test_ids_select_against_oracle_on_random_estimates(dev):
         qb = qb.to(dev)
         scores = torch.empty((n, A), device=dev)
         action = torch.empty(n, dtype=torch.int64, device=dev)
-        N.check(N.lib().prism_ids_select(N.ptr(z), N.ptr(qb), n, n_pad, T, A, heads, 0.1, 1e-10, 0.25, 0, N.ptr(scores), None,
+        N.check(N.lib().prism_ids_select(N.ptr(z), N.ptr(qb), n, n_pad, T, A, heads, lam, eps, rho, 0, N.ptr(scores), None,
                                          N.ptr(action), None, N.current_stream_handle()), "prism_ids_select")
         torch.cuda.synchronize()
         if T == 1 or heads == 1:
             continue          # torch.var / torch.std of a single element are NaN in the reference too; only "does not fault"
-        r = ids_scores(dist, q, 0.1, 1e-10, 0.25)
-        np.testing.assert_allclose(scores.cpu().numpy(), r["scores"].numpy(), rtol=2e-4, atol=1e-7)
-        np.testing.assert_array_equal(action.cpu().numpy(), r["action"].numpy())
+        r = ids_scores(dist, q, lam, eps, rho)
+        np.testing.assert_allclose(scores.cpu().numpy(), r["scores"].numpy(), rtol=S.IDS_SCORE_RTOL, atol=S.IDS_SCORE_ATOL)
+        clear = ~S.ids_ambiguous_rows(r["scores"].numpy())
+        np.testing.assert_array_equal(action.cpu().numpy()[clear], r["action"].numpy()[clear])
 
 
 def test_act_forward_rejects_bad_arguments(dev):

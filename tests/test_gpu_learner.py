@@ -30,6 +30,11 @@ def build_hip_agent(g, dev, **extra):
     torch.manual_seed(int(g["seed"]))
     with contextlib.redirect_stdout(io.StringIO()):
         agent = agent_factory.build_agent(cfg, (10, 10, int(g["C"])), int(g["A"]))
+    # fixtures recorded with scaled Q heads: the same scaling, online and target (the parameters are views of agent.flat /
+    # agent.flat_target; nothing is packed before the first update)
+    for m in (agent.model, agent.target_model):
+        if m is not None:
+            H.scale_heads(m.named_parameters(), H.case_head_scale(g))
     return cfg, agent
 
 
@@ -51,6 +56,10 @@ IQN_CASES = ["iqn_small", "iqn_c3", "iqn_tau32", "iqn_target", "iqn_doubleq",
              "abl_iqn", "abl_ln_notarget", "abl_doubleq", "abl_ids", "abl_ids_var", "abl_sub",
              # value squish of the TD target (loss_squish_fn_id: symlog, obs_look_further) in every loss kernel that forms one
              "iqn_symlog", "full_olf", "dqn_symlog"]
+# away from the presets' scalars: Huber kappa != 1 in the in-tile loss (iqn_scalars, abl_scalars at width 256), the stand-alone
+# loss (iqn_t16_scalars) and the linear head (iqn_l0_scalars); loss weights != 1; the Theil coefficient 0.5 on heads of
+# unequal norm (full_scalars); propagate_grad = 0 (full_nodistgrad); a clip coefficient < 1 every step; other Adam values
+IQN_CASES += H.SCALAR_CASES
 
 
 # Both ways of multiplying the forward GEMMs (include/prism_hip.h gemm_mode) are held to the same fixtures at the same
@@ -65,7 +74,7 @@ def test_iqn_update_matches_reference_and_oracle(dev, name, gemm_mode):
     s0 = np.array([float(v.double().sum()) for v in agent.model.state_dict().values()])
     np.testing.assert_array_equal(s0, g["init_sum"])
     cpu_cfg = H.case_config(g)
-    sd, tgt = H.build_init_state(cpu_cfg, int(g["seed"]), C=int(g["C"]), A=int(g["A"]))
+    sd, tgt = H.build_init_state(cpu_cfg, int(g["seed"]), C=int(g["C"]), A=int(g["A"]), head_scale=H.case_head_scale(g))
     orc = LearnerOracle(sd, H.spec_from_config(cpu_cfg, C=int(g["C"]), A=int(g["A"])), tgt)
     names = list(sd.keys())
     kink_total = 0
@@ -164,7 +173,7 @@ def test_philox_taus_are_uniform_and_recorded(dev):
     # replaying the recorded taus through the oracle reproduces the in-kernel-RNG step
     from oracle.learner_ref import LearnerOracle
     cpu_cfg = H.case_config(g)
-    sd, tgt = H.build_init_state(cpu_cfg, int(g["seed"]), C=int(g["C"]), A=int(g["A"]))
+    sd, tgt = H.build_init_state(cpu_cfg, int(g["seed"]), C=int(g["C"]), A=int(g["A"]), head_scale=H.case_head_scale(g))
     orc = LearnerOracle(sd, H.spec_from_config(cpu_cfg, C=int(g["C"]), A=int(g["A"])), tgt)
     taus = [t1[0, :T * B].cpu().reshape(-1, 1), t1[1, :T * B].cpu().reshape(-1, 1)]
     td_o = orc.update(batch, w, taus)

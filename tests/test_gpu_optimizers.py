@@ -123,7 +123,7 @@ def oracle_run(name):
         from oracle.learner_ref import LearnerOracle
         g = H.load_case(name)
         cpu_cfg = H.case_config(g)
-        sd, tgt = H.build_init_state(cpu_cfg, int(g["seed"]), C=int(g["C"]), A=int(g["A"]))
+        sd, tgt = H.build_init_state(cpu_cfg, int(g["seed"]), C=int(g["C"]), A=int(g["A"]), head_scale=H.case_head_scale(g))
         spec = H.spec_from_config(cpu_cfg, C=int(g["C"]), A=int(g["A"]))
         orc = swap_optimizer(LearnerOracle(sd, spec, tgt), cpu_cfg)
         steps = []

@@ -25,7 +25,16 @@ def _mk(dev, fused, graph, B=32, cap=4096, base=2, fuse_tail=True, **over):
 
 @pytest.mark.parametrize("over", [dict(), dict(use_target_network=True, target_update_period=2),
                                   dict(base=0), dict(base=1), dict(base=3, target_update_period=3),
-                                  dict(base=1, use_layer_norm=True, use_double_q_learning=True, use_target_network=True)])
+                                  dict(base=1, use_layer_norm=True, use_double_q_learning=True, use_target_network=True),
+                                  # away from the presets' scalars: the fused tail and the in-graph writeback have call sites of
+                                  # their own for the clip, the optimizer and the priority exponent; the unfused form is held to
+                                  # the oracle at such scalars by tests/test_gpu_learner.py and tests/test_gpu_optimizers.py
+                                  dict(iqn_huber_loss_kappa=0.37, distributional_loss_weight=0.6, max_grad_norm=0.05,
+                                       learning_rate=5e-4, adam_beta1=0.8, adam_beta2=0.95, adam_epsilon=3e-4, per_alpha=1.0),
+                                  dict(base=3, target_update_period=3, q_loss_weight=1.7, distributional_loss_weight=0.3,
+                                       ids_ensemble_variation_coef=0.5, max_grad_norm=0.5, per_alpha=0.7),
+                                  dict(base=1, q_loss_weight=0.4, use_adam=False, use_rmsprop=True, rmsprop_alpha=0.9,
+                                       rmsprop_epsilon=0.02, learning_rate=5e-4, max_grad_norm=0.1)])
 def test_fused_and_graph_equal_unfused(over):
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")

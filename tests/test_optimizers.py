@@ -11,7 +11,9 @@ import torch
 
 from tests import helpers as H
 
-NEW_CASES = ["dqn_c2_rmsprop", "iqn_c3_rmsprop", "abl_ln_notarget_rmsprop", "full_small_sgd"]
+NEW_CASES = ["dqn_c2_rmsprop", "iqn_c3_rmsprop", "abl_ln_notarget_rmsprop", "full_small_sgd",
+             # centered RMSprop away from the preset: alpha 0.9, eps 0.02, lr 5e-4, q_loss_weight 0.4, clip at 0.5
+             "dqn_rmsprop_scalars"]
 
 
 def swap_optimizer(orc, cfg):
@@ -191,7 +193,7 @@ def test_oracle_with_swapped_optimizer_reproduces_the_reference(name):
     g = H.load_case(name)
     cfg = H.case_config(g)
     assert not cfg.use_adam
-    sd, tgt = H.build_init_state(cfg, int(g["seed"]), C=int(g["C"]), A=int(g["A"]))
+    sd, tgt = H.build_init_state(cfg, int(g["seed"]), C=int(g["C"]), A=int(g["A"]), head_scale=H.case_head_scale(g))
     orc = swap_optimizer(LearnerOracle(sd, H.spec_from_config(cfg, C=int(g["C"]), A=int(g["A"])), tgt), cfg)
     width = max(cfg.iqn_quantile_model_feature_dim if cfg.use_iqn else 0, cfg.ids_q_head_feature_dim if cfg.use_ids else 0)
     for step in range(int(g["steps"])):

@@ -14,7 +14,7 @@ LOSS_TOL = 1e-5       # BASELINE.json: loss parity to reference within 1e-5
 def test_oracle_matches_reference_update(name):
     g = H.load_case(name)
     cfg = H.case_config(g)
-    sd, tgt = H.build_init_state(cfg, int(g["seed"]), C=int(g["C"]), A=int(g["A"]))
+    sd, tgt = H.build_init_state(cfg, int(g["seed"]), C=int(g["C"]), A=int(g["A"]), head_scale=H.case_head_scale(g))
     s0, l0 = H.checksums(sd)
     assert list(sd.keys()) == list(g["param_names"])
     np.testing.assert_array_equal(s0, g["init_sum"])           # init parity is exact

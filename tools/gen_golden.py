@@ -53,15 +53,16 @@ def _import_reference():
     sys.modules["wandb"] = types.ModuleType("wandb")
 
 
-def synth_batch(rng, B, C=4, A=6, p_term=0.05):
+def synth_batch(rng, B, C=4, A=6, p_term=0.05, p_short=0.05):
+    """p_short: share of samples whose n-step walk was cut short (gamma 0.99**2, half of them 0.99)."""
     obs = (rng.random((B, 1, 10, 10, C)) < 0.1).astype(np.float32)
     nobs = (rng.random((B, 1, 10, 10, C)) < 0.1).astype(np.float32)
     rew = rng.standard_normal((B, 1)).astype(np.float32)
     nonterm = rng.random((B, 1)) >= p_term
     g = np.full((B, 1), 0.99 ** 3, np.float32)
     sel = rng.random(B)
-    g[sel < 0.05, 0] = np.float32(0.99 ** 2)
-    g[sel < 0.025, 0] = np.float32(0.99)
+    g[sel < p_short, 0] = np.float32(0.99 ** 2)
+    g[sel < p_short / 2, 0] = np.float32(0.99)
     act = rng.integers(0, A, size=(B, 1)).astype(np.int64)
     w = (rng.random(B).astype(np.float32) * 0.9 + 0.1)
     return dict(obs=obs, next_obs=nobs, reward=rew, nonterminal=nonterm, gamma=g, action=act, w=w)
@@ -80,8 +81,11 @@ def tensor_stats(sd):
     return names, s, l2
 
 
+_ADAM_SCALARS = dict(learning_rate=5e-4, adam_beta1=0.8, adam_beta2=0.95, adam_epsilon=3e-4)
+_MIXED = (0.3, 0.5)
+
 CASES = {
-    # name: (config overrides, B, steps, store_full_params)
+    # name: (config overrides, B, steps, store_full_params[, (p_term, p_short)])
     "iqn_small": (dict(use_ids=False, use_iqn=True, use_dqn=False, iqn_n_current_state_quantile_samples=4,
                        iqn_n_next_state_quantile_samples=4), 8, 3, True),
     "iqn_c3": (dict(use_ids=False, use_iqn=True, use_dqn=False), 256, 3, False),
@@ -133,16 +137,50 @@ CASES = {
                                      use_rmsprop=True), 64, 2, False),
     "full_small_sgd": (dict(use_ids=True, use_iqn=True, use_target_network=True, use_adam=False, use_rmsprop=False),
                        16, 2, False),
+    # ---- away from the presets' scalars: Huber kappa on both sides of 1, loss weights, the Theil coefficient, the clip
+    # threshold below the gradient norm, Adam / RMSprop hyper-parameters (lr / eps at or below the presets' ratio).  A fifth
+    # element is synth_batch's (p_term, p_short): more terminal samples and more short-walk gammas per step; a third number
+    # in it is added to the seed of the batch generator -- the first offset at which the oracle's own gradient is free of
+    # kink-adjacent ReLU units at the recorded inputs (tests/scalar_cases.py worst_kink <= 0.5, asserted by
+    # tests/test_scalar_case_inputs.py; width 256 without LayerNorm and the ten heads meet such units at most seeds).
+    # "head_scale" = (a, b): every parameter of Q head h is multiplied by a + b * h after the factory built the agent
+    # (heads of equal norm leave the Theil term at ~4e-8).
+    "iqn_scalars": (dict(use_ids=False, use_iqn=True, use_dqn=False, iqn_huber_loss_kappa=0.37, distributional_loss_weight=0.6,
+                         max_grad_norm=0.05, **_ADAM_SCALARS), 32, 2, False, _MIXED),
+    "iqn_t16_scalars": (dict(use_ids=False, use_iqn=True, use_dqn=False, use_target_network=True, use_double_q_learning=True,
+                             iqn_n_current_state_quantile_samples=16, iqn_n_next_state_quantile_samples=16,
+                             iqn_huber_loss_kappa=1.6, distributional_loss_weight=2.0, max_grad_norm=3.0), 16, 2, False, _MIXED),
+    "iqn_l0_scalars": (dict(use_ids=False, use_iqn=True, use_dqn=False, iqn_quantile_model_layers=0, iqn_huber_loss_kappa=0.37,
+                            distributional_loss_weight=0.6, **_ADAM_SCALARS), 32, 2, False, _MIXED),
+    "full_scalars": (dict(use_ids=True, use_iqn=True, use_target_network=True, iqn_huber_loss_kappa=1.6,
+                          distributional_loss_weight=0.3, q_loss_weight=1.7, ids_ensemble_variation_coef=0.5, max_grad_norm=0.5,
+                          head_scale=(0.55, 0.1)), 16, 2, False, _MIXED + (1,)),
+    "full_nodistgrad": (dict(use_ids=True, use_iqn=True, use_target_network=True, ids_allow_distributional_gradients=False,
+                             iqn_huber_loss_kappa=1.6, distributional_loss_weight=0.3, q_loss_weight=1.7), 16, 2, False, _MIXED),
+    "dqn_rmsprop_scalars": (dict(use_ids=False, use_iqn=False, use_dqn=True, use_layer_norm=False, q_loss_weight=0.4,
+                                 use_adam=False, use_rmsprop=True, rmsprop_alpha=0.9, rmsprop_epsilon=0.02, learning_rate=5e-4,
+                                 max_grad_norm=0.1), 32, 2, False, _MIXED),          # (gradient norms 0.31 - 0.45 at q weight 0.4)
+    "abl_scalars": (dict(base="additive", iqn_huber_loss_kappa=0.37, distributional_loss_weight=0.6), 64, 2, False, _MIXED + (21,)),
 }
 
 
-def gen_update_case(name, overrides, B, steps, store_full):
+def scale_heads(model, head_scale):
+    """Every parameter of Q head h times a + b * h, in place."""
+    a, b = head_scale
+    with torch.no_grad():
+        for k, p in model.named_parameters():
+            if k.startswith("q_function_model.q_heads."):
+                p.mul_(a + b * int(k.split(".")[2]))
+
+
+def gen_update_case(name, overrides, B, steps, store_full, batch_p=None):
     from prism.config import Config, MINATAR_CONFIG, ADDITIVE_ABLATION_BASE_CONFIG, SUBTRACTIVE_ABLATION_BASE_CONFIG
     from prism.factory import agent_factory
 
     overrides = dict(overrides)
     base = overrides.get("base", "minatar")
     C = overrides.pop("C", 4)
+    head_scale = overrides.pop("head_scale", None)
     A = 6
     preset = {"minatar": MINATAR_CONFIG, "additive": ADDITIVE_ABLATION_BASE_CONFIG,
               "subtractive": SUBTRACTIVE_ABLATION_BASE_CONFIG}[base]
@@ -155,6 +193,10 @@ def gen_update_case(name, overrides, B, steps, store_full):
     with contextlib.redirect_stdout(io.StringIO()):
         agent = agent_factory.build_agent(cfg, (10, 10, C), A)
     out = {"seed": cfg.seed, "B": B, "steps": steps, "C": C, "A": A}
+    if head_scale is not None:
+        scale_heads(agent.model, head_scale)
+        scale_heads(agent.target_model, head_scale)
+        out["head_scale"] = np.array(head_scale, np.float64)
     ov = {k: v for k, v in overrides.items() if k != "base"}
     out["base"] = base
     out["overrides_keys"] = np.array(list(ov.keys()))
@@ -167,10 +209,10 @@ def gen_update_case(name, overrides, B, steps, store_full):
         for k, v in agent.model.state_dict().items():
             out["init/" + k] = v.numpy().copy()
 
-    rng = np.random.default_rng(1000 + sum(map(ord, name)))
+    rng = np.random.default_rng(1000 + sum(map(ord, name)) + (batch_p[2] if batch_p is not None and len(batch_p) > 2 else 0))
     real_rand = torch.rand
     for step in range(steps):
-        b = synth_batch(rng, B, C, A)
+        b = synth_batch(rng, B, C, A) if batch_p is None else synth_batch(rng, B, C, A, *batch_p[:2])
         taus = []
 
         def rec(*a, **k):
