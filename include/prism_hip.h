@@ -659,6 +659,38 @@ int prism_env_breakout_reset(const prism_env_desc *d, const uint8_t *first_side_
 int prism_env_breakout_step(const prism_env_desc *d, const int64_t *actions, const double *u_in, const uint8_t *side_in,
                             int32_t parity, prism_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * MinAtar Freeway on the device, behind the same descriptor, checks, ping-pong contract, action checks and status word as
+ * Breakout above (DESIGN.md 7.4 has the rules: a restatement of MinAtar v1, not checked against the `minatar` package).
+ * Observations are [n_envs][10][10][7], values 0 / 1, fp32 or uint8; channel 0 the chicken at (pos, 4), 1 the cars at
+ * (y, x), 1 + |speed| (2..6) the trail cell of a car at (y, x - 1) for speed > 0, else (y, x + 1), wrapped to 0..9.
+ * An environment's image is 2800 bytes in fp32 and 700 bytes in uint8: the buffers are 16-byte aligned at their base, a
+ * byte image inside them at 4 bytes only.
+ *
+ * State block: PRISM_ENV_STATE_WORDS uint32 per environment; car i = 0..7 is on row y = i + 1,
+ *   [0] x of car i (0..9) in bits 4i .. 4i+3
+ *   [1] timer of car i (0..5) in bits 3i .. 3i+2 | direction of car i in bit 24 + i (1: speed > 0, moves to +x)
+ *   [2] ep_steps
+ *   [3] |speed| of car i (1..5) in bits 3i .. 3i+2
+ *   [4], [5] t, the environment's lifetime step count (low, high)
+ *   [6] pos (bits 0-3) | move_timer (4-5) | terminate_timer (6-17, 0..2500) | last_action (18-20; the game's action 0..5
+ *       after the 3-action map)
+ *   [7] zero
+ * Draws, with t the count BEFORE the step and one stream key per purpose: the sticky coin is the 53-bit uniform of words
+ * 0, 1 of Philox4x32-10(seed, t, (env << 32) | "FWYC" = 0x46575943).  A set of eight speeds is the four words of the draw
+ * under a first key (cars 0-3) and the four under a second (cars 4-7), |speed| = 1 + (((uint64_t)(w >> 1) * 5) >> 31),
+ * direction + if w & 1: the win set under "FWW0", "FWW1" = 0x46575730, 0x46575731 at counter t, drawn only on a step
+ * that wins; the reset set under "FWR0", "FWR1" = 0x46575230, 0x46575231 at counter t, drawn only on a step that ends an
+ * episode; the first episode's speeds are the reset set at counter 2^64 - 1.  u_in ([n_envs] double) replaces the coin;
+ * speeds_in ([n_envs][8] int8, each +-1 .. +-5) replaces BOTH sets of that step, first_speeds_in the reset's: the parity
+ * path.
+ * actions: [n_envs] int64 on the device, read in place.  n_actions 6: n, l, u, r, d, f (only u = 2 and d = 4 act);
+ * n_actions 3: 0 -> n, 1 -> u, 2 -> d.  Out of range: as Breakout.
+ * ------------------------------------------------------------------------------------------ */
+int prism_env_freeway_reset(const prism_env_desc *d, const int8_t *first_speeds_in, prism_stream_t stream);
+int prism_env_freeway_step(const prism_env_desc *d, const int64_t *actions, const double *u_in, const int8_t *speeds_in,
+                           int32_t parity, prism_stream_t stream);
+
 /* Agent.sync_target_model (agent.py:149-152): target := online (device-to-device copy). */
 int prism_sync_target(float *target_params, const float *params, int64_t n_params,
                       prism_stream_t stream);

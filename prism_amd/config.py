@@ -29,6 +29,10 @@ constructing unchanged); they are read with ``getattr(config, name, default)``:
                       observation arrays as one byte per element -- a quarter of the HBM -- for byte-exact
                       observations (integers 0..255 such as MinAtar's boolean planes); results are bit for bit
                       those of the fp32 ring, any other observation is refused (HipReplayBuffer obs_storage)
+    device_env_games  tuple of the MinAtar games ``env_factory.build_environment`` may put on the device, default
+                      ("Breakout",); with "Freeway" in it, env_name "MinAtar/Freeway-v0" / "-v1" builds a
+                      ``DeviceFreeway`` (prism_amd/envs.py) instead of raising NotImplementedError; a name that is
+                      no device game is a ValueError
 """
 import dataclasses
 import json

@@ -1,8 +1,8 @@
-"""``DeviceBreakout`` -- MinAtar Breakout for N lock-stepped environments, stepped by one launch of
-``prism_env_breakout_step`` (include/prism_hip.h; the rules are DESIGN.md 7.3: a restatement of MinAtar v1 that is NOT
-checked against the ``minatar`` package).  It is the ``VectorCollector`` protocol (prism_amd/collectors.py), so acting, the
-environment step, the replay ingestion and the learner step sit on one stream and no host code reads an observation, a
-reward or an episode end.
+"""The MinAtar games on the device: ``DeviceBreakout`` and ``DeviceFreeway`` -- N lock-stepped environments, stepped by one
+launch of ``prism_env_breakout_step`` / ``prism_env_freeway_step`` (include/prism_hip.h; the rules are DESIGN.md 7.3 and
+7.4: restatements of MinAtar v1 that are NOT checked against the ``minatar`` package).  Either is the ``VectorCollector``
+protocol (prism_amd/collectors.py), so acting, the environment step, the replay ingestion and the learner step sit on one
+stream and no host code reads an observation, a reward or an episode end.
 
 What ``step`` returns are views of persistent device buffers; nothing synchronises.
 
@@ -10,6 +10,10 @@ What ``step`` returns are views of persistent device buffers; nothing synchronis
 * The observation to act on alternates between two addresses: ``step`` writes the one ``observe()`` did NOT return last and
   leaves the other untouched, so the observation a step acted on can still be handed to ``extend_batch`` after it, and
   ``Agent.forward``'s captured launch reads either address in place (its "ptr" mode keeps one capture per address).
+
+The two games share ``_DeviceEnv`` (buffers, descriptor, staging, status word, ping-pong, snapshots); a game adds its entry
+points, its state codec and the draws its parity path replaces.  The module-level ``OBS_SHAPE``, ``pack_state``,
+``unpack_state`` and ``render`` are Breakout's; Freeway's carry its name.
 """
 import ctypes
 
@@ -20,12 +24,25 @@ from prism_amd import _native as N
 from prism_amd.experience.hip_replay import _Staging, _is_dev
 
 OBS_SHAPE = (10, 10, 4)
+FREEWAY_OBS_SHAPE = (10, 10, 7)
+FREEWAY_CARS = 8
 _OBS_DTYPES = {"float32": (N.OBS_F32, torch.float32), "uint8": (N.OBS_U8, torch.uint8)}
 _FIELDS = ("pos", "ball_x", "ball_y", "ball_dir", "last_x", "last_y", "strike", "last_action")
 _SHIFTS = dict(pos=(0, 15), ball_x=(4, 15), ball_y=(8, 15), ball_dir=(12, 3), last_x=(16, 15), last_y=(20, 15), strike=(24, 1),
                last_action=(25, 7))
-_NP = {torch.uint8: np.uint8, torch.float64: np.float64}
+_NP = {torch.uint8: np.uint8, torch.int8: np.int8, torch.float64: np.float64}
 _LIMITS = dict(pos=9, ball_x=9, ball_y=9, ball_dir=3, last_x=9, last_y=9, strike=1, last_action=5)
+# Freeway: word 6 of the record, and the per-car words (include/prism_hip.h)
+_FW_FIELDS = ("pos", "move_timer", "terminate_timer", "last_action")
+_FW_SHIFTS = dict(pos=(0, 15), move_timer=(4, 3), terminate_timer=(6, 4095), last_action=(18, 7))
+_FW_LIMITS = dict(pos=9, move_timer=3, terminate_timer=2500, last_action=5)
+
+
+def _counters(words, fields, n):
+    """Words [2], [4], [5] of either game's record: ``ep_steps`` and the 64-bit ``t``."""
+    words[:, 2] = np.asarray(fields["ep_steps"]).astype(np.uint32)
+    t = np.array([int(x) for x in fields["t"]], dtype=np.uint64).reshape(n)
+    words[:, 4], words[:, 5] = (t & np.uint64(0xFFFFFFFF)).astype(np.uint32), (t >> np.uint64(32)).astype(np.uint32)
 
 
 def pack_state(fields):
@@ -43,9 +60,7 @@ def pack_state(fields):
         if v.min() < 0 or v.max() > _LIMITS[name]:
             raise ValueError(f"DeviceBreakout.set_state: {name} outside [0, {_LIMITS[name]}]")
         words[:, 1] |= (v << _SHIFTS[name][0]).astype(np.uint32)
-    words[:, 2] = np.asarray(fields["ep_steps"]).astype(np.uint32)
-    t = np.array([int(x) for x in fields["t"]], dtype=np.uint64)
-    words[:, 4], words[:, 5] = (t & np.uint64(0xFFFFFFFF)).astype(np.uint32), (t >> np.uint64(32)).astype(np.uint32)
+    _counters(words, fields, n)
     return words.view(np.int32)
 
 
@@ -62,33 +77,106 @@ def unpack_state(words):
     return out
 
 
-class DeviceBreakout:
+def render(fields):
+    """The observation of a state dict, uint8 [N, 10, 10, 4]: paddle | ball | last ball cell | bricks.  Only ``set_state``
+    draws an image on the host (there is no launch that only draws); every image of a run is the kernel's."""
+    n = len(fields["pos"])
+    img = np.zeros((n,) + OBS_SHAPE, np.uint8)
+    i = np.arange(n)
+    img[i, 9, np.asarray(fields["pos"]), 0] = 1
+    img[i, np.asarray(fields["ball_y"]), np.asarray(fields["ball_x"]), 1] = 1
+    img[i, np.asarray(fields["last_y"]), np.asarray(fields["last_x"]), 2] = 1
+    img[..., 3] = np.asarray(fields["bricks"]).reshape(n, 10, 10) != 0
+    return img
+
+
+def pack_freeway_state(fields):
+    """Freeway's state block, int32 [N, 8], from a dict of host arrays: ``pos``, ``move_timer``, ``terminate_timer``,
+    ``last_action``, ``ep_steps``, ``t`` [N] and, per car, ``car_x`` (0..9), ``car_timer`` (0..5), ``car_speed`` (signed,
+    +-1 .. +-5) [N, 8]."""
+    n = len(fields["pos"])
+    words = np.zeros((n, N.ENV_STATE_WORDS), np.uint32)
+    x, timer, speed = (np.asarray(fields[k]).astype(np.int64).reshape(n, FREEWAY_CARS) for k in ("car_x", "car_timer", "car_speed"))
+    for name, v, lo, hi in (("car_x", x, 0, 9), ("car_timer", timer, 0, 5), ("|car_speed|", np.abs(speed), 1, 5)):
+        if v.min() < lo or v.max() > hi:
+            raise ValueError(f"DeviceFreeway.set_state: {name} outside [{lo}, {hi}]")
+    car = np.arange(FREEWAY_CARS, dtype=np.int64)
+    words[:, 0] = (x << (4 * car)).sum(axis=1).astype(np.uint32)
+    words[:, 1] = ((timer << (3 * car)).sum(axis=1) | ((speed > 0).astype(np.int64) << (24 + car)).sum(axis=1)).astype(np.uint32)
+    words[:, 3] = (np.abs(speed) << (3 * car)).sum(axis=1).astype(np.uint32)
+    for name in _FW_FIELDS:
+        v = np.asarray(fields[name]).astype(np.int64).reshape(n)
+        if v.min() < 0 or v.max() > _FW_LIMITS[name]:
+            raise ValueError(f"DeviceFreeway.set_state: {name} outside [0, {_FW_LIMITS[name]}]")
+        words[:, 6] |= (v << _FW_SHIFTS[name][0]).astype(np.uint32)
+    _counters(words, fields, n)
+    return words.view(np.int32)
+
+
+def unpack_freeway_state(words):
+    """The inverse of ``pack_freeway_state`` (``t`` as uint64)."""
+    w = np.ascontiguousarray(words).view(np.uint32).reshape(-1, N.ENV_STATE_WORDS)
+    out = {name: ((w[:, 6] >> sh) & mask).astype(np.int32) for name, (sh, mask) in _FW_SHIFTS.items()}
+    car = np.arange(FREEWAY_CARS, dtype=np.uint32)
+    out["car_x"] = ((w[:, 0:1] >> (4 * car)) & 15).astype(np.int32)
+    out["car_timer"] = ((w[:, 1:2] >> (3 * car)) & 7).astype(np.int32)
+    mag = ((w[:, 3:4] >> (3 * car)) & 7).astype(np.int32)
+    out["car_speed"] = np.where((w[:, 1:2] >> (24 + car)) & 1, mag, -mag).astype(np.int32)
+    out["ep_steps"] = w[:, 2].astype(np.int64)
+    out["t"] = w[:, 4].astype(np.uint64) | (w[:, 5].astype(np.uint64) << np.uint64(32))
+    return out
+
+
+def render_freeway(fields):
+    """The observation of a Freeway state dict, uint8 [N, 10, 10, 7]: chicken | cars | the trail cell of a car in channel
+    1 + |speed|.  As ``render``: only ``set_state`` draws on the host."""
+    n = len(fields["pos"])
+    img = np.zeros((n,) + FREEWAY_OBS_SHAPE, np.uint8)
+    i = np.arange(n)
+    img[i, np.asarray(fields["pos"]), 4, 0] = 1
+    x, speed = (np.asarray(fields[k]).astype(np.int64).reshape(n, FREEWAY_CARS) for k in ("car_x", "car_speed"))
+    for c in range(FREEWAY_CARS):
+        img[i, c + 1, x[:, c], 1] = 1
+        img[i, c + 1, (x[:, c] - np.sign(speed[:, c])) % 10, 1 + np.abs(speed[:, c])] = 1
+    return img
+
+
+class _DeviceEnv:
+    """What the device games share.  A game sets ``OBS_SHAPE``, the names of its two entry points, the dtype and per-
+    environment width of the draws its parity path takes, and its codec (``_pack`` / ``_unpack`` / ``_render``)."""
+    OBS_SHAPE = None
+    _RESET = _STEP = None
+    _DRAW_DTYPE, _DRAW_WIDTH = None, 1
+    _pack = _unpack = _render = None
+
     def __init__(self, n_envs, seed, device="cuda:0", sticky_action_prob=0.0, episode_timestep_limit=0, minimal_actions=False,
                  obs_dtype="float32"):
+        self._name = name = type(self).__name__
         n_envs, limit, p = int(n_envs), int(episode_timestep_limit or 0), float(sticky_action_prob)
         if not 1 <= n_envs <= N.ENV_MAX:
-            raise ValueError(f"DeviceBreakout: n_envs must be in [1, {N.ENV_MAX}]")
+            raise ValueError(f"{name}: n_envs must be in [1, {N.ENV_MAX}]")
         if not 0.0 <= p <= 1.0:
-            raise ValueError("DeviceBreakout: sticky_action_prob must be in [0, 1]")
+            raise ValueError(f"{name}: sticky_action_prob must be in [0, 1]")
         if limit < 0 or limit >= 2 ** 31:
-            raise ValueError("DeviceBreakout: episode_timestep_limit must be in [0, 2^31)")
+            raise ValueError(f"{name}: episode_timestep_limit must be in [0, 2^31)")
         if obs_dtype not in _OBS_DTYPES:
-            raise ValueError(f"DeviceBreakout: obs_dtype = {obs_dtype!r} must be one of {sorted(_OBS_DTYPES)}")
+            raise ValueError(f"{name}: obs_dtype = {obs_dtype!r} must be one of {sorted(_OBS_DTYPES)}")
         if not str(device).startswith("cuda"):
-            raise N.NativeLibraryError("DeviceBreakout needs a GPU device; there is no CPU fallback")
+            raise N.NativeLibraryError(f"{name} needs a GPU device; there is no CPU fallback")
         N.lib()
         self.n_envs, self.seed, self.device = n_envs, int(seed) & (2 ** 64 - 1), torch.device(device)
         self.sticky_action_prob, self.episode_timestep_limit, self.minimal_actions = p, limit, bool(minimal_actions)
         self.obs_dtype = obs_dtype
-        self.n_actions, self.obs_shape = (3 if minimal_actions else 6), OBS_SHAPE
+        self.n_actions, self.obs_shape = (3 if minimal_actions else 6), self.OBS_SHAPE
         kind, dtype = _OBS_DTYPES[obs_dtype]
         self._on_device = torch.cuda.device(self.device)
         dev = self.device
         with self._on_device:
             self._state = torch.zeros((n_envs, N.ENV_STATE_WORDS), dtype=torch.int32, device=dev)
             self._status = torch.zeros(1, dtype=torch.int32, device=dev)
-            self._obs = torch.zeros((2, n_envs) + OBS_SHAPE, dtype=dtype, device=dev)
-            self._next_obs = torch.zeros((n_envs,) + OBS_SHAPE, dtype=dtype, device=dev)
+            # two allocations: each ping-pong buffer starts 16-byte aligned whatever an image's size (700 bytes in Freeway)
+            self._obs = tuple(torch.zeros((n_envs,) + self.OBS_SHAPE, dtype=dtype, device=dev) for _ in range(2))
+            self._next_obs = torch.zeros((n_envs,) + self.OBS_SHAPE, dtype=dtype, device=dev)
             self._reward = torch.zeros(n_envs, dtype=torch.float32, device=dev)
             self._done = torch.zeros(n_envs, dtype=torch.uint8, device=dev)
             self._truncated = torch.zeros(n_envs, dtype=torch.uint8, device=dev)
@@ -104,13 +192,10 @@ class DeviceBreakout:
         self.closed = False
 
     # ------------------------------------------------------------------ the VectorCollector protocol
-    def reset(self, first_side=None):
-        """Start every environment: a fresh first episode, lifetime step count 0.  ``first_side`` (tests): the sides, 0 / 1,
-        in place of the draws."""
+    def _reset(self, first):
         with self._on_device:
-            side = None if first_side is None else self._dev(first_side, torch.uint8)
-            N.check(N.lib().prism_env_breakout_reset(self._desc_ref, N.ptr(side), N.current_stream_handle()),
-                    "prism_env_breakout_reset")
+            first = None if first is None else self._dev(first, self._DRAW_DTYPE, self._DRAW_WIDTH)
+            N.check(getattr(N.lib(), self._RESET)(self._desc_ref, N.ptr(first), N.current_stream_handle()), self._RESET)
         self._parity, self._started = 0, True
         return self._obs[0]
 
@@ -119,10 +204,7 @@ class DeviceBreakout:
         self._need_started("observe")
         return self._obs[self._parity]
 
-    def step(self, actions, u=None, side=None):
-        """One step of every environment -> (next_obs, reward, done, truncated), views of persistent device buffers.
-        ``actions``: a device int64 tensor is read in place; anything else goes through a pinned rotation.  ``u`` / ``side``
-        (tests): the sticky coins (float64) and the sides of the episodes that begin, in place of the draws."""
+    def _step(self, actions, u, draws):
         self._need_started("step")
         n = self.n_envs
         with self._on_device:
@@ -134,11 +216,11 @@ class DeviceBreakout:
             else:
                 act = actions
             if act.numel() != n:
-                raise ValueError(f"DeviceBreakout.step: {act.numel()} actions for {n} environments")
+                raise ValueError(f"{self._name}.step: {act.numel()} actions for {n} environments")
             u_dev = None if u is None else self._dev(u, torch.float64)
-            side_dev = None if side is None else self._dev(side, torch.uint8)
-            N.check(N.lib().prism_env_breakout_step(self._desc_ref, N.ptr(act), N.ptr(u_dev), N.ptr(side_dev), self._parity,
-                                                    N.current_stream_handle()), "prism_env_breakout_step")
+            draws_dev = None if draws is None else self._dev(draws, self._DRAW_DTYPE, self._DRAW_WIDTH)
+            N.check(getattr(N.lib(), self._STEP)(self._desc_ref, N.ptr(act), N.ptr(u_dev), N.ptr(draws_dev), self._parity,
+                                                 N.current_stream_handle()), self._STEP)
             if staged:
                 self._stage.submit()
         self._parity ^= 1
@@ -158,51 +240,51 @@ class DeviceBreakout:
         status = int(self._status.item())
         if status & N.ENV_STATUS_BAD_ACTION:
             self._status.zero_()
-            raise N.PrismError(f"DeviceBreakout: a step was given an action outside [0, {self.n_actions}); it acted as no-op")
+            raise N.PrismError(f"{self._name}: a step was given an action outside [0, {self.n_actions}); it acted as no-op")
 
     # ------------------------------------------------------------------ state, for tests and resume
     def get_state(self):
         """The state of every environment as a dict of host arrays (synchronises)."""
-        return unpack_state(self._state.cpu().numpy())
+        return type(self)._unpack(self._state.cpu().numpy())
 
     def set_state(self, fields):
         """Install a state (the dict ``get_state`` returns) and redraw the acting observation from it: afterwards
         ``observe()`` shows the installed state.  Synchronises; for tests and resume, not for the loop."""
-        words = pack_state(fields)
+        words = type(self)._pack(fields)
         if words.shape[0] != self.n_envs:
-            raise ValueError("DeviceBreakout.set_state: one state per environment")
+            raise ValueError(f"{self._name}.set_state: one state per environment")
         with self._on_device:
             self._state.copy_(torch.from_numpy(words))
-            self._obs[0].copy_(torch.from_numpy(render(fields)).to(self._obs.dtype))
+            self._obs[0].copy_(torch.from_numpy(type(self)._render(fields)).to(self._next_obs.dtype))
         self._parity, self._started = 0, True
 
     def state_dict(self):
         """Plain data for an exact-resume snapshot: the state block (the draws follow from it and the seed)."""
-        return dict(kind="DeviceBreakout", n_envs=self.n_envs, n_actions=self.n_actions, seed=self.seed,
+        return dict(kind=self._name, n_envs=self.n_envs, n_actions=self.n_actions, seed=self.seed,
                     started=bool(self._started), state=self._state.cpu().clone())
 
     def load_state_dict(self, state):
         for name in ("kind", "n_envs", "n_actions", "seed"):
-            have = "DeviceBreakout" if name == "kind" else getattr(self, name)
+            have = self._name if name == "kind" else getattr(self, name)
             if state[name] != have:
-                raise ValueError(f"DeviceBreakout.load_state_dict: {name} = {state[name]!r} in the snapshot, {have!r} here")
+                raise ValueError(f"{self._name}.load_state_dict: {name} = {state[name]!r} in the snapshot, {have!r} here")
         if state["started"]:
-            self.set_state(unpack_state(state["state"].numpy()))
+            self.set_state(type(self)._unpack(state["state"].numpy()))
         else:
             self._started = False
 
     # ------------------------------------------------------------------
     def _need_started(self, what):
         if not self._started:
-            raise RuntimeError(f"DeviceBreakout.{what}: call reset() first")
+            raise RuntimeError(f"{self._name}.{what}: call reset() first")
 
-    def _dev(self, x, dtype):
+    def _dev(self, x, dtype, width=1):
         if _is_dev(x):
             x = x.to(dtype).contiguous()
         else:
             x = torch.from_numpy(np.ascontiguousarray(np.asarray(x).reshape(-1).astype(_NP[dtype]))).to(self.device)
-        if x.numel() != self.n_envs:
-            raise ValueError("DeviceBreakout: one value per environment")
+        if x.numel() != self.n_envs * width:
+            raise ValueError(f"{self._name}: {'one value' if width == 1 else f'{width} values'} per environment")
         return x
 
     def _stage_actions(self, actions):
@@ -218,14 +300,45 @@ class DeviceBreakout:
         return dev
 
 
-def render(fields):
-    """The observation of a state dict, uint8 [N, 10, 10, 4]: paddle | ball | last ball cell | bricks.  Only ``set_state``
-    draws an image on the host (there is no launch that only draws); every image of a run is the kernel's."""
-    n = len(fields["pos"])
-    img = np.zeros((n,) + OBS_SHAPE, np.uint8)
-    i = np.arange(n)
-    img[i, 9, np.asarray(fields["pos"]), 0] = 1
-    img[i, np.asarray(fields["ball_y"]), np.asarray(fields["ball_x"]), 1] = 1
-    img[i, np.asarray(fields["last_y"]), np.asarray(fields["last_x"]), 2] = 1
-    img[..., 3] = np.asarray(fields["bricks"]).reshape(n, 10, 10) != 0
-    return img
+class DeviceBreakout(_DeviceEnv):
+    OBS_SHAPE = OBS_SHAPE
+    _RESET, _STEP = "prism_env_breakout_reset", "prism_env_breakout_step"
+    _DRAW_DTYPE, _DRAW_WIDTH = torch.uint8, 1
+    _pack, _unpack, _render = staticmethod(pack_state), staticmethod(unpack_state), staticmethod(render)
+
+    def reset(self, first_side=None):
+        """Start every environment: a fresh first episode, lifetime step count 0.  ``first_side`` (tests): the sides, 0 / 1,
+        in place of the draws."""
+        return self._reset(first_side)
+
+    def step(self, actions, u=None, side=None):
+        """One step of every environment -> (next_obs, reward, done, truncated), views of persistent device buffers.
+        ``actions``: a device int64 tensor is read in place; anything else goes through a pinned rotation.  ``u`` / ``side``
+        (tests): the sticky coins (float64) and the sides of the episodes that begin, in place of the draws."""
+        return self._step(actions, u, side)
+
+
+class DeviceFreeway(_DeviceEnv):
+    OBS_SHAPE = FREEWAY_OBS_SHAPE
+    _RESET, _STEP = "prism_env_freeway_reset", "prism_env_freeway_step"
+    _DRAW_DTYPE, _DRAW_WIDTH = torch.int8, FREEWAY_CARS
+    _pack, _unpack, _render = staticmethod(pack_freeway_state), staticmethod(unpack_freeway_state), staticmethod(render_freeway)
+
+    def reset(self, first_speeds=None):
+        """Start every environment: a fresh first episode, lifetime step count 0.  ``first_speeds`` (tests): the cars'
+        speeds [n_envs, 8], each +-1 .. +-5, in place of the draws."""
+        return self._reset(self._speeds(first_speeds))
+
+    def step(self, actions, u=None, speeds=None):
+        """One step of every environment -> (next_obs, reward, done, truncated), as ``DeviceBreakout.step``.  ``u`` /
+        ``speeds`` (tests): the sticky coins (float64) and the speeds [n_envs, 8] that a win or a reset on this step
+        installs, in place of the draws."""
+        return self._step(actions, u, self._speeds(speeds))
+
+    @staticmethod
+    def _speeds(speeds):
+        if speeds is not None and not _is_dev(speeds):
+            mag = np.abs(np.asarray(speeds).astype(np.int64))
+            if mag.size and (mag.min() < 1 or mag.max() > 5):
+                raise ValueError("DeviceFreeway: speeds must be +-1 .. +-5")
+        return speeds

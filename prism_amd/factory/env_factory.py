@@ -1,25 +1,44 @@
 """``build_environment``: the environments of a configuration as ONE object of the ``VectorCollector`` protocol
 (prism_amd/collectors.py).  Where the reference starts one process per environment
-(its ``multiprocessing_experience_collection/environment_process.py:35-48``), MinAtar Breakout here is N
-environments stepped by one launch on the learner's device (prism_amd/envs.py)."""
+(its ``multiprocessing_experience_collection/environment_process.py:35-48``), a MinAtar game here is N environments
+stepped by one launch on the learner's device (prism_amd/envs.py)."""
 
 MINATAR_GAMES = ("Asterix", "Breakout", "Freeway", "Seaquest", "SpaceInvaders")
+DEVICE_GAMES = {"Breakout": "DeviceBreakout", "Freeway": "DeviceFreeway"}          # game -> its class in prism_amd/envs.py
+DEFAULT_DEVICE_GAMES = ("Breakout",)
+
+
+def enabled_games(config):
+    """``config.device_env_games`` (a plain attribute, default ``("Breakout",)``): the games ``build_environment`` may put on
+    the device.  A name that is no device game is a ``ValueError``."""
+    games = getattr(config, "device_env_games", DEFAULT_DEVICE_GAMES)
+    games = (games,) if isinstance(games, str) else tuple(games)
+    for g in games:
+        if g not in DEVICE_GAMES:
+            raise ValueError(f"build_environment: device_env_games names {g!r}; the device games are {sorted(DEVICE_GAMES)}")
+    return games
 
 
 def build_environment(config, n_envs, seed=None):
     """``env_name`` "MinAtar/Breakout-v0" (six actions) or "MinAtar/Breakout-v1" (the minimal action set: no-op, left,
-    right) -> ``DeviceBreakout``.  The other MinAtar games are not on the device: ``NotImplementedError`` naming the game.
-    Anything else: ``ValueError``."""
+    right) -> ``DeviceBreakout``; with "Freeway" in ``config.device_env_games``, "MinAtar/Freeway-v0" / "-v1" (no-op, up,
+    down) -> ``DeviceFreeway``.  A MinAtar game that is not on the device, or not enabled: ``NotImplementedError`` naming
+    the game.  Anything else: ``ValueError``."""
     name = str(config.env_name)
     if "MinAtar/" not in name:
-        raise ValueError(f"build_environment: no device environment for env_name = {name!r} (MinAtar/Breakout-v0 / -v1 only)")
+        raise ValueError(f"build_environment: no device environment for env_name = {name!r} (MinAtar/Breakout and MinAtar/Freeway, "
+                         "-v0 / -v1, only)")
     game = name.split("MinAtar/", 1)[1].split("-", 1)[0]
-    if game != "Breakout":
+    if game not in enabled_games(config):
+        if game in DEVICE_GAMES:
+            raise NotImplementedError(f"build_environment: MinAtar {game} on the device is opt-in: add {game!r} to "
+                                      f"config.device_env_games (default {DEFAULT_DEVICE_GAMES!r})")
         if game in MINATAR_GAMES:
-            raise NotImplementedError(f"build_environment: MinAtar {game} is not implemented on the device (Breakout only)")
+            raise NotImplementedError(f"build_environment: MinAtar {game} is not implemented on the device "
+                                      f"({' and '.join(sorted(DEVICE_GAMES))} only)")
         raise ValueError(f"build_environment: unknown MinAtar game in env_name = {name!r}")
-    from prism_amd.envs import DeviceBreakout
-    return DeviceBreakout(n_envs, int(getattr(config, "seed", 0) if seed is None else seed), config.device,
-                          sticky_action_prob=float(getattr(config, "atari_sticky_actions_prob", 0.0)),
-                          episode_timestep_limit=int(getattr(config, "episode_timestep_limit", 0) or 0),
-                          minimal_actions=name.endswith("-v1"))
+    from prism_amd import envs
+    return getattr(envs, DEVICE_GAMES[game])(n_envs, int(getattr(config, "seed", 0) if seed is None else seed), config.device,
+                                             sticky_action_prob=float(getattr(config, "atari_sticky_actions_prob", 0.0)),
+                                             episode_timestep_limit=int(getattr(config, "episode_timestep_limit", 0) or 0),
+                                             minimal_actions=name.endswith("-v1"))
