@@ -642,7 +642,8 @@ int prism_egreedy_select(const float *z, const float *q, int32_t n, int32_t n_pa
 #define PRISM_ENV_MAX 65536
 #define PRISM_ENV_STATUS_BAD_ACTION 1u
 typedef struct prism_env_desc {
-    int32_t n_envs, n_actions;      /* n_envs in [1, PRISM_ENV_MAX]; n_actions 6 or 3 */
+    int32_t n_envs, n_actions;      /* n_envs in [1, PRISM_ENV_MAX]; n_actions 6 or the game's minimal set: 3 in Breakout
+                                       and Freeway, 5 in Asterix */
     int32_t step_limit;             /* > 0: truncate an episode after that many steps; 0: never */
     int32_t obs_kind;               /* PRISM_OBS_F32 | PRISM_OBS_U8 */
     double sticky_p;                /* in [0, 1]: probability that a step repeats the action before it */
@@ -689,6 +690,37 @@ int prism_env_breakout_step(const prism_env_desc *d, const int64_t *actions, con
  * ------------------------------------------------------------------------------------------ */
 int prism_env_freeway_reset(const prism_env_desc *d, const int8_t *first_speeds_in, prism_stream_t stream);
 int prism_env_freeway_step(const prism_env_desc *d, const int64_t *actions, const double *u_in, const int8_t *speeds_in,
+                           int32_t parity, prism_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * MinAtar Asterix on the device, behind the same descriptor, checks (but n_actions must be 5 or 6), ping-pong contract,
+ * action checks and status word as Breakout above (DESIGN.md 7.5 has the rules: a restatement of MinAtar v1, not checked
+ * against the `minatar` package).  Observations are [n_envs][10][10][4], values 0 / 1, fp32 or uint8; channel 0 the player
+ * at (py, px), 1 an enemy at (y, x), 3 a gold at (y, x), 2 the trail cell of either at (y, x - dir) where that column is
+ * in 0..9 (no wrap).
+ *
+ * State block: PRISM_ENV_STATE_WORDS uint32 per environment; entity slot i = 0..7 is row y = i + 1 and is empty or holds
+ * one entity; every field of an empty slot is zero,
+ *   [0] x of slot i (0..9) in bits 4i .. 4i+3
+ *   [1] slot i occupied in bit i | its direction in bit 8 + i (1: dir = +1, moves to +x) | gold in bit 16 + i
+ *   [2] ep_steps
+ *   [3] px (bits 0-3) | py (4-7, 1..8) | spawn_speed (8-11, 1..10) | spawn_timer (12-15, 0..10) | move_speed (16-18, 1..5) |
+ *       move_timer (19-21, 0..5) | last_action (22-24, 0..5) | ramp_index (25-29)
+ *   [4], [5] t, the environment's lifetime step count (low, high)
+ *   [6] ramp_timer + 1 (bits 0-6: ramp_timer is -1..100)
+ *   [7] zero
+ * Draws, with t the count BEFORE the step and one stream key per purpose: the sticky coin is the 53-bit uniform of words
+ * 0, 1 of Philox4x32-10(seed, t, (env << 32) | "ASXC" = 0x41535843).  A spawn takes the words w of the draw under
+ * "ASXS" = 0x41535853 at counter t, drawn only on a step that spawns: side = w[0] & 1 (1: x = 0 moving to +x, 0: x = 9
+ * moving to -x), gold = (((uint64_t)w[1] * 3) >> 32) == 0, and among the k empty slots in ascending order the one of
+ * rank ((uint64_t)w[2] * k) >> 32.  A reset draws nothing.  u_in ([n_envs] double) replaces the coin; spawn_in
+ * ([n_envs][3] uint8: side 0 / 1, gold 0 / 1, rank 0..7, a rank >= k taken as k - 1) replaces the spawn draw of that step:
+ * the parity path.
+ * actions: [n_envs] int64 on the device, read in place.  n_actions 6: n, l, u, r, d, f (f does nothing); n_actions 5:
+ * n, l, u, r, d.  Out of range: as Breakout.
+ * ------------------------------------------------------------------------------------------ */
+int prism_env_asterix_reset(const prism_env_desc *d, prism_stream_t stream);
+int prism_env_asterix_step(const prism_env_desc *d, const int64_t *actions, const double *u_in, const uint8_t *spawn_in,
                            int32_t parity, prism_stream_t stream);
 
 /* Agent.sync_target_model (agent.py:149-152): target := online (device-to-device copy). */

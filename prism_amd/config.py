@@ -31,8 +31,9 @@ constructing unchanged); they are read with ``getattr(config, name, default)``:
                       those of the fp32 ring, any other observation is refused (HipReplayBuffer obs_storage)
     device_env_games  tuple of the MinAtar games ``env_factory.build_environment`` may put on the device, default
                       ("Breakout",); with "Freeway" in it, env_name "MinAtar/Freeway-v0" / "-v1" builds a
-                      ``DeviceFreeway`` (prism_amd/envs.py) instead of raising NotImplementedError; a name that is
-                      no device game is a ValueError
+                      ``DeviceFreeway`` (prism_amd/envs.py) instead of raising NotImplementedError, and with
+                      "Asterix" in it env_name "MinAtar/Asterix-v0" (6 actions) / "-v1" (5) a ``DeviceAsterix``; a
+                      name that is no device game is a ValueError
 """
 import dataclasses
 import json

@@ -1,7 +1,7 @@
-"""The MinAtar games on the device: ``DeviceBreakout`` and ``DeviceFreeway`` -- N lock-stepped environments, stepped by one
-launch of ``prism_env_breakout_step`` / ``prism_env_freeway_step`` (include/prism_hip.h; the rules are DESIGN.md 7.3 and
-7.4: restatements of MinAtar v1 that are NOT checked against the ``minatar`` package).  Either is the ``VectorCollector``
-protocol (prism_amd/collectors.py), so acting, the environment step, the replay ingestion and the learner step sit on one
+"""The MinAtar games on the device: ``DeviceBreakout``, ``DeviceFreeway`` and ``DeviceAsterix`` -- N lock-stepped
+environments, stepped by one launch of ``prism_env_breakout_step`` / ``prism_env_freeway_step`` / ``prism_env_asterix_step``
+(include/prism_hip.h; the rules are DESIGN.md 7.3, 7.4 and 7.5: restatements of MinAtar v1 that are NOT checked against the
+``minatar`` package).  Each is the ``VectorCollector`` protocol (prism_amd/collectors.py), so acting, the environment step, the replay ingestion and the learner step sit on one
 stream and no host code reads an observation, a reward or an episode end.
 
 What ``step`` returns are views of persistent device buffers; nothing synchronises.
@@ -11,9 +11,9 @@ What ``step`` returns are views of persistent device buffers; nothing synchronis
   leaves the other untouched, so the observation a step acted on can still be handed to ``extend_batch`` after it, and
   ``Agent.forward``'s captured launch reads either address in place (its "ptr" mode keeps one capture per address).
 
-The two games share ``_DeviceEnv`` (buffers, descriptor, staging, status word, ping-pong, snapshots); a game adds its entry
-points, its state codec and the draws its parity path replaces.  The module-level ``OBS_SHAPE``, ``pack_state``,
-``unpack_state`` and ``render`` are Breakout's; Freeway's carry its name.
+The games share ``_DeviceEnv`` (buffers, descriptor, staging, status word, ping-pong, snapshots); a game adds its entry
+points, its minimal action count, its state codec and the draws its parity path replaces.  The module-level ``OBS_SHAPE``,
+``pack_state``, ``unpack_state`` and ``render`` are Breakout's; Freeway's and Asterix's carry their names.
 """
 import ctypes
 
@@ -36,6 +36,12 @@ _LIMITS = dict(pos=9, ball_x=9, ball_y=9, ball_dir=3, last_x=9, last_y=9, strike
 _FW_FIELDS = ("pos", "move_timer", "terminate_timer", "last_action")
 _FW_SHIFTS = dict(pos=(0, 15), move_timer=(4, 3), terminate_timer=(6, 4095), last_action=(18, 7))
 _FW_LIMITS = dict(pos=9, move_timer=3, terminate_timer=2500, last_action=5)
+# Asterix: word 3 of the record (ramp_timer + 1 is word 6), and the per-slot words (include/prism_hip.h)
+ASTERIX_SLOTS = 8
+_AX_SHIFTS = dict(px=(0, 15), py=(4, 15), spawn_speed=(8, 15), spawn_timer=(12, 15), move_speed=(16, 7), move_timer=(19, 7),
+                  last_action=(22, 7), ramp_index=(25, 31))
+_AX_RANGES = dict(px=(0, 9), py=(1, 8), spawn_speed=(1, 10), spawn_timer=(0, 10), move_speed=(1, 5), move_timer=(0, 5),
+                  last_action=(0, 5), ramp_index=(0, 15))
 
 
 def _counters(words, fields, n):
@@ -141,12 +147,79 @@ def render_freeway(fields):
     return img
 
 
+def pack_asterix_state(fields):
+    """Asterix's state block, int32 [N, 8], from a dict of host arrays: ``px``, ``py``, ``spawn_speed``, ``spawn_timer``,
+    ``move_speed``, ``move_timer``, ``ramp_timer`` (-1..100), ``ramp_index``, ``last_action``, ``ep_steps``, ``t`` [N] and, per
+    slot, ``ent_active`` (0 / 1), ``ent_x`` (0..9), ``ent_dir`` (+1 / -1) and ``ent_gold`` (0 / 1) [N, 8]; every field of
+    an empty slot is 0."""
+    n = len(fields["px"])
+    words = np.zeros((n, N.ENV_STATE_WORDS), np.uint32)
+    active, x, direction, gold = (np.asarray(fields[k]).astype(np.int64).reshape(n, ASTERIX_SLOTS)
+                                  for k in ("ent_active", "ent_x", "ent_dir", "ent_gold"))
+    for name, v, lo, hi in (("ent_active", active, 0, 1), ("ent_x", x, 0, 9), ("ent_gold", gold, 0, 1)):
+        if v.min() < lo or v.max() > hi:
+            raise ValueError(f"DeviceAsterix.set_state: {name} outside [{lo}, {hi}]")
+    if (np.abs(direction) != active).any():
+        raise ValueError("DeviceAsterix.set_state: ent_dir must be +1 or -1 in a slot that holds an entity, 0 in an empty one")
+    if (x[active == 0] != 0).any() or (gold[active == 0] != 0).any():
+        raise ValueError("DeviceAsterix.set_state: ent_x and ent_gold of an empty slot must be 0")
+    slot = np.arange(ASTERIX_SLOTS, dtype=np.int64)
+    words[:, 0] = (x << (4 * slot)).sum(axis=1).astype(np.uint32)
+    words[:, 1] = ((active << slot) | ((direction > 0).astype(np.int64) << (8 + slot)) | (gold << (16 + slot))).sum(axis=1).astype(np.uint32)
+    for name, (lo, hi) in _AX_RANGES.items():
+        v = np.asarray(fields[name]).astype(np.int64).reshape(n)
+        if v.min() < lo or v.max() > hi:
+            raise ValueError(f"DeviceAsterix.set_state: {name} outside [{lo}, {hi}]")
+        words[:, 3] |= (v << _AX_SHIFTS[name][0]).astype(np.uint32)
+    ramp = np.asarray(fields["ramp_timer"]).astype(np.int64).reshape(n)
+    if ramp.min() < -1 or ramp.max() > 100:
+        raise ValueError("DeviceAsterix.set_state: ramp_timer outside [-1, 100]")
+    words[:, 6] = (ramp + 1).astype(np.uint32)
+    _counters(words, fields, n)
+    return words.view(np.int32)
+
+
+def unpack_asterix_state(words):
+    """The inverse of ``pack_asterix_state`` (``t`` as uint64)."""
+    w = np.ascontiguousarray(words).view(np.uint32).reshape(-1, N.ENV_STATE_WORDS)
+    out = {name: ((w[:, 3] >> sh) & mask).astype(np.int32) for name, (sh, mask) in _AX_SHIFTS.items()}
+    out["ramp_timer"] = (w[:, 6] & 127).astype(np.int32) - 1
+    slot = np.arange(ASTERIX_SLOTS, dtype=np.uint32)
+    out["ent_active"] = ((w[:, 1:2] >> slot) & 1).astype(np.int32)
+    out["ent_x"] = ((w[:, 0:1] >> (4 * slot)) & 15).astype(np.int32)
+    out["ent_dir"] = np.where((w[:, 1:2] >> (8 + slot)) & 1, 1, -1).astype(np.int32) * out["ent_active"]
+    out["ent_gold"] = ((w[:, 1:2] >> (16 + slot)) & 1).astype(np.int32)
+    out["ep_steps"] = w[:, 2].astype(np.int64)
+    out["t"] = w[:, 4].astype(np.uint64) | (w[:, 5].astype(np.uint64) << np.uint64(32))
+    return out
+
+
+def render_asterix(fields):
+    """The observation of an Asterix state dict, uint8 [N, 10, 10, 4]: player | enemies | trail cells | golds; a trail cell
+    off the board is not drawn.  As ``render``: only ``set_state`` draws on the host."""
+    n = len(fields["px"])
+    img = np.zeros((n,) + OBS_SHAPE, np.uint8)
+    i = np.arange(n)
+    img[i, np.asarray(fields["py"]), np.asarray(fields["px"]), 0] = 1
+    active, x, direction, gold = (np.asarray(fields[k]).astype(np.int64).reshape(n, ASTERIX_SLOTS)
+                                  for k in ("ent_active", "ent_x", "ent_dir", "ent_gold"))
+    for c in range(ASTERIX_SLOTS):
+        there = active[:, c] != 0
+        img[i[there], c + 1, x[there, c], np.where(gold[there, c] != 0, 3, 1)] = 1
+        back = x[:, c] - direction[:, c]
+        trail = there & (back >= 0) & (back <= 9)
+        img[i[trail], c + 1, back[trail], 2] = 1
+    return img
+
+
 class _DeviceEnv:
-    """What the device games share.  A game sets ``OBS_SHAPE``, the names of its two entry points, the dtype and per-
-    environment width of the draws its parity path takes, and its codec (``_pack`` / ``_unpack`` / ``_render``)."""
+    """What the device games share.  A game sets ``OBS_SHAPE``, the names of its two entry points, the size of its minimal
+    action set, the dtype and per-environment width of the draws its parity path takes (``_RESET_DRAWS``: whether its reset
+    takes any), and its codec (``_pack`` / ``_unpack`` / ``_render``)."""
     OBS_SHAPE = None
     _RESET = _STEP = None
-    _DRAW_DTYPE, _DRAW_WIDTH = None, 1
+    _MINIMAL_ACTIONS = 3
+    _DRAW_DTYPE, _DRAW_WIDTH, _RESET_DRAWS = None, 1, True
     _pack = _unpack = _render = None
 
     def __init__(self, n_envs, seed, device="cuda:0", sticky_action_prob=0.0, episode_timestep_limit=0, minimal_actions=False,
@@ -167,7 +240,7 @@ class _DeviceEnv:
         self.n_envs, self.seed, self.device = n_envs, int(seed) & (2 ** 64 - 1), torch.device(device)
         self.sticky_action_prob, self.episode_timestep_limit, self.minimal_actions = p, limit, bool(minimal_actions)
         self.obs_dtype = obs_dtype
-        self.n_actions, self.obs_shape = (3 if minimal_actions else 6), self.OBS_SHAPE
+        self.n_actions, self.obs_shape = (self._MINIMAL_ACTIONS if minimal_actions else 6), self.OBS_SHAPE
         kind, dtype = _OBS_DTYPES[obs_dtype]
         self._on_device = torch.cuda.device(self.device)
         dev = self.device
@@ -195,7 +268,8 @@ class _DeviceEnv:
     def _reset(self, first):
         with self._on_device:
             first = None if first is None else self._dev(first, self._DRAW_DTYPE, self._DRAW_WIDTH)
-            N.check(getattr(N.lib(), self._RESET)(self._desc_ref, N.ptr(first), N.current_stream_handle()), self._RESET)
+            draws = (N.ptr(first),) if self._RESET_DRAWS else ()          # a game whose reset draws nothing takes no pointer
+            N.check(getattr(N.lib(), self._RESET)(self._desc_ref, *draws, N.current_stream_handle()), self._RESET)
         self._parity, self._started = 0, True
         return self._obs[0]
 
@@ -342,3 +416,30 @@ class DeviceFreeway(_DeviceEnv):
             if mag.size and (mag.min() < 1 or mag.max() > 5):
                 raise ValueError("DeviceFreeway: speeds must be +-1 .. +-5")
         return speeds
+
+
+class DeviceAsterix(_DeviceEnv):
+    OBS_SHAPE = OBS_SHAPE
+    _RESET, _STEP = "prism_env_asterix_reset", "prism_env_asterix_step"
+    _MINIMAL_ACTIONS = 5
+    _DRAW_DTYPE, _DRAW_WIDTH, _RESET_DRAWS = torch.uint8, 3, False
+    _pack, _unpack, _render = staticmethod(pack_asterix_state), staticmethod(unpack_asterix_state), staticmethod(render_asterix)
+
+    def reset(self):
+        """Start every environment: a fresh first episode, lifetime step count 0.  A reset draws nothing."""
+        return self._reset(None)
+
+    def step(self, actions, u=None, spawn=None):
+        """One step of every environment -> (next_obs, reward, done, truncated), as ``DeviceBreakout.step``.  ``u`` /
+        ``spawn`` (tests): the sticky coins (float64) and the spawns [n_envs, 3] -- side 0 / 1, gold 0 / 1, rank 0..7 among
+        the empty slots -- that a step which spawns uses, in place of the draws."""
+        return self._step(actions, u, self._spawn(spawn))
+
+    @staticmethod
+    def _spawn(spawn):
+        if spawn is not None and not _is_dev(spawn):
+            v = np.asarray(spawn).astype(np.int64).reshape(-1)
+            v = v[:v.size - v.size % 3].reshape(-1, 3)          # (a wrong count is refused where the values are staged)
+            if v.size and (v.min() < 0 or v[:, :2].max() > 1 or v[:, 2].max() > 7):
+                raise ValueError("DeviceAsterix: spawn must be (side 0 / 1, gold 0 / 1, rank 0..7)")
+        return spawn
