@@ -643,7 +643,7 @@ int prism_egreedy_select(const float *z, const float *q, int32_t n, int32_t n_pa
 #define PRISM_ENV_STATUS_BAD_ACTION 1u
 typedef struct prism_env_desc {
     int32_t n_envs, n_actions;      /* n_envs in [1, PRISM_ENV_MAX]; n_actions 6 or the game's minimal set: 3 in Breakout
-                                       and Freeway, 5 in Asterix */
+                                       and Freeway, 5 in Asterix, 4 in Space Invaders */
     int32_t step_limit;             /* > 0: truncate an episode after that many steps; 0: never */
     int32_t obs_kind;               /* PRISM_OBS_F32 | PRISM_OBS_U8 */
     double sticky_p;                /* in [0, 1]: probability that a step repeats the action before it */
@@ -722,6 +722,39 @@ int prism_env_freeway_step(const prism_env_desc *d, const int64_t *actions, cons
 int prism_env_asterix_reset(const prism_env_desc *d, prism_stream_t stream);
 int prism_env_asterix_step(const prism_env_desc *d, const int64_t *actions, const double *u_in, const uint8_t *spawn_in,
                            int32_t parity, prism_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * MinAtar Space Invaders on the device, behind the same descriptor, checks (but n_actions must be 4 or 6), ping-pong
+ * contract, action checks and status word as Breakout above (DESIGN.md 7.6 has the rules: a restatement of MinAtar v1, not
+ * checked against the `minatar` package).  Observations are [n_envs][10][10][6], values 0 / 1, fp32 or uint8; channel 0 the
+ * cannon at (9, pos), 1 the aliens, 2 the aliens again while they move to -x, 3 the aliens again while they move to +x,
+ * 4 the friendly bullets, 5 the enemy bullets.  An environment's image is 2400 bytes in fp32 and 600 bytes in uint8: the
+ * buffers are 16-byte aligned at their base, a byte image inside them at 4 bytes only.
+ *
+ * State block: PRISM_ENV_STATE_WORDS uint32 per environment.  The aliens are a rigid block of 4 rows x 6 columns: the alien
+ * of block cell (r, c) stands on board cell ((alien_y + r) mod 10, alien_x + c); a live alien's column is on the board.  A
+ * bullet map holds at most one bullet per board row: the field of row y is x + 1, 0 for none (play never puts a second
+ * bullet into a row; placing one replaces the row's field),
+ *   [0] block cell (r, c) alive in bit 6r + c (bits 0-23, never all zero) | alien_x + 5 (bits 24-27, alien_x is -5..9) |
+ *       alien_y (28-31, 0..9)
+ *   [1] friendly bullet field of row y = 0..7 in bits 4y .. 4y+3
+ *   [2] ep_steps
+ *   [3] enemy bullet field of row y = 0..7 in bits 4y .. 4y+3
+ *   [4], [5] t, the environment's lifetime step count (low, high)
+ *   [6] friendly bullet fields of rows 8, 9 (bits 0-3, 4-7) | enemy bullet fields of rows 8, 9 (8-11, 12-15) | pos (16-19) |
+ *       shot_timer (20-22, 0..5) | direction (23; 1: alien_dir = +1) | last_action (24-26; the game's action 0..5 after the
+ *       4-action map)
+ *   [7] alien_move_timer (bits 0-3, 0..12) | alien_shot_timer (4-7, 0..10) | enemy_move_interval (8-11, 6..12) |
+ *       ramp_index (12-14, 0..6)
+ * Draws: only the sticky coin, the 53-bit uniform of words 0, 1 of Philox4x32-10(seed, t, (env << 32) | "SPIC" =
+ * 0x53504943) with t the count BEFORE the step; a reset draws nothing.  u_in ([n_envs] double) replaces the coin: the
+ * parity path.  There is no other draw, so neither entry point takes a draw array.
+ * actions: [n_envs] int64 on the device, read in place.  n_actions 6: n, l, u, r, d, f (only l = 1, r = 3 and f = 5 act);
+ * n_actions 4: 0 -> n, 1 -> l, 2 -> r, 3 -> f.  Out of range: as Breakout.
+ * ------------------------------------------------------------------------------------------ */
+int prism_env_invaders_reset(const prism_env_desc *d, prism_stream_t stream);
+int prism_env_invaders_step(const prism_env_desc *d, const int64_t *actions, const double *u_in, int32_t parity,
+                            prism_stream_t stream);
 
 /* Agent.sync_target_model (agent.py:149-152): target := online (device-to-device copy). */
 int prism_sync_target(float *target_params, const float *params, int64_t n_params,

@@ -167,6 +167,8 @@ SIGNATURES = {
     "prism_env_freeway_step": (ctypes.c_int, [_P(EnvDesc), c_vp, c_vp, c_vp, c_i32, c_vp]),
     "prism_env_asterix_reset": (ctypes.c_int, [_P(EnvDesc), c_vp]),
     "prism_env_asterix_step": (ctypes.c_int, [_P(EnvDesc), c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "prism_env_invaders_reset": (ctypes.c_int, [_P(EnvDesc), c_vp]),
+    "prism_env_invaders_step": (ctypes.c_int, [_P(EnvDesc), c_vp, c_vp, c_i32, c_vp]),
     "prism_sync_target": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp]),
     "prism_direct_reduce_scatter": (ctypes.c_int, [_P(DirectDesc), c_i32, c_vp]),
     "prism_direct_all_gather": (ctypes.c_int, [_P(DirectDesc), c_i32, c_vp]),

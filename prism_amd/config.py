@@ -32,8 +32,9 @@ constructing unchanged); they are read with ``getattr(config, name, default)``:
     device_env_games  tuple of the MinAtar games ``env_factory.build_environment`` may put on the device, default
                       ("Breakout",); with "Freeway" in it, env_name "MinAtar/Freeway-v0" / "-v1" builds a
                       ``DeviceFreeway`` (prism_amd/envs.py) instead of raising NotImplementedError, and with
-                      "Asterix" in it env_name "MinAtar/Asterix-v0" (6 actions) / "-v1" (5) a ``DeviceAsterix``; a
-                      name that is no device game is a ValueError
+                      "Asterix" in it env_name "MinAtar/Asterix-v0" (6 actions) / "-v1" (5) a ``DeviceAsterix``, with
+                      "SpaceInvaders" in it env_name "MinAtar/SpaceInvaders-v0" (6 actions) / "-v1" (4) a
+                      ``DeviceSpaceInvaders``; a name that is no device game is a ValueError
 """
 import dataclasses
 import json

@@ -1,7 +1,7 @@
-"""The MinAtar games on the device: ``DeviceBreakout``, ``DeviceFreeway`` and ``DeviceAsterix`` -- N lock-stepped
-environments, stepped by one launch of ``prism_env_breakout_step`` / ``prism_env_freeway_step`` / ``prism_env_asterix_step``
-(include/prism_hip.h; the rules are DESIGN.md 7.3, 7.4 and 7.5: restatements of MinAtar v1 that are NOT checked against the
-``minatar`` package).  Each is the ``VectorCollector`` protocol (prism_amd/collectors.py), so acting, the environment step, the replay ingestion and the learner step sit on one
+"""The MinAtar games on the device: ``DeviceBreakout``, ``DeviceFreeway``, ``DeviceAsterix`` and ``DeviceSpaceInvaders`` -- N
+lock-stepped environments, stepped by one launch of ``prism_env_breakout_step`` / ``prism_env_freeway_step`` /
+``prism_env_asterix_step`` / ``prism_env_invaders_step`` (include/prism_hip.h; the rules are DESIGN.md 7.3, 7.4, 7.5 and 7.6:
+restatements of MinAtar v1 that are NOT checked against the ``minatar`` package).  Each is the ``VectorCollector`` protocol (prism_amd/collectors.py), so acting, the environment step, the replay ingestion and the learner step sit on one
 stream and no host code reads an observation, a reward or an episode end.
 
 What ``step`` returns are views of persistent device buffers; nothing synchronises.
@@ -13,7 +13,8 @@ What ``step`` returns are views of persistent device buffers; nothing synchronis
 
 The games share ``_DeviceEnv`` (buffers, descriptor, staging, status word, ping-pong, snapshots); a game adds its entry
 points, its minimal action count, its state codec and the draws its parity path replaces.  The module-level ``OBS_SHAPE``,
-``pack_state``, ``unpack_state`` and ``render`` are Breakout's; Freeway's and Asterix's carry their names.
+``pack_state``, ``unpack_state`` and ``render`` are Breakout's; Freeway's, Asterix's and Space Invaders' carry their names.
+Space Invaders draws nothing but the sticky coin, so its step passes no draw pointer (``_STEP_DRAWS``).
 """
 import ctypes
 
@@ -42,6 +43,13 @@ _AX_SHIFTS = dict(px=(0, 15), py=(4, 15), spawn_speed=(8, 15), spawn_timer=(12, 
                   last_action=(22, 7), ramp_index=(25, 31))
 _AX_RANGES = dict(px=(0, 9), py=(1, 8), spawn_speed=(1, 10), spawn_timer=(0, 10), move_speed=(1, 5), move_timer=(0, 5),
                   last_action=(0, 5), ramp_index=(0, 15))
+# Space Invaders: the block of 4 x 6 aliens, and the small fields of words 6 and 7 of the record (include/prism_hip.h)
+SPACEINVADERS_OBS_SHAPE = (10, 10, 6)
+INVADERS_BLOCK = (4, 6)
+_SI_SHIFTS = {6: dict(pos=(16, 15), shot_timer=(20, 7), last_action=(24, 7)),
+              7: dict(alien_move_timer=(0, 15), alien_shot_timer=(4, 15), enemy_move_interval=(8, 15), ramp_index=(12, 7))}
+_SI_RANGES = dict(pos=(0, 9), shot_timer=(0, 5), last_action=(0, 5), alien_move_timer=(0, 12), alien_shot_timer=(0, 10),
+                  enemy_move_interval=(6, 12), ramp_index=(0, 6), alien_x=(-5, 9), alien_y=(0, 9))
 
 
 def _counters(words, fields, n):
@@ -212,14 +220,101 @@ def render_asterix(fields):
     return img
 
 
+def _invaders_fields(fields):
+    n = len(fields["pos"])
+    block = np.asarray(fields["alien_block"]).astype(np.int64).reshape((n,) + INVADERS_BLOCK)
+    f, e = (np.asarray(fields[k]).astype(np.int64).reshape(n, 10) for k in ("f_bullet_x", "e_bullet_x"))
+    return n, block, f, e
+
+
+def pack_invaders_state(fields):
+    """Space Invaders' state block, int32 [N, 8], from a dict of host arrays: ``pos``, ``alien_x`` (-5..9), ``alien_y``,
+    ``alien_dir`` (+1 / -1), ``alien_move_timer``, ``alien_shot_timer``, ``enemy_move_interval``, ``ramp_index``,
+    ``shot_timer``, ``last_action``, ``ep_steps``, ``t`` [N]; ``alien_block`` (0 / 1) [N, 4, 6], never empty, a live alien's
+    column ``alien_x + c`` on the board; ``f_bullet_x`` and ``e_bullet_x`` [N, 10], the column of the row's bullet, -1 for
+    none."""
+    n, block, f, e = _invaders_fields(fields)
+    words = np.zeros((n, N.ENV_STATE_WORDS), np.uint32)
+    scalars = {name: np.asarray(fields[name]).astype(np.int64).reshape(n) for name in _SI_RANGES}
+    for name, (lo, hi) in _SI_RANGES.items():
+        if scalars[name].min() < lo or scalars[name].max() > hi:
+            raise ValueError(f"DeviceSpaceInvaders.set_state: {name} outside [{lo}, {hi}]")
+    direction = np.asarray(fields["alien_dir"]).astype(np.int64).reshape(n)
+    if (np.abs(direction) != 1).any():
+        raise ValueError("DeviceSpaceInvaders.set_state: alien_dir must be +1 or -1")
+    if block.min() < 0 or block.max() > 1:
+        raise ValueError("DeviceSpaceInvaders.set_state: alien_block outside [0, 1]")
+    if not block.any(axis=(1, 2)).all():
+        raise ValueError("DeviceSpaceInvaders.set_state: alien_block is empty (a cleared board is refilled on its step)")
+    column = scalars["alien_x"][:, None] + np.arange(INVADERS_BLOCK[1])
+    if (block.any(axis=1) & ((column < 0) | (column > 9))).any():
+        raise ValueError("DeviceSpaceInvaders.set_state: alien_x puts a live alien of alien_block off the board")
+    for name, v in (("f_bullet_x", f), ("e_bullet_x", e)):
+        if v.min() < -1 or v.max() > 9:
+            raise ValueError(f"DeviceSpaceInvaders.set_state: {name} outside [-1, 9]")
+    bit = np.arange(INVADERS_BLOCK[0] * INVADERS_BLOCK[1], dtype=np.int64)
+    words[:, 0] = ((block.reshape(n, -1) << bit).sum(axis=1) | ((scalars["alien_x"] + 5) << 24) | (scalars["alien_y"] << 28)).astype(np.uint32)
+    row = 4 * np.arange(8, dtype=np.int64)
+    words[:, 1] = ((f[:, :8] + 1) << row).sum(axis=1).astype(np.uint32)
+    words[:, 3] = ((e[:, :8] + 1) << row).sum(axis=1).astype(np.uint32)
+    words[:, 6] = ((f[:, 8] + 1) | ((f[:, 9] + 1) << 4) | ((e[:, 8] + 1) << 8) | ((e[:, 9] + 1) << 12) |
+                   ((direction > 0).astype(np.int64) << 23)).astype(np.uint32)
+    for word, names in _SI_SHIFTS.items():
+        for name, (sh, _) in names.items():
+            words[:, word] |= (scalars[name] << sh).astype(np.uint32)
+    _counters(words, fields, n)
+    return words.view(np.int32)
+
+
+def unpack_invaders_state(words):
+    """The inverse of ``pack_invaders_state`` (``t`` as uint64)."""
+    w = np.ascontiguousarray(words).view(np.uint32).reshape(-1, N.ENV_STATE_WORDS)
+    n = w.shape[0]
+    out = {name: ((w[:, word] >> sh) & mask).astype(np.int32) for word, names in _SI_SHIFTS.items() for name, (sh, mask) in names.items()}
+    bit = np.arange(INVADERS_BLOCK[0] * INVADERS_BLOCK[1], dtype=np.uint32)
+    out["alien_block"] = ((w[:, 0:1] >> bit) & 1).astype(np.int32).reshape((n,) + INVADERS_BLOCK)
+    out["alien_x"] = ((w[:, 0] >> 24) & 15).astype(np.int32) - 5
+    out["alien_y"] = (w[:, 0] >> 28).astype(np.int32)
+    out["alien_dir"] = np.where((w[:, 6] >> 23) & 1, 1, -1).astype(np.int32)
+    row = 4 * np.arange(8, dtype=np.uint32)
+    for name, low, sh in (("f_bullet_x", 1, 0), ("e_bullet_x", 3, 8)):
+        fields = np.concatenate([(w[:, low:low + 1] >> row) & 15, (w[:, 6:7] >> np.array([sh, sh + 4], np.uint32)) & 15], axis=1)
+        out[name] = fields.astype(np.int32) - 1
+    out["ep_steps"] = w[:, 2].astype(np.int64)
+    out["t"] = w[:, 4].astype(np.uint64) | (w[:, 5].astype(np.uint64) << np.uint64(32))
+    return out
+
+
+def render_invaders(fields):
+    """The observation of a Space Invaders state dict, uint8 [N, 10, 10, 6]: cannon | aliens | aliens moving to -x | aliens
+    moving to +x | friendly bullets | enemy bullets; block row r is drawn on board row (alien_y + r) mod 10.  As ``render``:
+    only ``set_state`` draws on the host."""
+    n, block, f, e = _invaders_fields(fields)
+    img = np.zeros((n,) + SPACEINVADERS_OBS_SHAPE, np.uint8)
+    i = np.arange(n)
+    img[i, 9, np.asarray(fields["pos"]).astype(np.int64), 0] = 1
+    ax, ay, direction = (np.asarray(fields[k]).astype(np.int64).reshape(n) for k in ("alien_x", "alien_y", "alien_dir"))
+    for r in range(INVADERS_BLOCK[0]):
+        for c in range(INVADERS_BLOCK[1]):
+            there = (block[:, r, c] != 0) & (ax + c >= 0) & (ax + c <= 9)
+            y, x = (ay[there] + r) % 10, ax[there] + c
+            img[i[there], y, x, 1] = 1
+            img[i[there], y, x, np.where(direction[there] < 0, 2, 3)] = 1
+    for y in range(10):
+        for ch, v in ((4, f), (5, e)):
+            there = v[:, y] >= 0
+            img[i[there], y, v[there, y], ch] = 1
+    return img
+
+
 class _DeviceEnv:
     """What the device games share.  A game sets ``OBS_SHAPE``, the names of its two entry points, the size of its minimal
-    action set, the dtype and per-environment width of the draws its parity path takes (``_RESET_DRAWS``: whether its reset
-    takes any), and its codec (``_pack`` / ``_unpack`` / ``_render``)."""
+    action set, the dtype and per-environment width of the draws its parity path takes (``_RESET_DRAWS`` / ``_STEP_DRAWS``:
+    whether its reset / its step takes any), and its codec (``_pack`` / ``_unpack`` / ``_render``)."""
     OBS_SHAPE = None
     _RESET = _STEP = None
     _MINIMAL_ACTIONS = 3
-    _DRAW_DTYPE, _DRAW_WIDTH, _RESET_DRAWS = None, 1, True
+    _DRAW_DTYPE, _DRAW_WIDTH, _RESET_DRAWS, _STEP_DRAWS = None, 1, True, True
     _pack = _unpack = _render = None
 
     def __init__(self, n_envs, seed, device="cuda:0", sticky_action_prob=0.0, episode_timestep_limit=0, minimal_actions=False,
@@ -293,7 +388,8 @@ class _DeviceEnv:
                 raise ValueError(f"{self._name}.step: {act.numel()} actions for {n} environments")
             u_dev = None if u is None else self._dev(u, torch.float64)
             draws_dev = None if draws is None else self._dev(draws, self._DRAW_DTYPE, self._DRAW_WIDTH)
-            N.check(getattr(N.lib(), self._STEP)(self._desc_ref, N.ptr(act), N.ptr(u_dev), N.ptr(draws_dev), self._parity,
+            given = (N.ptr(draws_dev),) if self._STEP_DRAWS else ()          # a game that draws only the coin takes no pointer
+            N.check(getattr(N.lib(), self._STEP)(self._desc_ref, N.ptr(act), N.ptr(u_dev), *given, self._parity,
                                                  N.current_stream_handle()), self._STEP)
             if staged:
                 self._stage.submit()
@@ -443,3 +539,20 @@ class DeviceAsterix(_DeviceEnv):
             if v.size and (v.min() < 0 or v[:, :2].max() > 1 or v[:, 2].max() > 7):
                 raise ValueError("DeviceAsterix: spawn must be (side 0 / 1, gold 0 / 1, rank 0..7)")
         return spawn
+
+
+class DeviceSpaceInvaders(_DeviceEnv):
+    OBS_SHAPE = SPACEINVADERS_OBS_SHAPE
+    _RESET, _STEP = "prism_env_invaders_reset", "prism_env_invaders_step"
+    _MINIMAL_ACTIONS = 4
+    _RESET_DRAWS = _STEP_DRAWS = False
+    _pack, _unpack, _render = staticmethod(pack_invaders_state), staticmethod(unpack_invaders_state), staticmethod(render_invaders)
+
+    def reset(self):
+        """Start every environment: a fresh first episode, lifetime step count 0.  A reset draws nothing."""
+        return self._reset(None)
+
+    def step(self, actions, u=None):
+        """One step of every environment -> (next_obs, reward, done, truncated), as ``DeviceBreakout.step``.  ``u`` (tests):
+        the sticky coins (float64) in place of the draws -- the game draws nothing else."""
+        return self._step(actions, u, None)

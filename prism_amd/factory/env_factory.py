@@ -4,7 +4,8 @@
 stepped by one launch on the learner's device (prism_amd/envs.py)."""
 
 MINATAR_GAMES = ("Asterix", "Breakout", "Freeway", "Seaquest", "SpaceInvaders")
-DEVICE_GAMES = {"Breakout": "DeviceBreakout", "Freeway": "DeviceFreeway", "Asterix": "DeviceAsterix"}          # game -> its class in prism_amd/envs.py
+DEVICE_GAMES = {"Breakout": "DeviceBreakout", "Freeway": "DeviceFreeway", "Asterix": "DeviceAsterix",
+                "SpaceInvaders": "DeviceSpaceInvaders"}          # game -> its class in prism_amd/envs.py
 DEFAULT_DEVICE_GAMES = ("Breakout",)
 
 
@@ -23,12 +24,13 @@ def build_environment(config, n_envs, seed=None):
     """``env_name`` "MinAtar/Breakout-v0" (six actions) or "MinAtar/Breakout-v1" (the minimal action set: no-op, left,
     right) -> ``DeviceBreakout``; with "Freeway" in ``config.device_env_games``, "MinAtar/Freeway-v0" / "-v1" (no-op, up,
     down) -> ``DeviceFreeway``; with "Asterix" in it, "MinAtar/Asterix-v0" / "-v1" (five actions: no-op, left, up, right,
-    down) -> ``DeviceAsterix``.  A MinAtar game that is not on the device, or not enabled: ``NotImplementedError`` naming
+    down) -> ``DeviceAsterix``; with "SpaceInvaders" in it, "MinAtar/SpaceInvaders-v0" / "-v1" (four actions: no-op, left,
+    right, fire) -> ``DeviceSpaceInvaders``.  A MinAtar game that is not on the device, or not enabled: ``NotImplementedError`` naming
     the game.  Anything else: ``ValueError``."""
     name = str(config.env_name)
     if "MinAtar/" not in name:
-        raise ValueError(f"build_environment: no device environment for env_name = {name!r} (MinAtar/Breakout, MinAtar/Freeway and "
-                         "MinAtar/Asterix, -v0 / -v1, only)")
+        raise ValueError(f"build_environment: no device environment for env_name = {name!r} (MinAtar/Breakout, MinAtar/Freeway, "
+                         "MinAtar/Asterix and MinAtar/SpaceInvaders, -v0 / -v1, only)")
     game = name.split("MinAtar/", 1)[1].split("-", 1)[0]
     if game not in enabled_games(config):
         if game in DEVICE_GAMES:
