@@ -756,6 +756,41 @@ int prism_env_invaders_reset(const prism_env_desc *d, prism_stream_t stream);
 int prism_env_invaders_step(const prism_env_desc *d, const int64_t *actions, const double *u_in, int32_t parity,
                             prism_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * MinAtar Seaquest on the device, behind the same descriptor, checks (but n_actions must be 6: the minimal set is all six),
+ * ping-pong contract, action checks and status word as Breakout above (DESIGN.md 7.7 has the rules: a restatement of MinAtar
+ * v1, not checked against the `minatar` package).  Observations are [n_envs][10][10][10], values 0 / 1, fp32 or uint8;
+ * channel 0 the sub at (sub_y, sub_x), 1 the cell behind it, 2 friendly bullets, 3 the trail cell behind every fish, enemy
+ * sub and diver (only on the board), 4 enemy bullets, 5 fish, 6 enemy subs, 7 the oxygen gauge (row 9, columns
+ * 0 .. oxygen * 10 / 200 - 1), 8 the diver gauge (row 9, columns 9 - diver_count .. 8), 9 divers.
+ *
+ * State block: d->state is [n_envs][PRISM_ENV_SEAQUEST_STATE_WORDS] uint32 -- the row width belongs to the game, the
+ * descriptor is unchanged.  The game's five ordered lists are fixed-capacity arrays in list order; removal compacts them
+ * stably, an empty slot is all zeros,
+ *   [0] sub_x (bits 0-3) | sub_y (4-7, 0..8) | sub_or (8; 1: faces +x) | surface (9) | shot_timer (10-12, 0..5) |
+ *       diver_count (13-15, 0..6) | last_action (16-18) | move_speed (19-21, 2..5) | ramp_index (22-26, 0..19)
+ *   [1] oxygen + 1 (bits 0-7; oxygen is -1..200) | e_spawn_speed (8-12, 1..20) | e_spawn_timer (13-17, 0..20) |
+ *       d_spawn_timer (18-22, 0..30)
+ *   [2] ep_steps   [4], [5] t, the environment's lifetime step count (low, high)   [3], [6], [7] zero
+ *   [8 .. 39] fish   [40 .. 71] enemy subs   [72 .. 103] enemy bullets   [104 .. 107] friendly bullets   [108 .. 111] divers
+ * An entry: x (bits 0-3) | y (4-7) | direction (8; 1: moves to +x) | move_timer (9-11, 0..5; 0 in a bullet) | shot_timer
+ * (12-15, 0..10; enemy subs only) | present (16).
+ * An append to a full array is dropped and ORs PRISM_ENV_STATUS_OVERFLOW into *status (sticky, as the bad-action bit).
+ * Draws, with t the count BEFORE the step and one stream key per purpose: the sticky coin is the 53-bit uniform of words
+ * 0, 1 of Philox4x32-10(seed, t, (env << 32) | "SQXC" = 0x53515843).  An enemy spawn takes the words w of the draw under
+ * "SQXE" = 0x53515845 at counter t, drawn only on a step whose e_spawn_timer is 0: side = w[0] & 1 (1: x = 0 moving to +x,
+ * 0: x = 9 moving to -x), is_sub = (((uint64_t)w[1] * 3) >> 32) == 0, row = 1 + (w[2] >> 29).  A diver spawn takes the draw
+ * under "SQXD" = 0x53515844, only on a step whose d_spawn_timer is 0: side = w[0] & 1, row = 1 + (w[1] >> 29).  A reset
+ * draws nothing.  u_in ([n_envs] double) replaces the coin; draws_in ([n_envs][5] uint8: enemy side, is_sub, row 1..8; diver
+ * side, row 1..8) replaces both spawn draws of that step: the parity path.
+ * actions: [n_envs] int64 on the device, read in place: n, l, u, r, d, f.  Out of range: as Breakout.
+ * ------------------------------------------------------------------------------------------ */
+#define PRISM_ENV_SEAQUEST_STATE_WORDS 112
+#define PRISM_ENV_STATUS_OVERFLOW 2u
+int prism_env_seaquest_reset(const prism_env_desc *d, prism_stream_t stream);
+int prism_env_seaquest_step(const prism_env_desc *d, const int64_t *actions, const double *u_in, const uint8_t *draws_in,
+                            int32_t parity, prism_stream_t stream);
+
 /* Agent.sync_target_model (agent.py:149-152): target := online (device-to-device copy). */
 int prism_sync_target(float *target_params, const float *params, int64_t n_params,
                       prism_stream_t stream);

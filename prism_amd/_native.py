@@ -52,6 +52,7 @@ class EvalDesc(ctypes.Structure):
 
 
 ENV_STATE_WORDS, ENV_MAX, ENV_STATUS_BAD_ACTION = 8, 65536, 1
+ENV_SEAQUEST_STATE_WORDS, ENV_STATUS_OVERFLOW = 112, 2          # Seaquest's record is wider: five bounded entity lists
 
 
 class EnvDesc(ctypes.Structure):
@@ -169,6 +170,8 @@ SIGNATURES = {
     "prism_env_asterix_step": (ctypes.c_int, [_P(EnvDesc), c_vp, c_vp, c_vp, c_i32, c_vp]),
     "prism_env_invaders_reset": (ctypes.c_int, [_P(EnvDesc), c_vp]),
     "prism_env_invaders_step": (ctypes.c_int, [_P(EnvDesc), c_vp, c_vp, c_i32, c_vp]),
+    "prism_env_seaquest_reset": (ctypes.c_int, [_P(EnvDesc), c_vp]),
+    "prism_env_seaquest_step": (ctypes.c_int, [_P(EnvDesc), c_vp, c_vp, c_vp, c_i32, c_vp]),
     "prism_sync_target": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp]),
     "prism_direct_reduce_scatter": (ctypes.c_int, [_P(DirectDesc), c_i32, c_vp]),
     "prism_direct_all_gather": (ctypes.c_int, [_P(DirectDesc), c_i32, c_vp]),

@@ -35,6 +35,10 @@ constructing unchanged); they are read with ``getattr(config, name, default)``:
                       "Asterix" in it env_name "MinAtar/Asterix-v0" (6 actions) / "-v1" (5) a ``DeviceAsterix``, with
                       "SpaceInvaders" in it env_name "MinAtar/SpaceInvaders-v0" (6 actions) / "-v1" (4) a
                       ``DeviceSpaceInvaders``; a name that is no device game is a ValueError
+    device_env_wide_games
+                      tuple of the MinAtar games with a wider state record that ``build_environment`` may put on the
+                      device, default (); with "Seaquest" in it env_name "MinAtar/Seaquest-v0" / "-v1" (6 actions either
+                      way) builds a ``DeviceSeaquest``; a name that is no wide-record game is a ValueError
 """
 import dataclasses
 import json

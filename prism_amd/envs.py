@@ -1,6 +1,7 @@
-"""The MinAtar games on the device: ``DeviceBreakout``, ``DeviceFreeway``, ``DeviceAsterix`` and ``DeviceSpaceInvaders`` -- N
-lock-stepped environments, stepped by one launch of ``prism_env_breakout_step`` / ``prism_env_freeway_step`` /
-``prism_env_asterix_step`` / ``prism_env_invaders_step`` (include/prism_hip.h; the rules are DESIGN.md 7.3, 7.4, 7.5 and 7.6:
+"""The MinAtar games on the device: ``DeviceBreakout``, ``DeviceFreeway``, ``DeviceAsterix``, ``DeviceSpaceInvaders`` and
+``DeviceSeaquest`` -- N lock-stepped environments, stepped by one launch of ``prism_env_breakout_step`` /
+``prism_env_freeway_step`` / ``prism_env_asterix_step`` / ``prism_env_invaders_step`` / ``prism_env_seaquest_step``
+(include/prism_hip.h; the rules are DESIGN.md 7.3 to 7.7:
 restatements of MinAtar v1 that are NOT checked against the ``minatar`` package).  Each is the ``VectorCollector`` protocol (prism_amd/collectors.py), so acting, the environment step, the replay ingestion and the learner step sit on one
 stream and no host code reads an observation, a reward or an episode end.
 
@@ -14,7 +15,8 @@ What ``step`` returns are views of persistent device buffers; nothing synchronis
 The games share ``_DeviceEnv`` (buffers, descriptor, staging, status word, ping-pong, snapshots); a game adds its entry
 points, its minimal action count, its state codec and the draws its parity path replaces.  The module-level ``OBS_SHAPE``,
 ``pack_state``, ``unpack_state`` and ``render`` are Breakout's; Freeway's, Asterix's and Space Invaders' carry their names.
-Space Invaders draws nothing but the sticky coin, so its step passes no draw pointer (``_STEP_DRAWS``).
+Space Invaders draws nothing but the sticky coin, so its step passes no draw pointer (``_STEP_DRAWS``).  Seaquest keeps five
+ordered entity lists in a wider record (``_STATE_WORDS``); an append to a full one is dropped and ``check_status`` raises.
 """
 import ctypes
 
@@ -307,6 +309,104 @@ def render_invaders(fields):
     return img
 
 
+# Seaquest: the head fields of words 0 and 1 of its wider record, and its five bounded lists (include/prism_hip.h)
+SEAQUEST_OBS_SHAPE = (10, 10, 10)
+_SQ_SHIFTS = {0: dict(sub_x=(0, 15), sub_y=(4, 15), sub_or=(8, 1), surface=(9, 1), shot_timer=(10, 7), diver_count=(13, 7),
+                      last_action=(16, 7), move_speed=(19, 7), ramp_index=(22, 31)),
+              1: dict(e_spawn_speed=(8, 31), e_spawn_timer=(13, 31), d_spawn_timer=(18, 31))}
+_SQ_RANGES = dict(sub_x=(0, 9), sub_y=(0, 8), sub_or=(0, 1), surface=(0, 1), shot_timer=(0, 5), diver_count=(0, 6), last_action=(0, 5),
+                  move_speed=(2, 5), ramp_index=(0, 19), e_spawn_speed=(1, 20), e_spawn_timer=(0, 20), d_spawn_timer=(0, 30),
+                  oxygen=(-1, 200))
+# list -> (first word, capacity, rows allowed, number of fields of an entry: x, y, dir [, move_timer [, shot_timer]])
+SEAQUEST_LISTS = dict(e_fish=(8, 32, (1, 8), 4), e_subs=(40, 32, (1, 8), 5), e_bullets=(72, 32, (1, 8), 3),
+                      f_bullets=(104, 4, (0, 8), 3), divers=(108, 4, (1, 8), 4))
+_SQ_PRESENT = 1 << 16
+
+
+def pack_seaquest_state(fields):
+    """Seaquest's state block, int32 [N, 112], from a dict: the head fields ``sub_x``, ``sub_y``, ``sub_or`` (1: faces +x),
+    ``oxygen`` (-1..200), ``diver_count``, ``surface``, ``shot_timer``, ``e_spawn_speed``, ``e_spawn_timer``,
+    ``d_spawn_timer``, ``move_speed``, ``ramp_index``, ``last_action``, ``ep_steps``, ``t`` [N], and per environment the five
+    lists in list order: ``f_bullets`` and ``e_bullets`` of (x, y, dir), ``e_fish`` and ``divers`` of (x, y, dir,
+    move_timer), ``e_subs`` of (x, y, dir, move_timer, shot_timer); dir is +1 / -1.  Refused before anything is written: a list
+    longer than its capacity, a field out of range, a sub whose rear cell is off the board, an enemy row outside 1..8."""
+    n = len(fields["sub_x"])
+    words = np.zeros((n, N.ENV_SEAQUEST_STATE_WORDS), np.uint32)
+    scalars = {name: np.asarray(fields[name]).astype(np.int64).reshape(n) for name in _SQ_RANGES}
+    for name, (lo, hi) in _SQ_RANGES.items():
+        if scalars[name].min() < lo or scalars[name].max() > hi:
+            raise ValueError(f"DeviceSeaquest.set_state: {name} outside [{lo}, {hi}]")
+    rear = np.where(scalars["sub_or"] != 0, scalars["sub_x"] - 1, scalars["sub_x"] + 1)
+    if (rear < 0).any() or (rear > 9).any():
+        raise ValueError("DeviceSeaquest.set_state: the cell behind the sub (sub_x - 1 facing +x, sub_x + 1 facing -x) is off the board")
+    for word, names in _SQ_SHIFTS.items():
+        for name, (sh, _) in names.items():
+            words[:, word] |= (scalars[name] << sh).astype(np.uint32)
+    words[:, 1] |= (scalars["oxygen"] + 1).astype(np.uint32)
+    for name, (first, capacity, (y_lo, y_hi), width) in SEAQUEST_LISTS.items():
+        per_env = fields[name]
+        if len(per_env) != n:
+            raise ValueError(f"DeviceSeaquest.set_state: {name} needs one list per environment")
+        for i, entries in enumerate(per_env):
+            if len(entries) > capacity:
+                raise ValueError(f"DeviceSeaquest.set_state: {name} holds {len(entries)} entries, the record at most {capacity}")
+            for j, entry in enumerate(entries):
+                entry = [int(v) for v in entry]
+                if len(entry) != width:
+                    raise ValueError(f"DeviceSeaquest.set_state: an entry of {name} has {width} fields")
+                x, y, direction = entry[:3]
+                timer, shot = (entry[3] if width > 3 else 0), (entry[4] if width > 4 else 0)
+                if not 0 <= x <= 9 or not y_lo <= y <= y_hi:
+                    raise ValueError(f"DeviceSeaquest.set_state: {name} entry at ({x}, {y}): x outside [0, 9] or row outside [{y_lo}, {y_hi}]")
+                if direction not in (1, -1):
+                    raise ValueError(f"DeviceSeaquest.set_state: {name} dir must be +1 or -1")
+                if not 0 <= timer <= 5 or not 0 <= shot <= 10:
+                    raise ValueError(f"DeviceSeaquest.set_state: {name} move_timer outside [0, 5] or shot_timer outside [0, 10]")
+                words[i, first + j] = x | (y << 4) | ((direction > 0) << 8) | (timer << 9) | (shot << 12) | _SQ_PRESENT
+    _counters(words, fields, n)
+    return words.view(np.int32)
+
+
+def unpack_seaquest_state(words):
+    """The inverse of ``pack_seaquest_state`` (``t`` as uint64; the lists as Python lists of tuples, one per environment)."""
+    w = np.ascontiguousarray(words).view(np.uint32).reshape(-1, N.ENV_SEAQUEST_STATE_WORDS)
+    out = {name: ((w[:, word] >> sh) & mask).astype(np.int32) for word, names in _SQ_SHIFTS.items() for name, (sh, mask) in names.items()}
+    out["oxygen"] = (w[:, 1] & 255).astype(np.int32) - 1
+    for name, (first, capacity, _, width) in SEAQUEST_LISTS.items():
+        out[name] = []
+        for row in w:
+            entries = []
+            for e in (int(v) for v in row[first:first + capacity]):
+                if e & _SQ_PRESENT:
+                    entries.append((e & 15, (e >> 4) & 15, 1 if (e >> 8) & 1 else -1, (e >> 9) & 7, (e >> 12) & 15)[:width])
+            out[name].append(entries)
+    out["ep_steps"] = w[:, 2].astype(np.int64)
+    out["t"] = w[:, 4].astype(np.uint64) | (w[:, 5].astype(np.uint64) << np.uint64(32))
+    return out
+
+
+def render_seaquest(fields):
+    """The observation of a Seaquest state dict, uint8 [N, 10, 10, 10]: sub | the cell behind it | friendly bullets | trail
+    cells of fish, enemy subs and divers (on the board only) | enemy bullets | fish | enemy subs | oxygen gauge | diver gauge |
+    divers.  As ``render``: only ``set_state`` draws on the host."""
+    n = len(fields["sub_x"])
+    img = np.zeros((n,) + SEAQUEST_OBS_SHAPE, np.uint8)
+    for i in range(n):
+        x, y, facing = int(fields["sub_x"][i]), int(fields["sub_y"][i]), int(fields["sub_or"][i])
+        img[i, y, x, 0] = 1
+        img[i, y, x - 1 if facing else x + 1, 1] = 1
+        for name, ch, trail in (("f_bullets", 2, False), ("e_bullets", 4, False), ("e_fish", 5, True), ("e_subs", 6, True), ("divers", 9, True)):
+            for entry in fields[name][i]:
+                ex, ey, direction = (int(v) for v in entry[:3])
+                img[i, ey, ex, ch] = 1
+                if trail and 0 <= ex - direction <= 9:
+                    img[i, ey, ex - direction, 3] = 1
+        oxygen, divers = int(fields["oxygen"][i]), int(fields["diver_count"][i])
+        img[i, 9, 0:max(0, oxygen * 10 // 200), 7] = 1
+        img[i, 9, 9 - divers:9, 8] = 1
+    return img
+
+
 class _DeviceEnv:
     """What the device games share.  A game sets ``OBS_SHAPE``, the names of its two entry points, the size of its minimal
     action set, the dtype and per-environment width of the draws its parity path takes (``_RESET_DRAWS`` / ``_STEP_DRAWS``:
@@ -315,6 +415,7 @@ class _DeviceEnv:
     _RESET = _STEP = None
     _MINIMAL_ACTIONS = 3
     _DRAW_DTYPE, _DRAW_WIDTH, _RESET_DRAWS, _STEP_DRAWS = None, 1, True, True
+    _STATE_WORDS = N.ENV_STATE_WORDS          # the width of a state record (Seaquest's is wider)
     _pack = _unpack = _render = None
 
     def __init__(self, n_envs, seed, device="cuda:0", sticky_action_prob=0.0, episode_timestep_limit=0, minimal_actions=False,
@@ -340,7 +441,7 @@ class _DeviceEnv:
         self._on_device = torch.cuda.device(self.device)
         dev = self.device
         with self._on_device:
-            self._state = torch.zeros((n_envs, N.ENV_STATE_WORDS), dtype=torch.int32, device=dev)
+            self._state = torch.zeros((n_envs, self._STATE_WORDS), dtype=torch.int32, device=dev)
             self._status = torch.zeros(1, dtype=torch.int32, device=dev)
             # two allocations: each ping-pong buffer starts 16-byte aligned whatever an image's size (700 bytes in Freeway)
             self._obs = tuple(torch.zeros((n_envs,) + self.OBS_SHAPE, dtype=dtype, device=dev) for _ in range(2))
@@ -406,11 +507,15 @@ class _DeviceEnv:
         self.check_status()
 
     def check_status(self):
-        """Raise if a step has seen an action outside [0, n_actions) since the last check (it acted as no-op)."""
+        """Raise if a step has seen an action outside [0, n_actions) since the last check (it acted as no-op), or if a game
+        with bounded lists (Seaquest) has dropped an append to a full one."""
         status = int(self._status.item())
-        if status & N.ENV_STATUS_BAD_ACTION:
+        if status & (N.ENV_STATUS_BAD_ACTION | N.ENV_STATUS_OVERFLOW):
             self._status.zero_()
+        if status & N.ENV_STATUS_BAD_ACTION:
             raise N.PrismError(f"{self._name}: a step was given an action outside [0, {self.n_actions}); it acted as no-op")
+        if status & N.ENV_STATUS_OVERFLOW:
+            raise N.PrismError(f"{self._name}: a step appended to a full entity list of the state record; the append was dropped")
 
     # ------------------------------------------------------------------ state, for tests and resume
     def get_state(self):
@@ -556,3 +661,31 @@ class DeviceSpaceInvaders(_DeviceEnv):
         """One step of every environment -> (next_obs, reward, done, truncated), as ``DeviceBreakout.step``.  ``u`` (tests):
         the sticky coins (float64) in place of the draws -- the game draws nothing else."""
         return self._step(actions, u, None)
+
+
+class DeviceSeaquest(_DeviceEnv):
+    OBS_SHAPE = SEAQUEST_OBS_SHAPE
+    _RESET, _STEP = "prism_env_seaquest_reset", "prism_env_seaquest_step"
+    _MINIMAL_ACTIONS = 6
+    _DRAW_DTYPE, _DRAW_WIDTH, _RESET_DRAWS = torch.uint8, 5, False
+    _STATE_WORDS = N.ENV_SEAQUEST_STATE_WORDS
+    _pack, _unpack, _render = staticmethod(pack_seaquest_state), staticmethod(unpack_seaquest_state), staticmethod(render_seaquest)
+
+    def reset(self):
+        """Start every environment: a fresh first episode, lifetime step count 0.  A reset draws nothing."""
+        return self._reset(None)
+
+    def step(self, actions, u=None, draws=None):
+        """One step of every environment -> (next_obs, reward, done, truncated), as ``DeviceBreakout.step``.  ``u`` /
+        ``draws`` (tests): the sticky coins (float64) and the spawns [n_envs, 5] -- enemy side 0 / 1, is_sub 0 / 1, row 1..8;
+        diver side 0 / 1, row 1..8 -- that a step which spawns uses, in place of the draws."""
+        return self._step(actions, u, self._draws(draws))
+
+    @staticmethod
+    def _draws(draws):
+        if draws is not None and not _is_dev(draws):
+            v = np.asarray(draws).astype(np.int64).reshape(-1)
+            v = v[:v.size - v.size % 5].reshape(-1, 5)          # (a wrong count is refused where the values are staged)
+            if v.size and (v.min() < 0 or v[:, [0, 1, 3]].max() > 1 or v[:, [2, 4]].min() < 1 or v[:, [2, 4]].max() > 8):
+                raise ValueError("DeviceSeaquest: draws must be (enemy side 0 / 1, is_sub 0 / 1, row 1..8, diver side 0 / 1, row 1..8)")
+        return draws

@@ -1,13 +1,13 @@
 """Environment and whole-loop rates on the GPU box:
-python tools/bench_env.py [--game breakout|freeway|asterix|spaceinvaders] [--sizes 64,512,4096] [--calls 4000] [--reps 3]
-1. DeviceBreakout.step / DeviceFreeway.step / DeviceAsterix.step / DeviceSpaceInvaders.step alone (prism_amd/envs.py) for N environments: device events around --calls back-to-back steps on one
+python tools/bench_env.py [--game breakout|freeway|asterix|spaceinvaders|seaquest] [--sizes 64,512,4096] [--calls 4000] [--reps 3]
+1. DeviceBreakout.step / DeviceFreeway.step / DeviceAsterix.step / DeviceSpaceInvaders.step / DeviceSeaquest.step alone (prism_amd/envs.py) for N environments: device events around --calls back-to-back steps on one
    stream with fixed device actions -- once as eager calls (launch and the Python call included: what a step of the loop
    pays), once as replays of a hipGraph of 64 captured steps (the kernel and its boundary).  Environment steps per second
    = N * steps / time.
 2. The loop  Agent.forward -> envs.step -> extend_batch -> Learner.step  (one VectorCollector step
    and one learner step per iteration) at N = --loop-n on BASELINE's c3 (configs[2]): with the device environments, and with
    the NumPy host restatement of the same rules (tests/env_ref.py HostBreakout, tests/freeway_ref.py HostFreeway, tests/asterix_ref.py HostAsterix,
-   tests/invaders_ref.py HostSpaceInvaders: the
+   tests/invaders_ref.py HostSpaceInvaders, tests/seaquest_ref.py HostSeaquest: the
    baseline of the comparison, not a product path) in the same loop.  Host clock around work that ends in a device synchronise, the two loops by turns, one warm-up
    run each, medians of --reps."""
 import argparse, contextlib, io, json, os, sys, tempfile, time
@@ -15,12 +15,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from prism_amd.collectors import VectorCollector
 from prism_amd.config import baseline_config
-from prism_amd.envs import DeviceAsterix, DeviceBreakout, DeviceFreeway, DeviceSpaceInvaders
+from prism_amd.envs import DeviceAsterix, DeviceBreakout, DeviceFreeway, DeviceSeaquest, DeviceSpaceInvaders
 from prism_amd.learner import Learner
 
 DEV = "cuda:0"
 GAMES = {"breakout": (DeviceBreakout, "MinAtar/Breakout-v0"), "freeway": (DeviceFreeway, "MinAtar/Freeway-v0"),
-         "asterix": (DeviceAsterix, "MinAtar/Asterix-v0"), "spaceinvaders": (DeviceSpaceInvaders, "MinAtar/SpaceInvaders-v0")}
+         "asterix": (DeviceAsterix, "MinAtar/Asterix-v0"), "spaceinvaders": (DeviceSpaceInvaders, "MinAtar/SpaceInvaders-v0"),
+         "seaquest": (DeviceSeaquest, "MinAtar/Seaquest-v0")}
 GRAPH_STEPS = 64          # even: the ping-pong buffers end where they began
 
 
@@ -93,6 +94,8 @@ def loop_rates(game, n, iters, host_iters, reps):
         from tests.asterix_ref import HostAsterix as Host
     elif game == "spaceinvaders":
         from tests.invaders_ref import HostSpaceInvaders as Host
+    elif game == "seaquest":
+        from tests.seaquest_ref import HostSeaquest as Host
     else:
         from tests.env_ref import HostBreakout as Host
     with tempfile.TemporaryDirectory() as tmp:
