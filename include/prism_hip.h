@@ -53,6 +53,7 @@ extern "C" {
 #define PRISM_STATUS_NONPOSITIVE_PMIN 2
 #define PRISM_STATUS_INGEST_DUP_STREAM 4   /* prism_replay_ingest: a stream id repeated in one call or outside the table */
 #define PRISM_STATUS_OBS_INEXACT 8         /* byte ring: a float that is not byte-exact was narrowed (stored as 0) */
+#define PRISM_STATUS_INGEST_BAD_CURSOR 16  /* prism_replay_ingest_cursor: the device cursor word was negative; nothing was written */
 
 /* prism_replay_ingest obs_kind */
 #define PRISM_OBS_F32 0
@@ -189,6 +190,23 @@ int prism_replay_ingest_ring(const prism_replay_desc *rp, int32_t ring_kind, int
                              const uint8_t *truncated, const int32_t *stream_ids, int64_t *stream_tab,
                              int32_t n_streams, float alpha, float eps, const prism_episode_desc *ep,
                              prism_stream_t stream);
+
+/* prism_replay_ingest_ring with the ring cursor in device memory, for a launch that is captured once and replayed: a
+ * by-value cursor would send every replay to the same slots.  `cursor` is a pair of device words in ping-pong and `slot`
+ * (0 | 1, by value: a captured graph bakes it, successive launches alternate it) names the one this launch reads:
+ *   serial0 = cursor[slot], first_slot = serial0 % capacity
+ *   everything the launch writes is, bit for bit, what prism_replay_ingest_ring writes when handed those two values
+ *   before the launch ends one lane stores cursor[slot ^ 1] = serial0 + n (an ordinary store)
+ * No thread reads cursor[slot ^ 1] and none writes cursor[slot]: the word a launch reads is never written while it runs,
+ * and the next launch, handed the other slot, sees the advanced word across the kernel boundary.  A negative serial0
+ * cannot be refused on the host (the call never reads device memory there): the launch writes nothing to the ring, copies
+ * the value unchanged to cursor[slot ^ 1] and raises the sticky bit PRISM_STATUS_INGEST_BAD_CURSOR in rp->status.
+ * Refused on the host: what prism_replay_ingest_ring refuses (its two cursor checks aside), a NULL cursor, any other slot. */
+int prism_replay_ingest_cursor(const prism_replay_desc *rp, int32_t ring_kind, int32_t n, int64_t *cursor /* device, [2] */,
+                               int32_t slot /* 0 | 1 */, const void *obs, const void *next_obs, int32_t obs_kind,
+                               const float *reward, const int32_t *action, const uint8_t *done, const uint8_t *truncated,
+                               const int32_t *stream_ids, int64_t *stream_tab, int32_t n_streams, float alpha, float eps,
+                               const prism_episode_desc *ep, prism_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Evaluation bookkeeping -- SyncAgentEvaluator.evaluate_agent (prism/evals/sync_agent_evaluator.py:37-59) for n_streams

@@ -15,6 +15,7 @@ PRISM_OK, PRISM_ERR_INVALID, PRISM_ERR_HIP, PRISM_ERR_UNSUPPORTED = 0, -1, -2, -
 PRISM_MAX_NSTEP = 15
 FLAG_DONE, FLAG_TRUNC, FLAG_HAS_NEXT = 1, 2, 4
 STATUS_NONPOSITIVE_PSUM, STATUS_NONPOSITIVE_PMIN, STATUS_INGEST_DUP_STREAM, STATUS_OBS_INEXACT = 1, 2, 4, 8
+STATUS_INGEST_BAD_CURSOR = 16
 OBS_F32, OBS_U8 = 0, 1
 RING_F32, RING_U8 = 0, 1          # storage kind of the ring's observation arrays (the prism_*_ring entry points)
 CLIP_NONE, CLIP_CLAMP = 0, 1
@@ -129,6 +130,8 @@ SIGNATURES = {
                                                     c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, _P(EpisodeDesc), c_vp]),
     "prism_replay_ingest_ring": (ctypes.c_int, [_P(ReplayDesc), c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
                                                  c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, _P(EpisodeDesc), c_vp]),
+    "prism_replay_ingest_cursor": (ctypes.c_int, [_P(ReplayDesc), c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                                   c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, _P(EpisodeDesc), c_vp]),
     "prism_eval_track": (ctypes.c_int, [_P(EvalDesc), c_i32, c_vp, c_vp, c_vp, c_vp]),
     "prism_per_sample": (ctypes.c_int, [_P(ReplayDesc), c_i64, c_i32, c_vp, c_u64, c_u64, c_f32, c_vp, c_vp,
                                          c_vp]),

@@ -459,6 +459,7 @@ class HipAgent:
         self.rng_counters = torch.zeros(3, dtype=torch.int64, device=dev)     # {PER draws, tau draws, acting draws}
         self._rng_ptr = self.rng_counters.data_ptr()
         self._act_graphs, self._act_ptrs, self._act_dev_draws, self._act_packed_at = {}, {}, 0, None
+        self._act_slots = {}          # estimate buffers of acting passes enqueued into a caller's capture (_enqueue_act)
         self._eg_word, self._eg_dev_steps = torch.zeros(1, dtype=torch.int64, device=dev), None
         # observations one prism_act_forward takes: what the workspace holds, in whole 16-row tiles for two-layer Q heads
         self._act_cap = (B // 16) * 16 if self.dims.n_heads > 0 and self.dims.head_layers == 2 else B
@@ -609,24 +610,13 @@ class HipAgent:
         """Sample + update + priority writeback as four launches on one GPU, five around an all-reduce (prism_step_front, fwd_bwd,
         prism_step_back); replayed from a hipGraph when the replay is full (its size is baked into
         the captured launches) and the RNG counters live on the device."""
-        if self.tau_rng != "philox" or buf.mass_rng != "philox":
-            raise RuntimeError("fused step draws its random numbers in-kernel (per_mass_rng/tau_rng = 'philox')")
-        if buf._index is None or buf._index.shape[0] != buf.buffer._batch_size:
-            buf._alloc_batch(buf.buffer._batch_size)
-        self.poll_status()
-        d = self._bind_fused(buf)
-        d.rng_counters = self._rng_ptr
-        d.offset = self._draw_offset               # device counter + what update() has consumed: never the same draw twice
+        d = self._fused_begin(buf)
         graphable = use_graph and not eager and buf._size == buf.capacity
         with torch.cuda.device(self.device):
             if not graphable:
                 self._launch_fused(buf, d)
             else:
-                # a captured graph bakes every by-value launch argument: hyper-parameters, seeds, beta / alpha, offsets
-                h, smp = d.hyper, buf.buffer._sampler
-                key = (id(buf), buf._size, self.world, h.lr, h.beta1, h.beta2, h.eps, h.max_grad_norm, h.grad_scale, self._opt_key,
-                       self.seed, buf.seed, smp._beta, smp._alpha, smp._eps, self._draw_offset, buf._draws,
-                       self.overlap_writeback)
+                key = self._fused_key(buf, d)
                 g = self._graphs.get(key)
                 if g is None:
                     self._graphs.clear()                        # arguments changed: older captures are stale
@@ -640,6 +630,30 @@ class HipAgent:
                     if len(g) == 2:          # data parallel, two graphs around an eagerly launched collective
                         self._allreduce()
                         g[1].replay()
+        return self._fused_mirror(buf)
+
+    def _fused_begin(self, buf):
+        """What every fused step does on the host before its launches: the sticky bits polled, the descriptor bound to the
+        buffer's static batch and to the device counters.  Returns the descriptor."""
+        if self.tau_rng != "philox" or buf.mass_rng != "philox":
+            raise RuntimeError("fused step draws its random numbers in-kernel (per_mass_rng/tau_rng = 'philox')")
+        if buf._index is None or buf._index.shape[0] != buf.buffer._batch_size:
+            buf._alloc_batch(buf.buffer._batch_size)
+        self.poll_status()
+        d = self._bind_fused(buf)
+        d.rng_counters = self._rng_ptr
+        d.offset = self._draw_offset               # device counter + what update() has consumed: never the same draw twice
+        return d
+
+    def _fused_key(self, buf, d):
+        """Everything a captured ``_launch_fused`` bakes by value: hyper-parameters, seeds, beta / alpha, offsets."""
+        h, smp = d.hyper, buf.buffer._sampler
+        return (id(buf), buf._size, self.world, h.lr, h.beta1, h.beta2, h.eps, h.max_grad_norm, h.grad_scale, self._opt_key,
+                self.seed, buf.seed, smp._beta, smp._alpha, smp._eps, self._draw_offset, buf._draws, self.overlap_writeback)
+
+    def _fused_mirror(self, buf):
+        """The host mirrors of one fused step that ran (eagerly, from the step graph, or inside a larger replay): the two
+        device draw counters and what ``_step_done`` keeps.  Returns the TD errors."""
         self._fused_tau += 3 * max(self.dims.n_tau, self.dims.n_tau_next) * self._B
         buf._fused_draws += self._B
         return self._step_done()
@@ -945,13 +959,7 @@ class HipAgent:
             if st["pin_in"] is not None:
                 st["pin_np"] = [t.numpy() for t in st["pin_in"]]
             self._act_graphs[key] = st
-        if self._act_dev_draws != self._act_draws:          # eager calls / an explore branch moved the host count on
-            self.rng_counters[2] = self._act_draws
-            self._act_dev_draws = self._act_draws
-        if skey[0] == "egreedy" and self._eg_dev_steps != sel.epsilon.current_step:
-            # the first call, an eager call, a loaded checkpoint: the selector's count is the position, the device follows
-            self._eg_word[0] = int(sel.epsilon.current_step)
-            self._eg_dev_steps = sel.epsilon.current_step
+        self._seed_act_words(skey, sel)          # eager calls / an explore branch moved the host count on
         k = st["calls"] & 3
         if on_host:
             if st["calls"] >= 4:
@@ -999,6 +1007,54 @@ class HipAgent:
         self._act_raw = (st["z"], st["qb"], n, st["n_pad"], st["T"])
         self._act_scores = st["scores"]
         return _Actions.wrap(st["act"][k], st["pin_out"][k], st["ev"][k])
+
+    def _seed_act_words(self, skey, sel):
+        """Before a launch that binds the device words: ``rng_counters[2]`` follows ``_act_draws`` and the epsilon-greedy
+        word the selector's ``current_step`` whenever an eager call, an explore branch, an evaluation or a loaded checkpoint
+        has moved the host's count on (a store on the stream, only then)."""
+        if self._act_dev_draws != self._act_draws:
+            self.rng_counters[2] = self._act_draws
+            self._act_dev_draws = self._act_draws
+        if skey[0] == "egreedy" and self._eg_dev_steps != sel.epsilon.current_step:
+            self._eg_word[0] = int(sel.epsilon.current_step)
+            self._eg_dev_steps = sel.epsilon.current_step
+
+    def _act_slot(self, n, skey):
+        """The estimate buffers of an acting pass that is enqueued without a graph of its own, per (n, selector)."""
+        slots, key = self._act_slots, (n, skey)
+        st = slots.get(key)
+        if st is None:
+            z, qb, n_pad, T = self._act_buffers(n)
+            scores = torch.empty((n, self.dims.n_actions), device=self.device) if skey[0] in self._SCORED else None
+            st = slots[key] = dict(z=z, qb=qb, n_pad=n_pad, T=T, scores=scores)
+        return st
+
+    def _enqueue_act(self, obs, act, skey, current):
+        """One acting pass, enqueue only (safe inside a stream capture): ``prism_act_forward`` on the contiguous float32
+        device observations ``obs`` and the selector kernel of ``skey`` into the device int64 tensor ``act``.  No pinned host
+        copy, no graph of its own; the draws come from ``rng_counters[2]`` and the epsilon-greedy rows from the device word,
+        exactly as ``_forward_graph`` binds them (``_seed_act_words`` first, outside any capture).  ``current``: the packed
+        weight copies are those of the parameters (a pass behind another with no update between).  No host mirror moves:
+        ``_act_mirror`` does that, once per pass that ran."""
+        n = int(obs.shape[0])
+        st = self._act_slot(n, skey)
+        ptr = self.rng_counters.data_ptr()
+        self._act_launch(obs, n, st["T"], None, 0, st["z"], st["qb"], rng_counters=ptr,
+                         act_flags=N.ACT_WEIGHTS_CURRENT if current else 0)
+        self._select_launch(skey, st["z"], st["qb"], n, st["n_pad"], st["T"], act, None, st["scores"], rng_counters=ptr,
+                            eg_word=self._eg_word.data_ptr())
+
+    def _act_mirror(self, n, skey, sel):
+        """The host mirrors of one enqueued acting pass of ``n`` observations that ran, as ``_forward_graph`` applies them."""
+        st = self._act_slot(n, skey)
+        self._act_packed_at = self._param_version()
+        self._act_draws += st["T"] * n
+        self._act_dev_draws = self._act_draws
+        if skey[0] == "egreedy":          # (by arithmetic: the launch has added n to the device's count)
+            sel.epsilon.current_step += n
+            self._eg_dev_steps = sel.epsilon.current_step
+        self._act_raw = (st["z"], st["qb"], n, st["n_pad"], st["T"])
+        self._act_scores = st["scores"]
 
     def _forward_piece(self, obs, sel, row0, n_call):
         """Rows ``row0 ..`` of an eager call of ``n_call`` observations: estimates, then the selector on them."""

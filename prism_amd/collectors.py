@@ -41,12 +41,7 @@ class VectorCollector:
         """Whole environment steps until at least ``n_timesteps`` rows are stored; returns the rows stored.  ``random``:
         uniform actions from the collector's generator instead of ``agent.forward``."""
         envs = self.envs
-        if self._buffer is not exp_buffer:
-            exp_buffer.track_episodes(self.ema)
-            self._buffer = exp_buffer
-        if self._obs is None:
-            self._obs = envs.observe() if self._started else envs.reset()
-            self._started = True
+        self._begin(exp_buffer)
         got = 0
         while got < n_timesteps:
             obs = self._obs
@@ -58,6 +53,16 @@ class VectorCollector:
             got += n
         self.rows += got
         return got
+
+    def _begin(self, exp_buffer):
+        """What comes before the first environment step into ``exp_buffer``: episode tracking on, and the observations to act
+        on -- a reset, or (a restored run goes on) what the environments show."""
+        if self._buffer is not exp_buffer:
+            exp_buffer.track_episodes(self.ema)
+            self._buffer = exp_buffer
+        if self._obs is None:
+            self._obs = self.envs.observe() if self._started else self.envs.reset()
+            self._started = True
 
     def log(self, logger):
         """The reference's "Training Reward" (None until the first episode has ended) and the episode count: one small

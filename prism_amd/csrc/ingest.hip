@@ -5,8 +5,9 @@
 
 using namespace prism;
 
-// The checks both entry points run (a macro: the message names the entry point that was called).
-#define INGEST_CHECK_ARGS()                                                                                             \
+// The checks both entry points run (a macro: the message names the entry point that was called).  In two halves around
+// the cursor's own: the cursor form (prism_replay_ingest_cursor) reads the cursor on the device and runs the halves alone.
+#define INGEST_CHECK_SHAPE()                                                                                            \
     do {                                                                                                                \
         int rc = check_ring(rp, false);                                                                                 \
         if (rc) return rc;                                                                                              \
@@ -16,13 +17,23 @@ using namespace prism;
         PRISM_CHECK_ARG(n_streams >= 1 && n_streams <= INGEST_MAX_STREAMS, "n_streams must be in [1, 65536]");          \
         PRISM_CHECK_ARG(obs_kind == PRISM_OBS_F32 || obs_kind == PRISM_OBS_U8,                                          \
                         "obs_kind must be PRISM_OBS_F32 or PRISM_OBS_U8");                                              \
-        PRISM_CHECK_ARG(first_slot >= 0 && first_slot < rp->capacity, "first_slot must be in [0, capacity)");           \
-        PRISM_CHECK_ARG(serial0 >= 0 && serial0 % rp->capacity == first_slot,                                           \
-                        "serial0 must be >= 0 and serial0 % capacity == first_slot");                                   \
+    } while (0)
+
+#define INGEST_CHECK_ARRAYS()                                                                                           \
+    do {                                                                                                                \
         PRISM_CHECK_ARG(obs && next_obs && reward && action && done && truncated, "null transition array");             \
         PRISM_CHECK_ARG(stream_tab != nullptr, "null stream_tab");                                                      \
         PRISM_CHECK_ARG(stream_ids != nullptr || n <= n_streams,                                                        \
                         "stream_ids NULL (row i is stream i) needs n <= n_streams");                                    \
+    } while (0)
+
+#define INGEST_CHECK_ARGS()                                                                                             \
+    do {                                                                                                                \
+        INGEST_CHECK_SHAPE();                                                                                           \
+        PRISM_CHECK_ARG(first_slot >= 0 && first_slot < rp->capacity, "first_slot must be in [0, capacity)");           \
+        PRISM_CHECK_ARG(serial0 >= 0 && serial0 % rp->capacity == first_slot,                                           \
+                        "serial0 must be >= 0 and serial0 % capacity == first_slot");                                   \
+        INGEST_CHECK_ARRAYS();                                                                                          \
     } while (0)
 
 // ... and what the tracked launch adds on its episode descriptor
@@ -128,6 +139,38 @@ extern "C" int prism_replay_ingest_ring(const prism_replay_desc *rp, int32_t rin
     } else {
         if (ep) hipLaunchKernelGGL(replay_ingest_tracked_kernel, grid, block, 0, st, *rp, L.a, *ep);
         else hipLaunchKernelGGL(replay_ingest_kernel, grid, block, 0, st, *rp, L.a);
+    }
+    PRISM_CHECK_LAUNCH();
+    return PRISM_OK;
+}
+
+// prism_replay_ingest_ring with the ring cursor read on the device (ingest_kernels.h, "the cursor form"): the launch takes
+// serial0 = cursor[slot], first_slot = serial0 % capacity, and leaves serial0 + n in cursor[slot ^ 1].  `slot` is by value:
+// a captured graph bakes it, successive launches alternate it.
+extern "C" int prism_replay_ingest_cursor(const prism_replay_desc *rp, int32_t ring_kind, int32_t n, int64_t *cursor,
+                                          int32_t slot, const void *obs, const void *next_obs, int32_t obs_kind,
+                                          const float *reward, const int32_t *action, const uint8_t *done,
+                                          const uint8_t *truncated, const int32_t *stream_ids, int64_t *stream_tab,
+                                          int32_t n_streams, float alpha, float eps, const prism_episode_desc *ep,
+                                          prism_stream_t stream) {
+    INGEST_CHECK_SHAPE();
+    PRISM_CHECK_ARG(cursor != nullptr, "null cursor");
+    PRISM_CHECK_ARG(slot == 0 || slot == 1, "slot must be 0 or 1");
+    INGEST_CHECK_ARRAYS();
+    PRISM_CHECK_RING_KIND(rp, ring_kind);
+    if (ep) INGEST_CHECK_EPISODES();
+    // (first_slot / serial0 of the plan are placeholders: the kernel overwrites them with what it reads)
+    const IngestLaunch L = ingest_plan(rp, n, 0, 0, obs, next_obs, obs_kind, reward, action, done, truncated, stream_ids,
+                                       stream_tab, n_streams, alpha, eps, ring_kind);
+    const IngestCursor c{cursor, slot};
+    const dim3 grid((ep ? 2 : 1) + L.row_wgs), block(L.threads);
+    hipStream_t st = (hipStream_t)stream;
+    if (ring_kind == PRISM_RING_U8) {
+        if (ep) hipLaunchKernelGGL(byte_ring_cursor_ingest_tracked_kernel, grid, block, 0, st, *rp, L.a, *ep, c);
+        else hipLaunchKernelGGL(byte_ring_cursor_ingest_kernel, grid, block, 0, st, *rp, L.a, c);
+    } else {
+        if (ep) hipLaunchKernelGGL(cursor_ingest_tracked_kernel, grid, block, 0, st, *rp, L.a, *ep, c);
+        else hipLaunchKernelGGL(cursor_ingest_kernel, grid, block, 0, st, *rp, L.a, c);
     }
     PRISM_CHECK_LAUNCH();
     return PRISM_OK;

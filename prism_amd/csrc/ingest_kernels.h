@@ -425,4 +425,60 @@ static __global__ __launch_bounds__(1024) void byte_ring_ingest_tracked_kernel(p
     replay_ingest_body<true, PRISM_RING_U8>(rp, a, ep, threadIdx.x, blockDim.x, blockIdx.x, gridDim.x);
 }
 
+// ---- the cursor form (prism_replay_ingest_cursor): the ring cursor is read from device memory, so a captured launch
+// writes other slots on every replay.  cursor[2] is a pair of words in ping-pong: this launch READS cursor[slot] -- the
+// write serial of its first row -- and one lane WRITES cursor[slot ^ 1] = serial0 + n, an ordinary store.  No thread reads
+// the word the launch writes and none writes the word it reads, so every workgroup sees the same serial0 whenever it
+// runs; the next launch is handed the other `slot` and sees the advanced word across the kernel boundary.  A negative
+// serial0 (nothing on the host could refuse it): the ring is left alone, the word is passed on, the sticky bit is raised.
+struct IngestCursor {
+    int64_t *cursor;                                // device, [2]
+    int32_t slot;                                   // 0 | 1: the word this launch reads
+};
+
+// The four words that differ from the by-value launch are handed to the body in a copy of the argument struct made of
+// scalars (never indexed, never addressed past inlining: it stays in registers like the kernel arguments themselves).
+template <bool TRACKED, int RING>
+static __device__ __forceinline__ void cursor_ingest_body(const prism_replay_desc &rp, const IngestArgs &a,
+                                                                 const prism_episode_desc &ep, const IngestCursor &c,
+                                                                 const int tid, const int bd, const unsigned wg,
+                                                                 const unsigned n_wgs) {
+    const int64_t serial0 = c.cursor[c.slot];
+    if (serial0 < 0) {
+        if (wg == 0 && tid == 0) {
+            c.cursor[c.slot ^ 1] = serial0;
+            atomicOr(rp.status, PRISM_STATUS_INGEST_BAD_CURSOR);
+        }
+        return;
+    }
+    if (wg == 0 && tid == 0) c.cursor[c.slot ^ 1] = serial0 + a.n;
+    IngestArgs b = a;
+    b.serial0 = serial0;
+    b.first_slot = serial0 % rp.capacity;
+    replay_ingest_body<TRACKED, RING>(rp, b, ep, tid, bd, wg, n_wgs);
+}
+
+static __global__ __launch_bounds__(1024) void cursor_ingest_kernel(prism_replay_desc rp, IngestArgs a,
+                                                                           IngestCursor c) {
+    cursor_ingest_body<false, PRISM_RING_F32>(rp, a, prism_episode_desc{}, c, threadIdx.x, blockDim.x, blockIdx.x,
+                                                     gridDim.x);
+}
+
+static __global__ __launch_bounds__(1024) void cursor_ingest_tracked_kernel(prism_replay_desc rp, IngestArgs a,
+                                                                                   prism_episode_desc ep, IngestCursor c) {
+    cursor_ingest_body<true, PRISM_RING_F32>(rp, a, ep, c, threadIdx.x, blockDim.x, blockIdx.x, gridDim.x);
+}
+
+static __global__ __launch_bounds__(1024) void byte_ring_cursor_ingest_kernel(prism_replay_desc rp, IngestArgs a,
+                                                                              IngestCursor c) {
+    cursor_ingest_body<false, PRISM_RING_U8>(rp, a, prism_episode_desc{}, c, threadIdx.x, blockDim.x, blockIdx.x,
+                                                    gridDim.x);
+}
+
+static __global__ __launch_bounds__(1024) void byte_ring_cursor_ingest_tracked_kernel(prism_replay_desc rp, IngestArgs a,
+                                                                                      prism_episode_desc ep,
+                                                                                      IngestCursor c) {
+    cursor_ingest_body<true, PRISM_RING_U8>(rp, a, ep, c, threadIdx.x, blockDim.x, blockIdx.x, gridDim.x);
+}
+
 }  // namespace prism

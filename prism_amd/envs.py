@@ -494,8 +494,23 @@ class _DeviceEnv:
                                                  N.current_stream_handle()), self._STEP)
             if staged:
                 self._stage.submit()
-        self._parity ^= 1
+        self._step_mirror()
         return self._next_obs, self._reward, self._done, self._truncated
+
+    def _enqueue_step(self, act, parity):
+        """One step of every environment on the current stream, enqueue only (safe inside a stream capture): the game's own
+        draws, ``act`` a contiguous device int64 tensor read in place, acting on ping-pong buffer ``parity`` and writing the
+        other.  No host state moves: ``_step_mirror`` does that, once per launch that ran."""
+        self._need_started("step")
+        if not (_is_dev(act) and act.dtype == torch.int64 and act.is_contiguous() and act.numel() == self.n_envs):
+            raise ValueError(f"{self._name}: an enqueued step takes a contiguous device int64 tensor, one action per environment")
+        given = (None,) if self._STEP_DRAWS else ()
+        N.check(getattr(N.lib(), self._STEP)(self._desc_ref, N.ptr(act), None, *given, int(parity),
+                                             N.current_stream_handle()), self._STEP)
+
+    def _step_mirror(self):
+        """The host side of one step: the observation to act on next is in the other buffer."""
+        self._parity ^= 1
 
     def close(self):
         """Drains the staging rotation and checks the device status word (one small device-to-host copy)."""

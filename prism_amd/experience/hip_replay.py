@@ -225,6 +225,10 @@ class HipReplayBuffer:
         self._ep = None            # dict(ema, count_first_step) while tracking
         self._ep_return = self._ep_length = self._ep_words = self._ep_stats = self._ep_counts = None
         self._ep_desc = self._ep_desc_ref = None
+        # the cursor form of extend_batch (a captured launch): the two device words, and (slot, value) the host knows one of
+        # them to hold -- None or stale after anything else has moved the count
+        self._cursor_words = None
+        self._cursor_known = None
 
     # ------------------------------------------------------------------ allocation
     def _allocate(self, obs_shape):
@@ -587,8 +591,65 @@ class HipReplayBuffer:
         self._call(name, *head, n, first, serial, N.ptr(dev["obs"]), N.ptr(dev["next"]), kind,
                    N.ptr(dev["reward"]), N.ptr(dev["action"]), N.ptr(dev["done"]), N.ptr(dev["trunc"]), N.ptr(dev["ids"]),
                    N.ptr(tab), tab.numel(), smp._alpha, smp._eps, *tail, submit=self._ing if staged else None)
-        # host mirrors, by arithmetic; the slots get ids from a private (negative) range: no Timestep id matches them
-        cap = self.capacity
+        return self._mirror_rows(n)                    # host mirrors, by arithmetic
+
+    # ------------------------------------------------------------------ the cursor form: a launch a hipGraph can replay
+    def seed_cursor(self, slot):
+        """Before a launch (or a replay whose first launch) reads ``cursor[slot]``: make the word hold the host's count.  A
+        store on the stream, and only when an eager ingest, a bulk load, a restore -- or a caller that picks another slot --
+        has moved the count since the last cursor launch (the rule ``HipAgent._forward_graph`` follows for its counters)."""
+        if self._cursor_words is None:
+            self._cursor_words = torch.zeros(2, dtype=torch.int64, device=self.device)
+        if self._cursor_known != (slot, self._serial):
+            self._cursor_words[slot] = self._serial
+            self._cursor_known = (slot, self._serial)
+
+    def enqueue_extend_cursor(self, slot, obs, next_obs, action, reward, done, truncated):
+        """``extend_batch`` as ONE launch that takes the ring cursor from ``cursor[slot]`` on the device and leaves the
+        advanced count in ``cursor[slot ^ 1]`` (``prism_replay_ingest_cursor``): enqueue only, safe inside a stream capture.
+        Device tensors only, used in place (observations float32 or uint8, ``action`` int32, ``reward`` float32, ``done`` /
+        ``truncated`` uint8, all contiguous), row i is stream i; the ring, the stream table and (when tracking) the episode
+        arrays must already be there and sized -- nothing is allocated, staged or converted here, and no host mirror moves
+        (``extend_cursor_mirror`` does that, once per launch that ran)."""
+        n = int(obs.shape[0])
+        if self._desc is None or self._stream_tab is None or self._stream_tab.numel() < n or self._cursor_words is None:
+            raise RuntimeError("enqueue_extend_cursor: the ring, a stream table of n entries and the cursor words (seed_cursor) "
+                               "must exist before the launch is enqueued")
+        if slot not in (0, 1) or not 1 <= n <= self.capacity:
+            raise ValueError("enqueue_extend_cursor: slot must be 0 or 1 and n in [1, capacity]")
+        if self._n_staged:
+            raise RuntimeError("enqueue_extend_cursor: rows staged by extend() come first (flush())")
+        if self.reward_clipping_type == "sign":
+            raise ValueError('enqueue_extend_cursor: reward_clipping_type "sign" is not reproduced (see extend_batch)')
+        want = dict(obs=(torch.float32, torch.uint8), next_obs=(obs.dtype,), action=(torch.int32,), reward=(torch.float32,),
+                    done=(torch.uint8,), truncated=(torch.uint8,))
+        given = dict(obs=obs, next_obs=next_obs, action=action, reward=reward, done=done, truncated=truncated)
+        for k, x in given.items():
+            rows = n * self.obs_elems if k in ("obs", "next_obs") else n
+            if not (_is_dev(x) and x.dtype in want[k] and x.is_contiguous() and x.numel() == rows):
+                raise ValueError(f"enqueue_extend_cursor: {k} must be a contiguous device tensor of {rows} elements, dtype "
+                                 f"{' / '.join(str(t) for t in want[k])}")
+        ep = None
+        if self._ep is not None or self._clip != N.CLIP_NONE:
+            if self._ep_desc is None:
+                self._bind_episode_desc()
+            ep = self._ep_desc_ref
+        smp, tab = self.buffer._sampler, self._stream_tab
+        self._call("prism_replay_ingest_cursor", self._ring_kind, n, N.ptr(self._cursor_words), slot, N.ptr(obs),
+                   N.ptr(next_obs), N.OBS_F32 if obs.dtype == torch.float32 else N.OBS_U8, N.ptr(reward), N.ptr(action),
+                   N.ptr(done), N.ptr(truncated), None, N.ptr(tab), tab.numel(), smp._alpha, smp._eps, ep)
+
+    def extend_cursor_mirror(self, n, slot):
+        """The host mirrors of one cursor launch of ``n`` rows that read ``cursor[slot]``, by ``extend_batch``'s arithmetic."""
+        first = self._mirror_rows(n)
+        self._cursor_known = (slot ^ 1, self._serial)
+        return first
+
+    def _mirror_rows(self, n):
+        """``n`` rows went into the ring behind the writer: cursor, serial, size, and the slots' ids from a private
+        (negative) range -- no Timestep id matches them.  Returns the first slot."""
+        w, cap, serial = self.buffer._writer, self.capacity, self._serial
+        first = w._cursor
         own = np.arange(-2 - serial, -2 - serial - n, -1, dtype=np.int64)
         head = min(n, cap - first)
         self._slot_id[first:first + head] = own[:head]
@@ -664,6 +725,9 @@ class HipReplayBuffer:
         if bits & N.STATUS_OBS_INEXACT:
             raise RuntimeError("extend_batch: a device-side float observation was not byte-exact (+0.0, 1.0 .. 255.0); "
                                "obs_storage='uint8' stored it as 0")
+        if bits & N.STATUS_INGEST_BAD_CURSOR:
+            raise RuntimeError("enqueue_extend_cursor: a launch read a negative ring cursor from the device (it wrote nothing "
+                               "to the ring)")
 
     def update_priority(self, indices, priorities, take_abs=False):
         if not self.use_per:

@@ -32,6 +32,9 @@ class Learner:
         self.time_phases = True
         self.fused = True
         self.hip_graph = True
+        self.captured_loop = False
+        self.captured_iterations = 0
+        self._captured = None
         self._resumed = False
 
     def configure(self, config, collector=None, obs_shape=None, n_actions=None, process_group=None, eval_envs=None):
@@ -60,6 +63,11 @@ class Learner:
         self.fused = bool(getattr(config, "fused_step", True)) and \
             getattr(config, "per_mass_rng", "philox") == "philox" and getattr(config, "tau_rng", "philox") == "philox"
         self.hip_graph = bool(getattr(config, "hip_graph", True))
+        # ... / run a whole iteration (k x (act, environment step, ingest) + the step) as ONE hipGraph replay once its
+        # conditions hold (prism_amd/captured_loop.py; off by default, and the loop is the eager one wherever they do not)
+        self.captured_loop = bool(getattr(config, "captured_loop", False))
+        self.captured_iterations = 0
+        self._captured = None
         self._resumed = False
         self.checkpointer.attach(self, config)              # config.backup_checkpoints: the hourly exact-resume snapshot
         self.evaluator = None
@@ -78,12 +86,7 @@ class Learner:
             if self.use_per:
                 buf.buffer._sampler._beta = 0.5
             td = agent.step_fused(buf, eager=eager, use_graph=self.hip_graph)
-            self.cumulative_model_updates += 1
-            self.timesteps_since_target_model_update += timesteps_this_iteration
-            if self.use_target_network and \
-                    self.timesteps_since_target_model_update >= self.target_network_update_period:
-                agent.sync_target_model()
-                self.timesteps_since_target_model_update = 0
+            self._after_fused_update(timesteps_this_iteration)
             return td
         t0 = time.perf_counter() if tp else 0.0
         if self.cumulative_model_updates == 1 and agent.get_static_batch() is not None:
@@ -111,6 +114,40 @@ class Learner:
             self.loggables["Component Update Time"].append(t3 - t2)
         return new_per_weights
 
+    def _after_fused_update(self, timesteps_this_iteration):
+        """Behind every fused update, eager or inside a captured iteration: the counters and the target sync on its
+        timestep period (learner.py:122-124) -- an eager launch between two replays."""
+        self.cumulative_model_updates += 1
+        self.timesteps_since_target_model_update += timesteps_this_iteration
+        if self.use_target_network and self.timesteps_since_target_model_update >= self.target_network_update_period:
+            self.agent.sync_target_model()
+            self.timesteps_since_target_model_update = 0
+
+    # ------------------------------------------------------------------ the captured iteration (config.captured_loop)
+    def _captured_iteration(self):
+        """One iteration as one graph replay: the rows it collected, or None when the knob is off or this iteration has to
+        run eagerly (``captured_loop_refusal``)."""
+        if not self.captured_loop:
+            return None
+        if self._captured is None:
+            from prism_amd.captured_loop import CapturedLoop
+            self._captured = CapturedLoop(self)
+        n = self._captured.run()
+        if n is not None:
+            self.captured_iterations += 1
+            self._after_fused_update(n)
+        return n
+
+    def captured_loop_refusal(self):
+        """Why the loop is not running as captured iterations, in one line (the condition that failed at the last iteration,
+        or fails now if none has run); None when it is captured."""
+        if not self.captured_loop:
+            return "config.captured_loop is off"
+        if self._captured is None:
+            from prism_amd.captured_loop import CapturedLoop
+            self._captured = CapturedLoop(self)
+        return self._captured.reason if self._captured.judged else self._captured.check()[0]
+
     # ------------------------------------------------------------------ the outer loop
     def _learn(self):
         col = self.timestep_collector
@@ -123,16 +160,22 @@ class Learner:
         self._resumed = False
         while self.cumulative_timesteps < self.timestep_limit:
             loop_start = time.perf_counter()
-            n = col.collect_timesteps(self.timesteps_per_iteration, self.agent, self.experience_buffer)
-            dt = time.perf_counter() - loop_start
-            self.loggables["Timestep Collection Time"].append(dt)
-            if n > 0:
+            n = self._captured_iteration()
+            captured = n is not None
+            if captured:                       # collection and update were one replay: one timer, read at the bottom
                 self.cumulative_timesteps += n
                 self.timesteps_since_report += n
-                sps = n / dt
-                self.collected_steps_per_second_ema = sps if self.collected_steps_per_second_ema is None else \
-                    self.collected_steps_per_second_ema * 0.9 + 0.1 * sps
-            self.step(n)
+            else:
+                n = col.collect_timesteps(self.timesteps_per_iteration, self.agent, self.experience_buffer)
+                dt = time.perf_counter() - loop_start
+                self.loggables["Timestep Collection Time"].append(dt)
+                if n > 0:
+                    self.cumulative_timesteps += n
+                    self.timesteps_since_report += n
+                    sps = n / dt
+                    self.collected_steps_per_second_ema = sps if self.collected_steps_per_second_ema is None else \
+                        self.collected_steps_per_second_ema * 0.9 + 0.1 * sps
+                self.step(n)
             self.checkpointer.checkpoint(self.cumulative_timesteps)
             if self.evaluator is not None and \
                     self.evaluator.maybe_evaluate_agent(n, self.cumulative_timesteps) is not None:
@@ -147,6 +190,9 @@ class Learner:
                 sps = n / it
                 self.overall_steps_per_second_ema = sps if self.overall_steps_per_second_ema is None else \
                     self.overall_steps_per_second_ema * 0.9 + 0.1 * sps
+                if captured:
+                    self.collected_steps_per_second_ema = sps if self.collected_steps_per_second_ema is None else \
+                        self.collected_steps_per_second_ema * 0.9 + 0.1 * sps
 
     def report(self):
         self._log()
