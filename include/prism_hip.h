@@ -838,10 +838,20 @@ int prism_sync_target(float *target_params, const float *params, int64_t n_param
  *             kernel has ended (the start of a kernel invalidates).  No kernel ever reads a peer's gradient word that is
  *             written while it runs.
  * Failure: a wait that is not through after `wait_seconds` (0 = 30 s; RCCL would wait for ever, a rank that saves a
- * checkpoint or captures a graph can stall for seconds) gives up: it sets flags[rank][PRISM_MAX_PEERS] (sticky), ORs
- * PRISM_WS_STATUS_COLLECTIVE_TIMEOUT into *poison and into *host_status when given, and every later kernel of the
- * collective returns at once, as do prism_step_back / prism_learner_clip_adam of a learner whose workspace status word is
- * `poison`: a timed-out step applies NO update (never a partial sum) and the host sees the bit at its next poll.
+ * checkpoint or captures a graph can stall for seconds) gives up: it sets flags[rank][PRISM_MAX_PEERS] (sticky; bit 0),
+ * stores the mark 2 into flags[s][PRISM_MAX_PEERS] of EVERY peer s (a plain system-scope store, made in the launch that
+ * gave up, i.e. before this rank's next announcement), ORs PRISM_WS_STATUS_COLLECTIVE_TIMEOUT into *poison and into
+ * *host_status when given, and every later kernel of the collective returns at once, as do prism_step_back /
+ * prism_learner_clip_adam of a learner whose workspace status word is `poison`.  The rank goes on announcing its phases, so
+ * its peers do not wait out their own bound on it; but every wait, once through, reads the own sticky slot, and a peer
+ * that finds it set -- by its own wait or by a mark -- poisons ITS step in the same way before the launch behind the wait
+ * starts.  So: the step of the rank that timed out applies NO update (never a partial sum); neither does the step of any
+ * peer whose next wait ends after the mark has landed, which is every peer when the give-up was in phase 1 or 2 (a peer
+ * cannot pass phase 3 without this rank's phase-3 announcement, and that is stored after the mark).  A rank that gives
+ * up in phase 3 has gathered everything, and a peer may be through its last wait already: that peer applies the step's
+ * (complete) update and is stopped at the first wait of the next step.  The state is terminal on every rank: the sticky
+ * slots are never cleared, every wait kernel re-raises the poison bit while its slot is set, and the host sees the bit at
+ * its next poll; the way out is a new set of flag arrays on all ranks together.
  * ------------------------------------------------------------------------------------------ */
 #define PRISM_MAX_PEERS 8
 #define PRISM_DIRECT_FLAG_WORDS (PRISM_MAX_PEERS + 2)

@@ -490,6 +490,8 @@ class HipAgent:
         reference's draw order (parity tests); otherwise drawn in-kernel (Philox) or with
         ``torch.rand`` when ``config.tau_rng == 'torch'``."""
         self.train()
+        if self.world > 1:
+            self.poll_status()
         obs = batch["observation"]
         B = int(obs.shape[0])
         if self._B != B:
@@ -1082,13 +1084,16 @@ class HipAgent:
         return (self.n_updates, self._param_epoch)
 
     def _raise_status(self, bits):
+        self._graphs = {}
+        if bits & N.WS_STATUS_COLLECTIVE_TIMEOUT:
+            # terminal: the sticky slot of the flag array keeps the reduce kernels off, so the bit that keeps clip + Adam off
+            # stays where it is, in the workspace and in the pinned mirror -- every later poll raises again
+            raise pdist.CollectiveTimeout("prism_amd: the direct all-reduce gave up on a peer; the step that hit it applied no "
+                                          "update and the replicas may have diverged -- restore a checkpoint, then "
+                                          "reset_collective() on all ranks together")
         self._status.clear()
         if self._B is not None:
             self.workspace.view(torch.int32)[N.WS_STATUS_WORD] = 0
-        self._graphs = {}
-        if bits & N.WS_STATUS_COLLECTIVE_TIMEOUT:
-            raise pdist.CollectiveTimeout("prism_amd: the direct all-reduce gave up on a peer; the step that hit it applied no "
-                                          "update and the replicas may have diverged -- restore a checkpoint")
         self.fuse_tail = False
         raise RuntimeError("prism_amd: a fused-tail grid barrier timed out (is the GPU shared with another process?); "
                            "the last steps are incomplete -- restore a checkpoint; fuse_tail is now off")
@@ -1101,6 +1106,21 @@ class HipAgent:
         bits = self._status.bits()
         if bits:
             self._raise_status(bits)
+
+    def reset_collective(self):
+        """The one way out of a ``CollectiveTimeout``: every rank calls it together (it is a collective call where the
+        direct all-reduce is in use).  The direct all-reduce is rebuilt over fresh, zeroed flag arrays and only then are the
+        status bits cleared; parameters are the caller's business (restore a checkpoint first: replicas may differ)."""
+        torch.cuda.current_stream(self.device).synchronize()
+        if self._direct is not None:
+            poison = self._direct._desc.poison
+            self._direct.close()
+            self._direct = pdist.DirectAllReduce(self.grads, self.pg, status=self._status)
+            self._direct._desc.poison = poison
+        self._status.clear()
+        if self._B is not None:
+            self.workspace.view(torch.int32)[N.WS_STATUS_WORD] &= ~N.WS_STATUS_COLLECTIVE_TIMEOUT
+        self._graphs = {}
 
     def check_status(self):
         """``poll_status`` plus the device's own words (one D2H sync): the workspace status word and, data parallel with the

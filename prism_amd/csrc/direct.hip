@@ -15,7 +15,8 @@
 // barrier between the calls -- the only legal form for ranks that SHARE a device, where a spinning kernel would starve the
 // peer it waits for) or device flags (use_flags = 1, ranks on distinct devices): a one-workgroup kernel stores the phase
 // number into slot [rank] of every peer's flag array (system-scope release) and polls its own array until every slot has
-// reached it (bounded: gives up after the descriptor's wait_seconds, sets the sticky error slot and poisons the step).
+// reached it (bounded: gives up after the descriptor's wait_seconds, sets the sticky error slot -- its own and every peer's --
+// and poisons the step; a peer finds the mark behind its next wait and poisons its own).
 //
 // Memory types.  The flag arrays are UNCACHED device memory (prism_direct_flags_alloc: hipExtMallocWithFlags,
 // hipDeviceMallocUncached): a peer's store into an ordinary hipMalloc (coarse-grained) allocation is only guaranteed to be
@@ -40,7 +41,8 @@ struct DirectArgs {
     unsigned long long wait_ticks;      // of the 100 MHz real-time counter
 };
 
-// a wait of THIS rank has given up (sticky): every later kernel of the collective leaves the buffers alone
+// a wait of this rank has given up, or a peer that gave up has left its mark (sticky either way): every later kernel of the
+// collective leaves the buffers alone
 __device__ __forceinline__ bool direct_poisoned(const DirectArgs &a) {
     return a.flags[a.rank] != nullptr &&
            __hip_atomic_load(a.flags[a.rank] + PRISM_MAX_PEERS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
@@ -95,38 +97,60 @@ __global__ __launch_bounds__(256) void direct_all_gather_kernel(DirectArgs a) {
     }
 }
 
-// flags[r][s]: the last phase rank s has announced to rank r; slot PRISM_MAX_PEERS of the own array: sticky time-out;
+// flags[r][s]: the last phase rank s has announced to rank r; slot PRISM_MAX_PEERS: sticky time-out (bit 0: a wait of rank r
+// gave up, bit 1: a peer's did and marked r; nonzero is all anyone tests);
 // slot PRISM_MAX_PEERS + 1: the running all-reduce count E of this rank (all ranks advance it in lockstep).  The phase
 // announced is 3 E + a.phase: a captured hipGraph replays with fresh phase numbers.  `what`: bit 0 announce, bit 1 wait
 // (both in one launch on the step's path; apart -- with the host's barrier between them -- where ranks share a device).
-__global__ __launch_bounds__(64) void direct_signal_wait_kernel(DirectArgs a_in, int what) {
-    DirectArgs a = a_in;
+__global__ __launch_bounds__(64) void direct_signal_wait_kernel(DirectArgs a, int what) {
     const int t = threadIdx.x;
-    const unsigned int E = a.flags[a.rank][PRISM_MAX_PEERS + 1];
-    a.phase = 3u * E + a_in.phase;
+    unsigned int *const own = a.flags[a.rank];
+    unsigned int *peer = a.flags[0];                          // flags[t], selected: an indexed copy would live in scratch
+#pragma unroll
+    for (int s = 1; s < PRISM_MAX_PEERS; ++s)
+        if (t == s) peer = a.flags[s];
+    const unsigned int E = own[PRISM_MAX_PEERS + 1];
+    const unsigned int phase = 3u * E + a.phase;
     __builtin_amdgcn_s_barrier();                             // (every lane has read E before lane 0 may advance it)
-    if (a_in.phase == 3u && (what & 2) && t == 0) a.flags[a.rank][PRISM_MAX_PEERS + 1] = E + 1u;
+    if (a.phase == 3u && (what & 2) && t == 0) own[PRISM_MAX_PEERS + 1] = E + 1u;
     if (t < a.world) {
         if (what & 1) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");       // system scope: what this rank wrote is visible to the peers first
-            __hip_atomic_store(a.flags[t] + a.rank, a.phase, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(peer + a.rank, phase, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         if (what & 2) {
             const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            // a rank that has given up once announces its phases (the peers need not time out on it as well) but waits no more
+            // a rank whose sticky slot is set -- by a wait of its own or by a peer's mark -- announces its phases (the peers
+            // need not wait out their bound on it) but waits no more
             const bool dead = direct_poisoned(a);
+            bool gave_up = false;
             // (phase numbers only grow; compared as a signed difference so that the counter may wrap)
-            while (!dead && (int)(__hip_atomic_load(a.flags[a.rank] + t, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) - a.phase) < 0) {
+            while (!dead && (int)(__hip_atomic_load(own + t, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) - phase) < 0) {
                 __builtin_amdgcn_s_sleep(2);
                 if (__builtin_amdgcn_s_memrealtime() - t0 > a.wait_ticks) {
-                    atomicOr(a.flags[a.rank] + PRISM_MAX_PEERS, 1u);
-                    if (a.poison) atomicOr(a.poison, PRISM_WS_STATUS_COLLECTIVE_TIMEOUT);
-                    if (a.host_status)      // (a plain system-scope store of word 1 = bit 1: needs no PCIe atomics)
-                        __hip_atomic_store(a.host_status + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    gave_up = true;
                     break;
                 }
             }
+            // The poison spreads.  Lane t of a rank that gives up marks rank t's sticky slot there and then: 1 in its own
+            // (atomic: a peer's mark may land in it at any time), 2 -- "a peer gave up" -- in every peer's, as a plain
+            // system-scope store into the peer's uncached flag words.  The same lane stores this rank's next announcement
+            // into that array, in a LATER launch and behind a system-scope release fence, so whoever acquires an announcement
+            // made after the give-up finds the mark next to it.
+            const bool any_gave_up = __any(gave_up);
+            if (any_gave_up) {
+                if (t == a.rank) atomicOr(own + PRISM_MAX_PEERS, 1u);
+                else __hip_atomic_store(peer + PRISM_MAX_PEERS, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+            // ... and is looked for behind EVERY wait, before the launch that follows this one starts: a set sticky slot (also
+            // one set earlier: the host cannot switch the update back on while the reduce kernels stay off) poisons the step
+            if (any_gave_up ||
+                __hip_atomic_load(own + PRISM_MAX_PEERS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u) {
+                if (a.poison) atomicOr(a.poison, PRISM_WS_STATUS_COLLECTIVE_TIMEOUT);
+                if (a.host_status)      // (a plain system-scope store of word 1 = bit 1: needs no PCIe atomics)
+                    __hip_atomic_store(a.host_status + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
         }
     }
 }

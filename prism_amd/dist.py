@@ -85,8 +85,10 @@ class DirectAllReduce:
     device they share: the three barriers are then host-side (stream synchronize + group barrier) or the host paces
     announce / wait launches apart (``use_flags="paced"``).
 
-    A flag wait that is not through after ``wait_seconds`` poisons the step (no clip + Adam is applied, direct.hip) and
-    raises ``CollectiveTimeout`` at the next ``allreduce()`` / ``poll()`` -- one step late at most, without a device sync."""
+    A flag wait that is not through after ``wait_seconds`` poisons the step (no clip + Adam is applied, direct.hip) on the
+    rank that gave up and, through a mark in their flag arrays, on its peers, and raises ``CollectiveTimeout`` at the next
+    ``allreduce()`` / ``poll()`` -- one step late at most, without a device sync -- and at every one after it: the flag
+    arrays are spent, a new ``DirectAllReduce`` on all ranks together is the way on."""
 
     def __init__(self, flat_grads, group=None, use_flags=None, poison_ptr=None, status=None, wait_seconds=None):
         import ctypes

@@ -298,7 +298,9 @@ def test_direct_allreduce_flag_kernels_single_rank_and_graph_replay():
 def test_direct_allreduce_timeout_poisons_the_step_and_the_host_sees_it():
     """A peer that never arrives: the bounded wait (0.2 s here) gives up, sets the sticky slot, ORs
     PRISM_WS_STATUS_COLLECTIVE_TIMEOUT into the learner's status word and the pinned host word; the reduce / gather kernels
-    and clip + Adam behind it then leave gradients and parameters alone, and ``poll_status`` / ``save`` / ``log`` raise."""
+    and clip + Adam behind it then leave gradients and parameters alone, and ``poll_status`` / ``save`` / ``log`` raise --
+    and go on raising, with nothing applied, for a caller that catches the exception, until ``reset_collective()``.  (What
+    the give-up does to the PEERS: tests/test_gpu_direct_worlds.py.)"""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     import ctypes
@@ -326,6 +328,8 @@ def test_direct_allreduce_timeout_poisons_the_step_and_the_host_sees_it():
     N.check(N.lib().prism_direct_flags_read(fp.value, out, N.current_stream_handle()), "read")
     assert out[N.MAX_PEERS] == 1
     assert list((ctypes.c_uint32 * N.DIRECT_FLAG_WORDS).from_buffer_copy(bytes(out)))[1] == 0      # the peer never announced
+    N.check(N.lib().prism_direct_flags_read(fq.value, out, N.current_stream_handle()), "read")
+    assert out[N.MAX_PEERS] == 2                          # the mark the rank that gave up left in its peer's sticky slot
     for p in (fp, fq):
         N.check(N.lib().prism_direct_flags_free(p.value), "free")
 
@@ -348,9 +352,25 @@ def test_direct_allreduce_timeout_poisons_the_step_and_the_host_sees_it():
     ag._allreduce = lambda: 0.5
     with pytest.raises(pdist.CollectiveTimeout):
         ln.step(eager=True)                               # the poll at the top of the step
-    ag.workspace.view(torch.int32)[N.WS_STATUS_WORD] = N.WS_STATUS_COLLECTIVE_TIMEOUT
-    ag._launch_fused(ln.experience_buffer, ag._bind_fused(ln.experience_buffer))
+    # terminal: a caller that catches the exception and carries on gets it again, from every step entry point and poll, and
+    # the bit that keeps clip + Adam off is still in the workspace (the sticky flag slot keeps the reduce kernels off: an
+    # update now would run on un-reduced gradients)
+    for again in (lambda: ln.step(eager=True), lambda: ln.step(), lambda: ag.step_fused(ln.experience_buffer),
+                  ag.poll_status, ag.check_status):
+        with pytest.raises(pdist.CollectiveTimeout):
+            again()
+    torch.cuda.synchronize()
+    assert int(ag.workspace.view(torch.int32)[N.WS_STATUS_WORD].item()) & N.WS_STATUS_COLLECTIVE_TIMEOUT
+    assert torch.equal(ag.flat, before) and int(ag.optimizer.step_t.item()) == step0
+    ag._launch_fused(ln.experience_buffer, ag._bind_fused(ln.experience_buffer))      # (past the host's poll: the device's own check)
     torch.cuda.synchronize()
     assert torch.equal(ag.flat, before) and int(ag.optimizer.step_t.item()) == step0
     with pytest.raises(pdist.CollectiveTimeout):
         ag.save("/tmp/prism_never_written")
+    # the one way out: the collective reset on all ranks together (here there is none to rebuild); steps apply updates again
+    ag.reset_collective()
+    ag.poll_status()
+    ln.step(eager=True)
+    torch.cuda.synchronize()
+    ag.check_status()
+    assert not torch.equal(ag.flat, before) and int(ag.optimizer.step_t.item()) == step0 + 1
