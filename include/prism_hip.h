@@ -439,6 +439,43 @@ size_t prism_learner_workspace_bytes(const prism_model_dims *dims, int32_t batch
  * there would need the merged loss launch and the heads' embedding-gradient sum: not built). */
 int prism_learner_supported(const prism_model_dims *dims, int32_t batch);
 
+/* host: which launch forms an update of (dims, batch) takes in `gemm_mode` (PRISM_GEMM_*; 0 = the library default), as the
+ * learner entry points decide them before they launch.  Read-only, no device call.  Fills out[0 .. PRISM_PLAN_N):
+ *   PRISM_PLAN_BWD          the IQN trunk's backward: PRISM_BWD_NONE (no IQN) | PRISM_BWD_FP32 (iqn_bwd_kernel) |
+ *                           PRISM_BWD_BW3 (iqn_bwd3_kernel: bf16x3, width 128) | PRISM_BWD_BW4 (iqn_bwd4_kernel: bf16x3,
+ *                           width 256) | PRISM_BWD_LIN (the linear head's lin_bwd_kernel)
+ *   PRISM_PLAN_Q_BWD        the two-layer Q heads' input-side backward: PRISM_QB_NONE | PRISM_QB_ROWS | PRISM_QB_COLS
+ *                           (qh_bwd_kernel by rows / by columns) | PRISM_QB_QB2 (qh_bwd2_kernel)
+ *   PRISM_PLAN_CONV_IN_BWD  1: the conv backward's taps are folded into the IQN backward launch; 0: the post launch's
+ *   PRISM_PLAN_N_CHUNKS     row chunks of the IQN backward = gradient slabs the post launch sums
+ *   PRISM_PLAN_LOCAL_LOSS   1: the IQN loss finishes inside the forward tiles (no loss launch)
+ *   PRISM_PLAN_MERGED_LOSS  1: IQN and ensemble loss in one launch
+ *   PRISM_PLAN_SPLIT        1: forward GEMMs on the bf16 matrix pipe (three-piece operands)
+ *   PRISM_PLAN_Q_DE_SLOTS   embedding-gradient slots of the Q heads the post launch sums
+ *   PRISM_PLAN_POST_BLOCKS  workgroups of the post launch (without the priority writeback's)
+ * PRISM_ERR_INVALID: dims or out NULL, n_out < PRISM_PLAN_N.  PRISM_ERR_UNSUPPORTED: outside prism_learner_supported's
+ * envelope.  Neither sets prism_last_error(), as prism_learner_supported sets none. */
+#define PRISM_PLAN_BWD 0
+#define PRISM_PLAN_Q_BWD 1
+#define PRISM_PLAN_CONV_IN_BWD 2
+#define PRISM_PLAN_N_CHUNKS 3
+#define PRISM_PLAN_LOCAL_LOSS 4
+#define PRISM_PLAN_MERGED_LOSS 5
+#define PRISM_PLAN_SPLIT 6
+#define PRISM_PLAN_Q_DE_SLOTS 7
+#define PRISM_PLAN_POST_BLOCKS 8
+#define PRISM_PLAN_N 9
+#define PRISM_BWD_NONE 0
+#define PRISM_BWD_FP32 1
+#define PRISM_BWD_BW3 2
+#define PRISM_BWD_BW4 3
+#define PRISM_BWD_LIN 4
+#define PRISM_QB_NONE 0
+#define PRISM_QB_ROWS 1
+#define PRISM_QB_COLS 2
+#define PRISM_QB_QB2 3
+int prism_learner_plan_info(const prism_model_dims *dims, int32_t batch, int32_t gemm_mode, int32_t *out, int32_t n_out);
+
 /* get_losses + backward: fills out_*, grads (complete dL/dparams of
  * mean(dl*w) + mean(ql*w), agent.py:58-64,71-72) — the RCCL all-reduce of `grads` sits between
  * this call and prism_learner_clip_adam in data-parallel runs. */

@@ -23,6 +23,10 @@ INGEST_MAX_STREAMS = 65536
 WS_STATUS_WORD, WS_STATUS_BARRIER_TIMEOUT, WS_STATUS_COLLECTIVE_TIMEOUT = 7, 1, 2
 GEMM_MODES = {"auto": 0, "fp32": 1, "bf16x3": 2}
 ACT_WEIGHTS_CURRENT = 1
+# prism_learner_plan_info: the fields of `out` in order, and the names of the two form codes
+PLAN_FIELDS = ("bwd", "q_bwd", "conv_in_bwd", "n_chunks", "local_loss", "merged_loss", "split", "q_de_slots", "post_blocks")
+BWD_FORMS = ("none", "fp32", "bw3", "bw4", "lin")
+QBWD_FORMS = ("none", "rows", "cols", "qb2")
 
 c_i32, c_i64, c_u64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_void_p
 
@@ -145,6 +149,7 @@ SIGNATURES = {
     "prism_per_query": (ctypes.c_int, [_P(ReplayDesc), c_i64, c_vp, c_vp]),
     "prism_learner_workspace_bytes": (ctypes.c_size_t, [_P(ModelDims), c_i32]),
     "prism_learner_supported": (ctypes.c_int, [_P(ModelDims), c_i32]),
+    "prism_learner_plan_info": (ctypes.c_int, [_P(ModelDims), c_i32, c_i32, _P(c_i32), c_i32]),
     "prism_learner_fwd_bwd": (ctypes.c_int, [_P(LearnerDesc), c_vp]),
     "prism_learner_clip_adam": (ctypes.c_int, [_P(LearnerDesc), c_vp]),
     "prism_learner_clip_step": (ctypes.c_int, [_P(LearnerDesc), _P(OptHyper), c_vp]),
@@ -222,6 +227,20 @@ def check(rc, what=""):
     if rc != PRISM_OK:
         msg = lib().prism_last_error()
         raise PrismError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
+
+
+def plan_info(dims, batch, gemm_mode=0):
+    """prism_learner_plan_info as a dict over PLAN_FIELDS, `bwd` / `q_bwd` by name (BWD_FORMS / QBWD_FORMS); None outside
+    the envelope.  `gemm_mode`: a key of GEMM_MODES or its number."""
+    out = (c_i32 * len(PLAN_FIELDS))()
+    rc = lib().prism_learner_plan_info(ctypes.byref(dims), batch, GEMM_MODES.get(gemm_mode, gemm_mode), out, len(PLAN_FIELDS))
+    if rc == PRISM_ERR_UNSUPPORTED:
+        return None
+    if rc != PRISM_OK:
+        raise PrismError(f"prism_learner_plan_info failed (code {rc})")
+    info = dict(zip(PLAN_FIELDS, out))
+    info["bwd"], info["q_bwd"] = BWD_FORMS[info["bwd"]], QBWD_FORMS[info["q_bwd"]]
+    return info
 
 
 def ptr(t):

@@ -213,6 +213,13 @@ __global__ __launch_bounds__(512) void iqn_bwd3_kernel(IqnArgs a) {
                 if (T == 8) tsum += s_tap[(wq * 4 + so + 2) * TS + i];
                 s_row[wq * BWD_CONV_ROW + lane] = tsum;
             }
+            // a row is 9 C taps + the bias: 73 outputs at C = 8 (T >= 16, two channels a lane), nine more than a wave has lanes
+            // (they lie in the last lane subset, which starts at 9 (C - cpl) = 54: no second division)
+            const int o2 = lane + 64;
+            if (o2 <= 9 * C) {
+                const int so = o2 < 9 * C ? share - 1 : 0, i = o2 < 9 * C ? o2 - so * n_mine : BWD_CONV_TAPS;
+                s_row[wq * BWD_CONV_ROW + o2] = s_tap[(wq * 4 + so) * TS + i];
+            }
             // last of the four helper waves to get here folds (LDS operations of a wave retire in order: a wave's row is
             // in place before its count is)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -221,8 +228,9 @@ __global__ __launch_bounds__(512) void iqn_bwd3_kernel(IqnArgs a) {
             arrived = __builtin_amdgcn_readfirstlane(arrived);
             if (arrived == 3 && lane <= 9 * C) {
                 const float *r = s_row + lane;
-                a.ws.convpart[(int64_t)(rc * (E_DIM / 16) + (cs & ~3)) * BWD_CONV_ROW + lane] =
-                    ((r[0] + r[BWD_CONV_ROW]) + r[2 * BWD_CONV_ROW]) + r[3 * BWD_CONV_ROW];
+                float *out = a.ws.convpart + (int64_t)(rc * (E_DIM / 16) + (cs & ~3)) * BWD_CONV_ROW + lane;
+                out[0] = ((r[0] + r[BWD_CONV_ROW]) + r[2 * BWD_CONV_ROW]) + r[3 * BWD_CONV_ROW];
+                if (o2 <= 9 * C) out[64] = ((r[64] + r[64 + BWD_CONV_ROW]) + r[64 + 2 * BWD_CONV_ROW]) + r[64 + 3 * BWD_CONV_ROW];
             }
         }
         PRISM_STAMP(26);

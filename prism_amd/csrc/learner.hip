@@ -83,6 +83,27 @@ extern "C" size_t prism_learner_workspace_bytes(const prism_model_dims *dims, in
     return make_plan(*dims, batch).ws_bytes;
 }
 
+// What make_plan() decides for (dims, batch, gemm_mode), read-only and without a device call: out[0 .. PRISM_PLAN_N) in
+// the order of the PRISM_PLAN_* indices (include/prism_hip.h).  A test asks it which launch forms its case really takes.
+extern "C" int prism_learner_plan_info(const prism_model_dims *dims, int32_t batch, int32_t gemm_mode, int32_t *out, int32_t n_out) {
+    static_assert(BWD_NONE == PRISM_BWD_NONE && BWD_FP32 == PRISM_BWD_FP32 && BWD_BW3 == PRISM_BWD_BW3 && BWD_BW4 == PRISM_BWD_BW4 &&
+                      BWD_LIN == PRISM_BWD_LIN && QB_NONE == PRISM_QB_NONE && QB_ROWS == PRISM_QB_ROWS && QB_COLS == PRISM_QB_COLS &&
+                      QB_QB2 == PRISM_QB_QB2, "plan.h's forms are the header's");
+    if (!dims || !out || n_out < PRISM_PLAN_N) return PRISM_ERR_INVALID;
+    if (iqn_supported(dims, batch) != PRISM_OK) return PRISM_ERR_UNSUPPORTED;
+    const LearnerPlan p = make_plan(*dims, batch, gemm_mode);
+    out[PRISM_PLAN_BWD] = p.bwd;
+    out[PRISM_PLAN_Q_BWD] = p.q_bwd;
+    out[PRISM_PLAN_CONV_IN_BWD] = p.conv_in_bwd;
+    out[PRISM_PLAN_N_CHUNKS] = p.n_chunks;
+    out[PRISM_PLAN_LOCAL_LOSS] = p.local_loss;
+    out[PRISM_PLAN_MERGED_LOSS] = p.merged_loss;
+    out[PRISM_PLAN_SPLIT] = p.split;
+    out[PRISM_PLAN_Q_DE_SLOTS] = p.q_de_slots;
+    out[PRISM_PLAN_POST_BLOCKS] = p.post_blocks;
+    return PRISM_OK;
+}
+
 // The ONE envelope check, plan and carve of a call: every entry point starts here and hands `pl` on.
 // `need_batch`: the minibatch arrays and outputs of an update must be bound (not for the acting forward, which may well
 // run before the first update)

@@ -66,6 +66,24 @@ def test_argument_checks_without_device(lib):
     assert lib.prism_learner_supported(ctypes.byref(dims), 256) == 0
     assert lib.prism_learner_workspace_bytes(ctypes.byref(dims), 256) > 8 * 2 ** 20
     assert lib.prism_learner_supported(ctypes.byref(dims), 255) == -3                # B*T not a multiple of 16
+    # prism_learner_plan_info: null pointers and a short `out` are refused before anything is written; outside the envelope -3
+    n = len(N.PLAN_FIELDS)
+    assert n == 9 and "prism_learner_plan_info" in N.SIGNATURES
+    out = (ctypes.c_int32 * (n + 1))(*([-77] * (n + 1)))
+    assert lib.prism_learner_plan_info(None, 256, 0, out, n) == -1
+    assert lib.prism_learner_plan_info(ctypes.byref(dims), 256, 0, None, n) == -1
+    assert lib.prism_learner_plan_info(ctypes.byref(dims), 256, 0, out, n - 1) == -1
+    assert lib.prism_learner_plan_info(ctypes.byref(dims), 256, 0, out, 0) == -1
+    assert lib.prism_learner_plan_info(ctypes.byref(dims), 255, 0, out, n) == -3
+    assert lib.prism_learner_plan_info(ctypes.byref(N.ModelDims()), 256, 0, out, n) == -3
+    assert list(out) == [-77] * (n + 1)
+    dims.propagate_grad = 1
+    assert lib.prism_learner_plan_info(ctypes.byref(dims), 256, 2, out, n + 1) == 0      # (a longer `out` is fine: n entries are written)
+    # B * T = 2048 at width 128 in bf16x3: iqn_bwd3_kernel with the conv backward inside, 16 slabs, local loss, no heads
+    assert list(out) == [2, 0, 1, 16, 1, 0, 1, 0, out[8], -77] and out[8] > 0
+    assert lib.prism_learner_plan_info(ctypes.byref(dims), 256, 1, out, n) == 0
+    assert list(out)[:8] == [1, 0, out[2], 8, 1, 0, 0, 0] and N.plan_info(dims, 256, "fp32")["bwd"] == "fp32"
+    assert N.plan_info(dims, 255) is None
 
 
 def _fake_learner_desc(lib, cfg_index=2, batch=32):

@@ -6,7 +6,9 @@ The action count is not a passive dimension: the forward tiles stage W2[A][H] wi
 selector kernel masks lanes with `lane < A`, and the unpadded flat parameter buffer makes A decide n_params % 4 (the
 scalar tails of the optimizer kernels and of the all-reduce slices) and the alignment of every Q-head tensor.
 
-  a. the unfused update against LearnerOracle, both GEMM modes, tolerances of tests/test_gpu_variants.py;
+  a. the unfused update against LearnerOracle, both GEMM modes, tolerances of tests/test_gpu_variants.py; rows 11-16 of the
+     case table run every backward form the plan can pick (iqn_bwd3_kernel with and without the conv backward inside,
+     qh_bwd2_kernel, qh_bwd_kernel by rows, iqn_bwd4_kernel with 1 and 2 row chunks) in the mode that selects it;
   b. acting (prism_act_forward, prism_ids_select, prism_greedy_select, the hipGraph form) over the same grid, with exact ties;
   c. the fused step forms bit-equal to the unfused one at n_params % 4 in {1, 3};
   d. the direct all-reduce at lengths 8k + 1 and 8k + 3.
@@ -291,10 +293,15 @@ def test_fused_forms_equal_unfused_at_odd_parameter_counts(dev, name):
     """The pattern of tests/test_gpu_step.py::test_fused_and_graph_equal_unfused at parameter counts that leave a scalar
     tail of 1 and of 3 floats behind the float4 part of every flat-buffer kernel, and Q-head tensors at an odd float offset:
     unfused, fused eager, hipGraph and the five-launch form stay bit-identical for 6 steps.  With (a) holding the unfused
-    form to the oracle, bit-equality carries parity to the others."""
+    form to the oracle, bit-equality carries parity to the others.  Cases with a `B` of 64 or 128 run the post launch's sum
+    over iqn_bwd3_kernel's 16 gradient slabs (8 at B = 32) and over qh_bwd2_kernel's two embedding-gradient slots."""
     case = E.FUSED_CASES[name]
-    ref, fus, gra = _mk(dev, case, False, False), _mk(dev, case, True, False), _mk(dev, case, True, True)
-    spl = _mk(dev, case, True, True, fuse_tail=False)
+    B = case.get("B", 32)
+    ref, fus, gra = _mk(dev, case, False, False, B=B), _mk(dev, case, True, False, B=B), _mk(dev, case, True, True, B=B)
+    spl = _mk(dev, case, True, True, fuse_tail=False, B=B)
+    from prism_amd import _native as N
+    plan = N.plan_info(ref.agent.dims, B, str(getattr(ref.agent.config, "gemm_mode", "auto")))
+    assert {k: plan[k] for k in case["expect"]} == case["expect"]          # (the launch forms the case is here for)
     n_params, table = E.layout(ref.agent.model.state_dict())
     assert n_params == ref.agent.flat.numel() and n_params % 4 == case["rem"] and case["rem"] in (1, 3)
     head = E.first_head_offset(table)
@@ -312,7 +319,7 @@ def test_fused_forms_equal_unfused_at_odd_parameter_counts(dev, name):
         for i, other in enumerate(outs[1:]):
             for j, (x, y) in enumerate(zip(outs[0], other)):
                 np.testing.assert_array_equal(x, y, err_msg=f"step {step}, form {i + 1}, item {j}")
-        assert np.isfinite(outs[0][3]).all() and int(outs[0][0].shape[0]) == 32
+        assert np.isfinite(outs[0][3]).all() and int(outs[0][0].shape[0]) == B
     for ln in (ref, fus, gra, spl):
         assert int(ln.agent.optimizer.step_t.item()) == 6
         ln.agent.check_status()
