@@ -242,6 +242,38 @@ typedef struct prism_eval_desc {
 int prism_eval_track(const prism_eval_desc *ev, int32_t n, const float *reward, const uint8_t *done,
                      const uint8_t *truncated, prism_stream_t stream);
 
+/* The quota rule: the project's own stopping rule for n_streams > 1, not the reference's.  Under the budget rule above
+ * every stream gets budget / n_streams steps and the n_streams episodes open at the cut are dropped; an episode open at a
+ * fixed cut is length-biased long, so the mean is biased low where long episodes are the good ones.  Here every stream
+ * contributes exactly its first `quota` finished episodes, whatever their lengths: the counted set is fixed in advance.
+ * prism_eval_desc is used as it is (budget is not read); this struct carries what is new. */
+typedef struct prism_eval_quota {
+    int32_t quota;          /* E >= 1: finished episodes taken from every stream */
+    int64_t max_calls;      /* >= 1: the evaluation also closes after this many taken calls (safety cap) */
+    int32_t *ep_done;       /* device [n_streams]: finished episodes of stream i so far */
+    int64_t *qcounts;       /* device [2]: streams that have met the quota | unused (0) */
+    int64_t *host_closed;   /* optional, pinned host [1]: 1 once closed as this call leaves it, else 0 */
+} prism_eval_quota;
+
+/* One environment step of an evaluation under the quota rule: row i is stream i and n must equal n_streams (the rule
+ * speaks about every stream); reward [n] fp32, done / truncated [n].  The call first reads
+ * closed = qcounts[0] >= n_streams || counts[3] >= max_calls.  A closed evaluation takes nothing: every array stays bit
+ * for bit as it was and only host_counts and host_closed are rewritten, so a host that runs ahead of the device cannot
+ * spoil the result.  Otherwise, per row i, with live = ep_done[i] < quota read before the row: a row that is not live is
+ * not touched and its reward and flags are never read (they may be NaN or set); a live row does prism_eval_track's
+ * arithmetic, in float64 on the widened reward: len = ep_length[i] + 1; ret = reward[i] + ep_return[i] (an episode's
+ * first reward counts); done | truncated: an episode end (ret, len), both accumulators of i return to 0 and
+ * ep_done[i] += 1; else they are stored back.  Ends are folded in row order by the recurrences of prism_eval_track: log
+ * slot counts[0] while counts[0] < log_capacity; stats[0] += ret; stats[1] += ret * ret (the product and the sum each
+ * rounded); stats[2] / stats[3] = min / max by plain < / > compares, the first episode setting both; counts[0] += 1;
+ * counts[1] += len.  Each stream whose ep_done reaches quota in this call adds 1 to qcounts[0].  After the rows
+ * counts[2] += the number of live rows of this call and counts[3] += 1.  The whole call is taken or none of it: the rule
+ * is not read again between rows.  host_counts, when given, receives counts[0] and counts[2] and host_closed, when
+ * given, the closing predicate, both as the call leaves them (plain stores, visible to the host once the launch has
+ * ended).  Nothing the launch takes by value changes from step to step: a captured launch replays as it is. */
+int prism_eval_track_quota(const prism_eval_desc *ev, const prism_eval_quota *q, int32_t n, const float *reward,
+                           const uint8_t *done, const uint8_t *truncated, prism_stream_t stream);
+
 /* PrioritizedSampler.sample (called at timestep_buffer.py:37): p_sum/p_min = query(0,size);
  * index[i] = min(scan_lower_bound(mass[i]), size-1); weight[i] = (leaf/p_min) ** -beta.
  * mass == NULL: masses are drawn on the device, U(0,p_sum) in float64 narrowed to fp32, from

@@ -56,6 +56,10 @@ class EvalDesc(ctypes.Structure):
                 ("log_return", c_vp), ("log_length", c_vp), ("stats", c_vp), ("counts", c_vp), ("host_counts", c_vp)]
 
 
+class EvalQuota(ctypes.Structure):
+    _fields_ = [("quota", c_i32), ("max_calls", c_i64), ("ep_done", c_vp), ("qcounts", c_vp), ("host_closed", c_vp)]
+
+
 ENV_STATE_WORDS, ENV_MAX, ENV_STATUS_BAD_ACTION = 8, 65536, 1
 ENV_SEAQUEST_STATE_WORDS, ENV_STATUS_OVERFLOW = 112, 2          # Seaquest's record is wider: five bounded entity lists
 
@@ -137,6 +141,7 @@ SIGNATURES = {
     "prism_replay_ingest_cursor": (ctypes.c_int, [_P(ReplayDesc), c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
                                                    c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, _P(EpisodeDesc), c_vp]),
     "prism_eval_track": (ctypes.c_int, [_P(EvalDesc), c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "prism_eval_track_quota": (ctypes.c_int, [_P(EvalDesc), _P(EvalQuota), c_i32, c_vp, c_vp, c_vp, c_vp]),
     "prism_per_sample": (ctypes.c_int, [_P(ReplayDesc), c_i64, c_i32, c_vp, c_u64, c_u64, c_f32, c_vp, c_vp,
                                          c_vp]),
     "prism_uniform_sample": (ctypes.c_int, [c_i64, c_i32, c_u64, c_u64, c_vp, c_vp]),

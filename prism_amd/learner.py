@@ -73,8 +73,14 @@ class Learner:
         self.evaluator = None
         if eval_envs is not None:
             from prism_amd.evals import VectorEvaluator
+            # MI355X-only knobs, plain attributes like captured_loop: evaluation_episodes_per_env = E >= 1 evaluates by
+            # episode quota per environment (the rule for any N > 1; 0, the default, is the reference's budget rule) and
+            # evaluation_max_steps_per_env caps it (None: E x the environments' episode_timestep_limit where positive, else
+            # evaluation_timestep_horizon, per stream)
             self.evaluator = VectorEvaluator(self.agent, eval_envs, config.timesteps_between_evaluations,
-                                             config.evaluation_timestep_horizon)
+                                             config.evaluation_timestep_horizon,
+                                             episodes_per_env=int(getattr(config, "evaluation_episodes_per_env", 0) or 0),
+                                             max_steps_per_env=getattr(config, "evaluation_max_steps_per_env", None))
 
     # ------------------------------------------------------------------ the hot path
     def step(self, timesteps_this_iteration=0, eager=False):
@@ -182,6 +188,8 @@ class Learner:
                 last = self.evaluator.last
                 self.logger.log_data(last["mean"], "Report/Rewards", "Eval Reward")
                 self.logger.log_data(last["episodes"], "Report/Rewards", "Eval Episodes")
+                if last.get("incomplete_streams"):          # (quota rule only: the cap closed it)
+                    self.logger.log_data(last["incomplete_streams"], "Report/Rewards", "Eval Incomplete Streams")
             if self.timesteps_since_report >= self.timesteps_per_report:
                 self.report()
             it = time.perf_counter() - loop_start
@@ -283,6 +291,8 @@ class Learner:
         agent, buf = self.agent, self.experience_buffer
         parts = {"replay": buf._state_part(), "agent_resume": agent._state_part(), "learner": self._state_part()}
         manifest = {"compat": {"replay": buf._compat_record(), "agent": agent._compat_record()}}
+        if self.evaluator is not None and self.evaluator.episodes_per_env:          # (the record exists only under the quota rule)
+            manifest["compat"]["evaluator"] = self.evaluator._compat_record()
         return snapshot.write_snapshot(self._snapshot_dir(path), parts, manifest, extra=agent.save)
 
     def load_state(self, path):
@@ -297,8 +307,15 @@ class Learner:
         manifest = snapshot.read_manifest(d)
         agent._check_snapshot(manifest)          # every refusal comes before anything is touched
         buf._check_snapshot(manifest)
+        stored = (manifest.get("compat") or {}).get("evaluator")
+        if self.evaluator is not None and stored is not None:
+            snapshot.check_compat(stored, self.evaluator._compat_record(), "Learner.load_state (evaluator)")
         parts, _ = snapshot.read_snapshot(d, ["replay", "agent_resume", "learner"])
         st = parts["learner"]
+        if self.evaluator is not None and stored is None and st.get("evaluator") is not None:
+            # an evaluator's state written under the budget rule: refused by an evaluator under the quota rule
+            snapshot.check_compat(dict(episodes_per_env=0, max_steps_per_env=0), self.evaluator._compat_record(),
+                                  "Learner.load_state (evaluator)")
         buf._restore_part(parts["replay"])
         agent._restore_part(d, parts["agent_resume"])
         for name in ("cumulative_timesteps", "cumulative_model_updates", "timesteps_since_report",

@@ -6,7 +6,10 @@ back with .cpu() on every step, the sums kept in Python (sync_agent_evaluator.py
 a product path.  Then the cost of prism_eval_track alone at n = 16 and n = 1024: device events around --calls
 back-to-back launches on one stream (launch and the Python call included: what a step of the loop pays).
 --track-only [--track-sizes 16]   only that last part: the run to put under `rocprofv3 --kernel-trace --stats` for the
-                                  kernel's own duration, one size per run (the kernel has one name)."""
+                                  kernel's own duration, one size per run (the kernel has one name).
+--episodes-per-env E              the quota rule (prism_eval_track_quota) in place of the budget rule: whole evaluations
+                                  of E episodes per environment, capped at --steps steps (no host twin: the reference has
+                                  no such rule), and the cost of the quota kernel with every row live."""
 import argparse, contextlib, io, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -98,8 +101,29 @@ def rates(n, steps, reps):
                 device_all=[round(x, 1) for x in out["device"]], host_all=[round(x, 1) for x in out["host"]])
 
 
-def track_cost(n, calls):
-    tr = EvalTracker(n, 10 ** 15, 4096, DEV)
+def quota_rates(n, steps, reps, episodes_per_env):
+    cfg = baseline_config(3, device=DEV, log_to_wandb=False)
+    torch.manual_seed(0)
+    with contextlib.redirect_stdout(io.StringIO()):
+        agent = agent_factory.build_agent(cfg, StubEnvs.obs_shape, StubEnvs.n_actions)
+    ev = VectorEvaluator(agent, StubEnvs(n, steps), 0, steps * n, episodes_per_env=episodes_per_env, max_steps_per_env=steps)
+    out = []
+    for k in range(reps + 1):          # one warm-up evaluation (graph capture)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ev.evaluate_agent()
+        dt = time.perf_counter() - t0
+        if k:
+            out.append(ev.last["timesteps"] / dt)
+    last = ev.last
+    return dict(n=n, steps=steps, episodes_per_env=episodes_per_env, episodes=last["episodes"], calls=last["calls"],
+                incomplete_streams=last["incomplete_streams"], device_steps_per_s=round(float(np.median(out)), 1),
+                device_all=[round(x, 1) for x in out])
+
+
+def track_cost(n, calls, quota=0):
+    """quota > 0: the quota kernel, with a quota no stream reaches (every row stays live: the full cost)."""
+    tr = EvalTracker(n, 10 ** 15, 4096, DEV, episodes_per_stream=quota, max_calls=10 ** 15 if quota else 0)
     g = torch.Generator(device=DEV).manual_seed(n)
     reward = torch.rand(n, device=DEV, generator=g)
     done = torch.rand(n, device=DEV, generator=g) < 1 / 200
@@ -116,7 +140,7 @@ def track_cost(n, calls):
         b.record()
         b.synchronize()
         out.append(a.elapsed_time(b) * 1e3 / calls)
-    return dict(n=n, calls=calls, us_per_call=round(float(np.median(out)), 2), all=[round(x, 2) for x in out])
+    return dict(n=n, calls=calls, kernel="prism_eval_track_quota" if quota else "prism_eval_track", us_per_call=round(float(np.median(out)), 2), all=[round(x, 2) for x in out])
 
 
 if __name__ == "__main__":
@@ -127,16 +151,23 @@ if __name__ == "__main__":
     ap.add_argument("--calls", type=int, default=5000)
     ap.add_argument("--track-only", action="store_true")
     ap.add_argument("--track-sizes", default="16,1024")
+    ap.add_argument("--episodes-per-env", type=int, default=0)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_eval needs the GPU"
     res = {"rates": [], "track": []}
-    for n in (() if args.track_only else (int(x) for x in args.sizes.split(","))):
+    E = args.episodes_per_env
+    for n in (() if args.track_only or not E else (int(x) for x in args.sizes.split(","))):
+        r = quota_rates(n, args.steps, args.reps, E)
+        res["rates"].append(r)
+        print(f"N = {n:4d}: quota rule, {E} episodes per environment {r['device_steps_per_s']:10.1f} steps/s   "
+              f"({r['episodes']} episodes in {r['calls']} calls, {r['incomplete_streams']} incomplete streams)", flush=True)
+    for n in (() if args.track_only or E else (int(x) for x in args.sizes.split(","))):
         r = rates(n, args.steps, args.reps)
         res["rates"].append(r)
         print(f"N = {n:4d}: device bookkeeping {r['device_steps_per_s']:10.1f} steps/s   host bookkeeping "
               f"{r['host_steps_per_s']:10.1f} steps/s   ratio {r['ratio']:.3f}   ({r['episodes']} episodes)", flush=True)
     for n in (int(x) for x in args.track_sizes.split(",")):
-        r = track_cost(n, args.calls)
+        r = track_cost(n, args.calls, 2 ** 30 if E else 0)
         res["track"].append(r)
-        print(f"prism_eval_track n = {n:4d}: {r['us_per_call']:.2f} us per call, back to back on one stream", flush=True)
+        print(f"{r['kernel']} n = {n:4d}: {r['us_per_call']:.2f} us per call, back to back on one stream", flush=True)
     print(json.dumps(res))
