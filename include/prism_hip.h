@@ -54,6 +54,7 @@ extern "C" {
 #define PRISM_STATUS_INGEST_DUP_STREAM 4   /* prism_replay_ingest: a stream id repeated in one call or outside the table */
 #define PRISM_STATUS_OBS_INEXACT 8         /* byte ring: a float that is not byte-exact was narrowed (stored as 0) */
 #define PRISM_STATUS_INGEST_BAD_CURSOR 16  /* prism_replay_ingest_cursor: the device cursor word was negative; nothing was written */
+#define PRISM_STATUS_FRONT_BAD_SIZE 32     /* prism_step_front_cursor: the device cursor word was <= 0; the launch sampled as from one row */
 
 /* prism_replay_ingest obs_kind */
 #define PRISM_OBS_F32 0
@@ -542,6 +543,17 @@ int prism_step_front(const prism_learner_desc *ld, const prism_replay_desc *rp, 
 int prism_step_front_ring(const prism_learner_desc *ld, const prism_replay_desc *rp, int32_t ring_kind, int64_t size,
                           const float *mass, uint64_t seed, uint64_t offset, float beta,
                           int64_t *out_index, float *out_weight, prism_stream_t stream);
+
+/* prism_step_front_ring with the number of stored rows read on the device, for a launch a hipGraph replays while the
+ * ring fills: size = min(cursor[slot], rp->capacity), `cursor` the pair of words prism_replay_ingest_cursor keeps (the
+ * write serial, which is the ring's size until the ring wraps).  `slot` is by value: it names the word the last ingest
+ * launch in front of this one wrote.  The launch only reads the pair.  The kernel clamps the size into [1, capacity]; a
+ * word <= 0 raises the sticky bit PRISM_STATUS_FRONT_BAD_SIZE in rp->status and the launch samples as from one row.
+ * Everything else, results included, is prism_step_front_ring's at that size. */
+int prism_step_front_cursor(const prism_learner_desc *ld, const prism_replay_desc *rp, int32_t ring_kind,
+                            const int64_t *cursor, int32_t slot,
+                            const float *mass, uint64_t seed, uint64_t offset, float beta,
+                            int64_t *out_index, float *out_weight, prism_stream_t stream);
 
 /* prism_learner_clip_adam + prism_per_update(index, |ld->out_td|) in one launch. */
 int prism_step_back(const prism_learner_desc *ld, const prism_replay_desc *rp, const int64_t *index,

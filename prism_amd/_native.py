@@ -16,6 +16,7 @@ PRISM_MAX_NSTEP = 15
 FLAG_DONE, FLAG_TRUNC, FLAG_HAS_NEXT = 1, 2, 4
 STATUS_NONPOSITIVE_PSUM, STATUS_NONPOSITIVE_PMIN, STATUS_INGEST_DUP_STREAM, STATUS_OBS_INEXACT = 1, 2, 4, 8
 STATUS_INGEST_BAD_CURSOR = 16
+STATUS_FRONT_BAD_SIZE = 32
 OBS_F32, OBS_U8 = 0, 1
 RING_F32, RING_U8 = 0, 1          # storage kind of the ring's observation arrays (the prism_*_ring entry points)
 CLIP_NONE, CLIP_CLAMP = 0, 1
@@ -163,6 +164,8 @@ SIGNATURES = {
                                          c_vp]),
     "prism_step_front_ring": (ctypes.c_int, [_P(LearnerDesc), _P(ReplayDesc), c_i32, c_i64, c_vp, c_u64, c_u64, c_f32, c_vp,
                                               c_vp, c_vp]),
+    "prism_step_front_cursor": (ctypes.c_int, [_P(LearnerDesc), _P(ReplayDesc), c_i32, c_vp, c_i32, c_vp, c_u64, c_u64, c_f32,
+                                                c_vp, c_vp, c_vp]),
     "prism_step_back": (ctypes.c_int, [_P(LearnerDesc), _P(ReplayDesc), c_vp, c_f32, c_f32, c_vp]),
     "prism_act_forward": (ctypes.c_int, [_P(LearnerDesc), c_vp, c_i32, c_i32, c_vp, c_u64, c_u64, c_vp, c_vp, c_vp]),
     "prism_ids_select": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_i32, c_vp, c_vp,

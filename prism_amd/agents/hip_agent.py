@@ -337,6 +337,8 @@ class _DrawCount:
 
 
 class HipAgent:
+    CURSOR_FORM = "either slot"               # _fused_key's `form` for a capture whose graphs bake one cursor slot each
+
     def __init__(self, model, action_selector, eval_action_selector, target_model, config, in_channels,
                  n_actions, process_group=None):
         if not str(config.device).startswith("cuda"):
@@ -398,6 +400,7 @@ class HipAgent:
         # Agent.forward replayed from one hipGraph per (number of observations, selector): H2D of the observations, embed,
         # forward tiles, selector kernel, D2H of the actions (config.act_graph = False: the eager launches)
         self.act_graph = bool(getattr(config, "act_graph", True))
+        self.fill_graph_replays = 0               # replays of the cursor-form step graph (step_fused fill_graph; tests, tools)
         # epsilon-greedy with one coin per observation, tossed on the device (prism_egreedy_select), where the default tosses
         # the reference's one host coin per call.  The position of that stream is the selector's epsilon.current_step; the
         # device keeps a copy (_eg_word) that captured calls advance, _eg_dev_steps is what the host knows it to hold
@@ -574,7 +577,9 @@ class HipAgent:
         self._set_hyper()
         return d
 
-    def _launch_fused(self, buf, d, part="all"):
+    def _launch_fused(self, buf, d, part="all", cursor_slot=None):
+        """The step's launches on the current stream.  ``cursor_slot``: None, the front takes the ring's size by value; 0 | 1,
+        it reads ``min(cursor[slot], capacity)`` from the buffer's cursor words on the device (prism_step_front_cursor)."""
         L, st = N.lib(), N.current_stream_handle
         rp = ctypes.byref(buf._desc)
         smp = buf.buffer._sampler
@@ -588,7 +593,11 @@ class HipAgent:
         d.fuse_tail = int(part == "all" and self.world == 1 and self.fuse_tail and self._opt_key is None)
         if part in ("all", "front"):
             d.embed_done = 1
-            if buf._ring_kind:                             # a byte ring: the same launch, its row loads a word per thread
+            if cursor_slot is not None:
+                N.check(L.prism_step_front_cursor(ctypes.byref(d), rp, buf._ring_kind, N.ptr(buf._cursor_words), cursor_slot,
+                                                  None, buf.seed, buf._draws, buf.buffer._sampler._beta, N.ptr(buf._index),
+                                                  N.ptr(buf._weight), st()), "prism_step_front_cursor")
+            elif buf._ring_kind:                           # a byte ring: the same launch, its row loads a word per thread
                 N.check(L.prism_step_front_ring(ctypes.byref(d), rp, buf._ring_kind, buf._size, None, buf.seed, buf._draws,
                                                 buf.buffer._sampler._beta, N.ptr(buf._index), N.ptr(buf._weight), st()),
                         "prism_step_front_ring")
@@ -608,31 +617,52 @@ class HipAgent:
                 N.check(L.prism_step_back(ctypes.byref(d), rp, N.ptr(buf._index), smp._alpha, smp._eps, st()),
                         "prism_step_back")
 
-    def step_fused(self, buf, eager=False, use_graph=True):
+    def step_fused(self, buf, eager=False, use_graph=True, fill_graph=False):
         """Sample + update + priority writeback as four launches on one GPU, five around an all-reduce (prism_step_front, fwd_bwd,
         prism_step_back); replayed from a hipGraph when the replay is full (its size is baked into
-        the captured launches) and the RNG counters live on the device."""
+        the captured launches) and the RNG counters live on the device.  ``fill_graph`` (the learner passes its
+        ``graph_while_filling``, the one place the knob is held): while the ring is still filling, replay the form whose front
+        reads the ring's size from the buffer's cursor words instead (``fill_form``); at the fill the step goes over to the
+        by-value graph."""
         d = self._fused_begin(buf)
-        graphable = use_graph and not eager and buf._size == buf.capacity
+        slot = None
+        if use_graph and not eager and fill_graph and buf._size < buf.capacity and self.fill_form(buf) is None:
+            slot = buf._cursor_known[0] if buf._cursor_known is not None else 0
+        graphable = use_graph and not eager and (buf._size == buf.capacity or slot is not None)
         with torch.cuda.device(self.device):
             if not graphable:
                 self._launch_fused(buf, d)
             else:
-                key = self._fused_key(buf, d)
+                key = self._fused_key(buf, d, slot)
                 g = self._graphs.get(key)
+                if slot is not None:
+                    buf.seed_cursor(slot)                       # an eager ingest, a bulk load or a restore moved the count
                 if g is None:
                     self._graphs.clear()                        # arguments changed: older captures are stale
-                    self._launch_fused(buf, d)                  # first full-buffer step runs eagerly
+                    self._launch_fused(buf, d, cursor_slot=slot)   # first step of a form runs eagerly
                     self._graphs[key] = "warm"
                 elif g == "warm":
                     torch.cuda.current_stream().synchronize()
-                    self._graphs[key] = self._capture(buf, d)   # capture, then replay once = this step
+                    self._graphs[key] = self._capture(buf, d, slot)   # capture, then replay once = this step
                 else:
                     g[0].replay()
+                    if slot is not None:
+                        self.fill_graph_replays += 1
                     if len(g) == 2:          # data parallel, two graphs around an eagerly launched collective
                         self._allreduce()
                         g[1].replay()
         return self._fused_mirror(buf)
+
+    def fill_form(self, buf):
+        """Why the step cannot run in the form that reads the ring's size from the device (None: it can)."""
+        if self.world != 1:
+            return "data parallel (world > 1) keeps the step eager until the ring is full"
+        if self.tau_rng != "philox" or buf.mass_rng != "philox":
+            return "tau_rng and per_mass_rng must be 'philox'"
+        if buf._desc is None or buf._size != min(buf._serial, buf.capacity):
+            return ("the ring's write serial is behind its size (a load in the reference's format): the step stays eager "
+                    "until the ring is full")
+        return None
 
     def _fused_begin(self, buf):
         """What every fused step does on the host before its launches: the sticky bits polled, the descriptor bound to the
@@ -647,11 +677,14 @@ class HipAgent:
         d.offset = self._draw_offset               # device counter + what update() has consumed: never the same draw twice
         return d
 
-    def _fused_key(self, buf, d):
-        """Everything a captured ``_launch_fused`` bakes by value: hyper-parameters, seeds, beta / alpha, offsets."""
+    def _fused_key(self, buf, d, form=None):
+        """Everything a captured ``_launch_fused`` bakes by value: hyper-parameters, seeds, beta / alpha, offsets -- and the
+        ring's size, or what stands for it in the cursor form: ``form`` (the step graph: the slot of the word that holds the
+        size; the captured iteration: ``CURSOR_FORM``, its two graphs bake one slot each)."""
         h, smp = d.hyper, buf.buffer._sampler
-        return (id(buf), buf._size, self.world, h.lr, h.beta1, h.beta2, h.eps, h.max_grad_norm, h.grad_scale, self._opt_key,
-                self.seed, buf.seed, smp._beta, smp._alpha, smp._eps, self._draw_offset, buf._draws, self.overlap_writeback)
+        return (id(buf), buf._size if form is None else ("cursor", form), self.world, h.lr, h.beta1, h.beta2,
+                h.eps, h.max_grad_norm, h.grad_scale, self._opt_key, self.seed, buf.seed, smp._beta, smp._alpha, smp._eps,
+                self._draw_offset, buf._draws, self.overlap_writeback)
 
     def _fused_mirror(self, buf):
         """The host mirrors of one fused step that ran (eagerly, from the step graph, or inside a larger replay): the two
@@ -660,11 +693,11 @@ class HipAgent:
         buf._fused_draws += self._B
         return self._step_done()
 
-    def _capture(self, buf, d):
+    def _capture(self, buf, d, cursor_slot=None):
         if self.world == 1:
             g = torch.cuda.CUDAGraph()
             with graph_capture(g):
-                self._launch_fused(buf, d)
+                self._launch_fused(buf, d, cursor_slot=cursor_slot)
             g.replay()
             return (g,)
         if self.collective_in_graph:

@@ -5,8 +5,11 @@ Every piece a replay needs keeps its position on the device: the environments' s
 acting draws in ``rng_counters[2]``, the epsilon-greedy rows in the agent's device word, the observations in two ping-pong
 buffers, and the ring cursor in the buffer's two cursor words (``prism_replay_ingest_cursor``).  What the capture bakes by
 value alternates with the parity of the ping-pong: two graphs, one per starting parity; the cursor slot of an ingest launch
-is the parity of the observation buffer it reads.  The capture is a single chain on a single stream: no side stream, no
-event fork (a graph with parallel branches needs more hardware queues than a process may have open).
+is the parity of the observation buffer it reads.  While the ring is still filling (``config.graph_while_filling``) the step's
+front launch reads the ring's size from the cursor word the last of the k ingest launches wrote, slot ``p0 ^ (k & 1)``
+(``prism_step_front_cursor``); at the fill the loop goes over to the form that takes the size by value.  The capture is a
+single chain on a single stream: no side stream, no event fork (a graph with parallel branches needs more hardware queues
+than a process may have open).
 
 The host mirrors of everything the replay advanced are applied right behind it, by the same routines the eager calls use
 (``HipAgent._act_mirror`` / ``_fused_mirror``, ``_DeviceEnv._step_mirror``, ``HipReplayBuffer.extend_cursor_mirror``):
@@ -31,7 +34,8 @@ class CapturedLoop:
 
     # ------------------------------------------------------------------ conditions
     def check(self):
-        """``(reason, None)`` when the next iteration cannot be a replay, else ``(None, (selector, its native key))``."""
+        """``(reason, None)`` when the next iteration cannot be a replay, else ``(None, (selector, its native key, whether
+        the step's front reads the ring's size from the device))``."""
         from prism_amd.agents.action_selectors import EGreedyActionSelector
         from prism_amd.collectors import VectorCollector
         from prism_amd.envs import _DeviceEnv
@@ -66,13 +70,20 @@ class CapturedLoop:
             return f"the training selector ({type(sel).__name__}) has no native kernel", None
         if buf._n_staged:
             return "a row staged by extend() is pending", None
-        if buf._desc is None or buf._size != buf.capacity:
-            return "the ring is not full yet (its size is baked into the step's launches)", None
-        return None, (sel, skey)
+        filling = buf._desc is None or buf._size != buf.capacity
+        if filling:
+            if not ln.graph_while_filling or buf._desc is None:
+                return "the ring is not full yet (its size is baked into the step's launches)", None
+            why = agent.fill_form(buf)
+            if why is not None:
+                return f"the ring is not full yet and graph_while_filling does not apply: {why}", None
+        return None, (sel, skey, filling)
 
     # ------------------------------------------------------------------ one iteration
-    def _record(self, p0, k, d, skey, bufs):
-        """Enqueue one iteration that starts at ping-pong parity ``p0`` on the current stream (inside a capture)."""
+    def _record(self, p0, k, d, skey, bufs, filling=False):
+        """Enqueue one iteration that starts at ping-pong parity ``p0`` on the current stream (inside a capture).  ``filling``:
+        the step's front reads the ring's size from the cursor word the last ingest launch wrote -- launch j reads slot
+        ``p0 ^ (j & 1)`` and writes the other, so behind k launches the count stands in slot ``p0 ^ (k & 1)``."""
         ln = self.learner
         agent, buf, envs = ln.agent, ln.experience_buffer, ln.timestep_collector.envs
         act64, act32, obs32 = bufs
@@ -85,7 +96,7 @@ class CapturedLoop:
             envs._enqueue_step(act64, p)
             act32.copy_(act64)                         # (the ring stores int32 actions: extend_batch's conversion, captured)
             buf.enqueue_extend_cursor(p, obs, envs._next_obs, act32, envs._reward, envs._done, envs._truncated)
-        agent._launch_fused(buf, d)
+        agent._launch_fused(buf, d, cursor_slot=p0 ^ (k & 1) if filling else None)
 
     def run(self):
         """One training iteration as one replay: the rows it collected, or None when this iteration has to be the eager
@@ -95,7 +106,7 @@ class CapturedLoop:
         self.reason, plan = self.check()
         if plan is None:
             return None
-        sel, skey = plan
+        sel, skey, filling = plan
         agent, buf, col = ln.agent, ln.experience_buffer, ln.timestep_collector
         envs = col.envs
         n = envs.n_envs
@@ -107,8 +118,9 @@ class CapturedLoop:
             buf._stream_table(n)
             d = agent._fused_begin(buf)
             ep = buf._ep_return
-            key = (agent._fused_key(buf, d), skey, id(sel), id(envs), n, k, agent._B, agent.workspace.data_ptr(),
-                   buf._stream_tab.data_ptr(), None if ep is None else ep.data_ptr(), buf._clip)
+            # (the cursor form's key carries the form, not a slot: the two graphs, one per starting parity, bake one each)
+            key = (agent._fused_key(buf, d, agent.CURSOR_FORM if filling else None), skey, id(sel), id(envs), n, k, agent._B,
+                   agent.workspace.data_ptr(), buf._stream_tab.data_ptr(), None if ep is None else ep.data_ptr(), buf._clip)
             if key != self._key:                       # what a capture bakes has changed: this iteration runs eagerly
                 self._key, self._graphs = key, "warm"
                 return None
@@ -128,7 +140,7 @@ class CapturedLoop:
                     for p in (0, 1):
                         graphs[p] = g = torch.cuda.CUDAGraph()
                         with graph_capture(g, capture_error_mode="thread_local"):
-                            self._record(p, k, d, skey, bufs)
+                            self._record(p, k, d, skey, bufs, filling)
                 except Exception as e:          # noqa: BLE001 -- any capture failure selects the eager loop, for good
                     torch.cuda.synchronize()
                     self.failed, self._graphs = repr(e), None

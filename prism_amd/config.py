@@ -14,6 +14,13 @@ constructing unchanged); they are read with ``getattr(config, name, default)``:
                       seeded reference run; costs one D2H sync per sample)
     tau_rng           "philox" (in-kernel, default)  | "torch" (torch.rand on the model device)
     hip_graph         bool, capture Learner.step() into a hipGraph (default True on GPU)
+    graph_while_filling
+                      bool (default False): replay the fused step -- and, with captured_loop, the whole iteration --
+                      from a hipGraph while the replay ring is still filling, not only once it is full.  The step's
+                      front launch then reads the ring's size from the device (prism_step_front_cursor); at the fill
+                      the step goes over to the by-value graph.  Results are bit for bit those of the run with it off.
+                      Stays eager until full under data parallel, the parity RNG modes, or a ring whose write serial
+                      is behind its size (a reference-format load): ``Learner.captured_loop_refusal()`` says which
     e_greedy_per_env  bool, epsilon-greedy tosses one coin per observation, on the device (Philox,
                       inside the acting hipGraph), instead of the reference's one host coin per
                       Agent.forward call (default False); for vector collectors under use_e_greedy

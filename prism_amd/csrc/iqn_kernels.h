@@ -350,6 +350,7 @@ __device__ __forceinline__ void conv_embed_rows(const float *s_obs, const float 
 
 __device__ void embed_extra_block(const IqnArgs &a, int x, float *s_red);
 
+#ifndef PRISM_STEP_NO_KERNELS          // (front_cursor.hip includes this header for its device functions alone)
 __global__ __launch_bounds__(256) void iqn_embed_kernel(IqnArgs a) {
     __shared__ __attribute__((aligned(16))) float s_obs[1024];
     __shared__ __attribute__((aligned(16))) float s_w[CONV_W_FLOATS];
@@ -371,6 +372,7 @@ __global__ __launch_bounds__(256) void iqn_embed_kernel(IqnArgs a) {
     __syncthreads();
     conv_embed_rows(s_obs, s_w, s_b, C, dst, tid);
 }
+#endif  // PRISM_STEP_NO_KERNELS
 
 // Workgroup barrier that orders LDS traffic only: global loads issued before it stay in flight
 // (a plain __syncthreads() also waits for vmcnt(0), which would serialise every weight prefetch).

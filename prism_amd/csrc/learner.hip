@@ -768,22 +768,23 @@ static int check_replay_for_step(const prism_learner_desc *ld, const prism_repla
     return PRISM_OK;
 }
 
-// the launch of prism_step_front / prism_step_front_ring
+// the launch of prism_step_front / prism_step_front_ring and, with `cursor` set, of prism_step_front_cursor (`size` unused:
+// the kernel reads it)
 static int step_front(const prism_learner_desc *ld, const prism_replay_desc *rp, int32_t ring_kind, int64_t size,
                       const float *mass, uint64_t seed, uint64_t offset, float beta, int64_t *out_index, float *out_weight,
-                      prism_stream_t stream_) {
+                      prism_stream_t stream_, const int64_t *cursor = nullptr, int32_t slot = 0) {
     LearnerPlan pl;
     int rc = check_learner(ld, pl);
     if (rc) return rc;
     rc = check_replay_for_step(ld, rp);
     if (rc) return rc;
-    PRISM_CHECK_ARG(size > 0 && size <= rp->capacity, "size must be in (0, capacity] (empty storage)");
+    PRISM_CHECK_ARG(cursor || (size > 0 && size <= rp->capacity), "size must be in (0, capacity] (empty storage)");
     PRISM_CHECK_ARG(out_index && (rp->tree == nullptr || out_weight), "null outputs");
     hipStream_t stream = (hipStream_t)stream_;
     IqnArgs a;
     fill_iqn_args(ld, pl, a);
     FrontArgs f;
-    f.size = size;
+    f.size = cursor ? 1 : size;
     f.mass = mass;
     f.seed = seed;
     f.offset = offset;
@@ -802,7 +803,9 @@ static int step_front(const prism_learner_desc *ld, const prism_replay_desc *rp,
         ProfileScope ps_(K_FRONT, stream);
         const IqnArgs af = front_args(a);
         const int extra = front_extra_blocks(extra_dims(af));
-        if (ring_kind == PRISM_RING_U8)
+        if (cursor)
+            launch_front_cursor(ring_kind, ld->batch + extra, stream, af, *rp, f, cursor, slot);          // (front_cursor.hip)
+        else if (ring_kind == PRISM_RING_U8)
             hipLaunchKernelGGL(step_front_byte_ring_kernel, dim3(ld->batch + extra), dim3(256), 0, stream, af, *rp, f);
         else
             hipLaunchKernelGGL(step_front_kernel, dim3(ld->batch + extra), dim3(256), 0, stream, af, *rp, f);
@@ -826,6 +829,23 @@ extern "C" int prism_step_front_ring(const prism_learner_desc *ld, const prism_r
                         ((reinterpret_cast<uintptr_t>(rp->obs) | reinterpret_cast<uintptr_t>(rp->succ_obs)) & 3) == 0,
                     "a byte ring's obs / succ_obs must be 4-byte aligned");
     return step_front(ld, rp, ring_kind, size, mass, seed, offset, beta, out_index, out_weight, stream_);
+}
+
+// prism_step_front_ring with the ring's size read on the device (front_cursor.hip): size =
+// min(cursor[slot], capacity).  `slot` is by value: a captured graph bakes it.
+extern "C" int prism_step_front_cursor(const prism_learner_desc *ld, const prism_replay_desc *rp, int32_t ring_kind,
+                                       const int64_t *cursor, int32_t slot, const float *mass, uint64_t seed,
+                                       uint64_t offset, float beta, int64_t *out_index, float *out_weight,
+                                       prism_stream_t stream_) {
+    PRISM_CHECK_ARG(ring_kind == PRISM_RING_F32 || ring_kind == PRISM_RING_U8,
+                    "ring_kind must be PRISM_RING_F32 or PRISM_RING_U8");
+    PRISM_CHECK_ARG(ring_kind != PRISM_RING_U8 || rp == nullptr ||
+                        ((reinterpret_cast<uintptr_t>(rp->obs) | reinterpret_cast<uintptr_t>(rp->succ_obs)) & 3) == 0,
+                    "a byte ring's obs / succ_obs must be 4-byte aligned");
+    PRISM_CHECK_ARG(cursor != nullptr, "null cursor");
+    PRISM_CHECK_ARG(slot == 0 || slot == 1, "slot must be 0 or 1");
+    PRISM_CHECK_ARG(rp == nullptr || (out_index && (rp->tree == nullptr || out_weight)), "null outputs");
+    return step_front(ld, rp, ring_kind, 0, mass, seed, offset, beta, out_index, out_weight, stream_, cursor, slot);
 }
 
 static int step_back(const prism_learner_desc *ld, const prism_opt_hyper *opt, const prism_replay_desc *rp, const int64_t *index,

@@ -557,6 +557,7 @@ __device__ __forceinline__ void conv_bwd_sample_row(const float *s_dc, const flo
     }
 }
 
+#ifndef PRISM_STEP_NO_KERNELS          // (front_cursor.hip includes this header for its device functions alone)
 __global__ __launch_bounds__(256) void dqn_loss_kernel(IqnArgs a) {
     __shared__ __attribute__((aligned(16))) float s_x[E_DIM], s_xhat[E_DIM], s_nx[E_DIM], s_tmp[E_DIM];
     __shared__ float s_ob[1000];
@@ -672,9 +673,11 @@ __global__ __launch_bounds__(256) void dqn_loss_kernel(IqnArgs a) {
     __syncthreads();
     conv_bwd_sample_row(s_tmp, s_ob, a.C, a.ws.convpart + (int64_t)b * CONV_ROW);
 }
+#endif  // PRISM_STEP_NO_KERNELS
 
 // acting forward of the one-layer head (agent.py:31-41 -> q_ensemble.py:44-48): Q values of observation b from its
 // embedding (left in ws.e_cur by the embed launch), with the routines the loss kernel uses.  out_q: [1][n_pad][A].
+#ifndef PRISM_STEP_NO_KERNELS          // (front_cursor.hip includes this header for its device functions alone)
 __global__ __launch_bounds__(256) void dqn1_act_kernel(IqnArgs a, float *__restrict__ out_q) {
     __shared__ __attribute__((aligned(16))) float s_x[E_DIM], s_xhat[E_DIM];
     __shared__ float s_q[16], s_red[64];
@@ -689,6 +692,7 @@ __global__ __launch_bounds__(256) void dqn1_act_kernel(IqnArgs a, float *__restr
     dqn_q_values(s_x, P + a.off.h_w1, P + a.off.h_b1, a.A, s_q, s_red);
     if (tid < a.A) out_q[(int64_t)b * a.A + tid] = s_q[tid];
 }
+#endif  // PRISM_STEP_NO_KERNELS
 
 // post role: dW[a][n] = sum_{b: act=a} dq_b * y_b[n], db[a], and with LayerNorm dg[n] = sum_b dy_b[n] xhat_b[n],
 // dbeta[n] = sum_b dy_b[n] (dy_b = dq_b W[act_b]).  With y = g * xhat + beta this is the algebra of

@@ -457,6 +457,7 @@ __device__ __forceinline__ void step_front_body(const IqnArgs &a, const prism_re
     PRISM_STAMP(31);
 }
 
+#ifndef PRISM_STEP_NO_KERNELS          // (front_cursor.hip includes this header for its device functions alone)
 __global__ __launch_bounds__(256) void step_front_kernel(IqnArgs a, prism_replay_desc rp, FrontArgs f) {
     step_front_body<PRISM_RING_F32>(a, rp, f, threadIdx.x, blockIdx.x);
 }
@@ -465,6 +466,13 @@ __global__ __launch_bounds__(256) void step_front_kernel(IqnArgs a, prism_replay
 __global__ __launch_bounds__(256) void step_front_byte_ring_kernel(IqnArgs a, prism_replay_desc rp, FrontArgs f) {
     step_front_body<PRISM_RING_U8>(a, rp, f, threadIdx.x, blockIdx.x);
 }
+#endif  // PRISM_STEP_NO_KERNELS
+
+// prism_step_front_cursor's launch: step_front_body with the number of stored rows read from cursor[slot] on the device.
+// Its two kernels (fp32 ring, byte ring) are a translation unit, hence a code object, of their own (front_cursor.hip): this
+// header's code object is what it was before they came.
+void launch_front_cursor(int32_t ring_kind, unsigned blocks, hipStream_t stream, const IqnArgs &a, const prism_replay_desc &rp,
+                         const FrontArgs &f, const int64_t *cursor, int32_t slot);
 
 // ------------------------------------------------------------------------------------------
 // post: 1024-thread blocks, three roles.

@@ -728,6 +728,9 @@ class HipReplayBuffer:
         if bits & N.STATUS_INGEST_BAD_CURSOR:
             raise RuntimeError("enqueue_extend_cursor: a launch read a negative ring cursor from the device (it wrote nothing "
                                "to the ring)")
+        if bits & N.STATUS_FRONT_BAD_SIZE:
+            raise RuntimeError("prism_step_front_cursor: a launch read a ring size <= 0 from the device cursor (it sampled "
+                               "as from a ring of one row)")
 
     def update_priority(self, indices, priorities, take_abs=False):
         if not self.use_per:

@@ -33,6 +33,7 @@ class Learner:
         self.fused = True
         self.hip_graph = True
         self.captured_loop = False
+        self.graph_while_filling = False
         self.captured_iterations = 0
         self._captured = None
         self._resumed = False
@@ -66,6 +67,9 @@ class Learner:
         # ... / run a whole iteration (k x (act, environment step, ingest) + the step) as ONE hipGraph replay once its
         # conditions hold (prism_amd/captured_loop.py; off by default, and the loop is the eager one wherever they do not)
         self.captured_loop = bool(getattr(config, "captured_loop", False))
+        # ... / replay the step, and the captured iteration, while the ring is still filling as well (the front launch
+        # then reads the ring's size from the device; off by default)
+        self.graph_while_filling = bool(getattr(config, "graph_while_filling", False))
         self.captured_iterations = 0
         self._captured = None
         self._resumed = False
@@ -91,7 +95,7 @@ class Learner:
             buf.flush()
             if self.use_per:
                 buf.buffer._sampler._beta = 0.5
-            td = agent.step_fused(buf, eager=eager, use_graph=self.hip_graph)
+            td = agent.step_fused(buf, eager=eager, use_graph=self.hip_graph, fill_graph=self.graph_while_filling)
             self._after_fused_update(timesteps_this_iteration)
             return td
         t0 = time.perf_counter() if tp else 0.0
