@@ -615,6 +615,35 @@ int prism_act_forward(const prism_learner_desc *ld, const float *obs, int32_t n,
                       const float *tau_in, uint64_t seed, uint64_t offset, float *out_z, float *out_q,
                       prism_stream_t stream);
 
+/* Risk-sensitive acting (config.iqn_risk_policy_id; Dabney et al. 2018, "Risk-sensitive reinforcement learning"): the
+ * quantile samples of one acting forward, passed through a distortion beta, for prism_act_forward's tau_in.
+ *   out_tau[t*n + b] = float32(beta(u)), u = tau_raw_in ? tau_raw_in[t*n + b]
+ *     : float32(Philox4x32-10(seed, c0 + t*n + b, "TAU0" + 3)[0] >> 8) * 2^-24        (the acting forward's own draw)
+ *   beta is evaluated in float64 from the float32 u and narrowed once:
+ *     PRISM_RISK_NEUTRAL  u
+ *     PRISM_RISK_CVAR     eta * u                                                 0 < eta <= 1
+ *     PRISM_RISK_WANG     Phi(Phi^-1(u) + eta)                                    eta finite (< 0: risk-averse)
+ *     PRISM_RISK_CPW      u^eta / (u^eta + (1 - u)^eta)^(1 / eta)                 0 < eta <= 1
+ *     PRISM_RISK_POW      eta >= 0: u^(1 / (1 + |eta|)); eta < 0: 1 - (1 - u)^(1 / (1 + |eta|))     eta finite
+ *   every one maps 0 to 0 (Wang through Phi^-1(0) = -inf) and [0, 1] into [0, 1].
+ *   c0 = offset, plus rng_counters[2] when rng_counters is set and tau_raw_in is NULL; the launch then leaves that word
+ *   advanced by n * n_tau, exactly as prism_act_forward with tau_in == NULL does: the prism_act_forward behind it takes
+ *   out_tau as tau_in with ld->rng_counters unset.  With tau_raw_in the word is neither read nor written.
+ * The word while the launch runs: one lane per sample, ceil(n * n_tau / 256) workgroups, and every workgroup has to read the
+ * count before any advances it.  One atomic add per workgroup is both its read and its ticket; the tickets stand in bits
+ * 42 .. 61 (fewer than 2^20 workgroups: n * n_tau < 2^28), the count in bits 0 .. 41 and 62 .. 63 -- a count is
+ * k * 2^62 + c with c + n * n_tau < 2^42, which covers the training counts and those of evaluations (2^62 + c).  The holder
+ * of the last ticket takes the tickets off and adds n * n_tau: between launches the word is the plain count, and its value
+ * does not depend on the order of the workgroups.  Calls on one word must follow each other on the device.
+ * out_tau_raw (optional) [n_tau*n]: the raw samples u. */
+#define PRISM_RISK_NEUTRAL 0
+#define PRISM_RISK_CVAR 1
+#define PRISM_RISK_WANG 2
+#define PRISM_RISK_CPW 3
+#define PRISM_RISK_POW 4
+int prism_act_tau_distort(int32_t n, int32_t n_tau, int32_t policy, double eta, const float *tau_raw_in, uint64_t seed,
+                          uint64_t offset, uint64_t *rng_counters, float *out_tau, float *out_tau_raw, prism_stream_t stream);
+
 /* IDSActionSelector.generate_action_probs + select_action for ids_use_random_samples = False
  * (prism/agents/action_selectors.py:125-176): scores [n][A] = regret^2 / information gain, action [n] = argmin.
  * z / q: the buffers prism_act_forward filled.  out_aux (optional) [n][4][A]: ensemble mean, ensemble spread

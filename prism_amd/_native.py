@@ -24,6 +24,8 @@ INGEST_MAX_STREAMS = 65536
 WS_STATUS_WORD, WS_STATUS_BARRIER_TIMEOUT, WS_STATUS_COLLECTIVE_TIMEOUT = 7, 1, 2
 GEMM_MODES = {"auto": 0, "fp32": 1, "bf16x3": 2}
 ACT_WEIGHTS_CURRENT = 1
+RISK_NEUTRAL, RISK_CVAR, RISK_WANG, RISK_CPW, RISK_POW = 0, 1, 2, 3, 4          # prism_act_tau_distort's `policy`
+RISK_COUNT_BITS = 42          # ... and its word: a count is k * 2^62 + c with c + n * n_tau < 2^42
 # prism_learner_plan_info: the fields of `out` in order, and the names of the two form codes
 PLAN_FIELDS = ("bwd", "q_bwd", "conv_in_bwd", "n_chunks", "local_loss", "merged_loss", "split", "q_de_slots", "post_blocks")
 BWD_FORMS = ("none", "fp32", "bw3", "bw4", "lin")
@@ -168,6 +170,7 @@ SIGNATURES = {
                                                 c_vp, c_vp, c_vp]),
     "prism_step_back": (ctypes.c_int, [_P(LearnerDesc), _P(ReplayDesc), c_vp, c_f32, c_f32, c_vp]),
     "prism_act_forward": (ctypes.c_int, [_P(LearnerDesc), c_vp, c_i32, c_i32, c_vp, c_u64, c_u64, c_vp, c_vp, c_vp]),
+    "prism_act_tau_distort": (ctypes.c_int, [c_i32, c_i32, c_i32, ctypes.c_double, c_vp, c_u64, c_u64, c_vp, c_vp, c_vp, c_vp]),
     "prism_ids_select": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_i32, c_vp, c_vp,
                                         c_vp, c_vp, c_vp]),
     "prism_ids_sample_select": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_i32, c_vp,

@@ -406,6 +406,12 @@ class HipAgent:
         # device keeps a copy (_eg_word) that captured calls advance, _eg_dev_steps is what the host knows it to hold
         self.e_greedy_per_env = bool(getattr(config, "e_greedy_per_env", False))
         self._eg_word, self._eg_dev_steps = None, None
+        # risk-sensitive acting (config.iqn_risk_policy_id, agents/risk_policies.py): (PRISM_RISK_* id, eta).  Non-neutral:
+        # every acting forward embeds beta(tau) -- one prism_act_tau_distort in front of it (_act_launch); the update stays
+        # neutral.  Neutral: no launch, no buffer, the keys and records of an agent without the knob
+        from prism_amd.agents import risk_policies
+        self.risk = risk_policies.for_config(config)
+        self._risk_on = self.risk[0] != N.RISK_NEUTRAL
         self._param_epoch, self._act_packed_at = 0, None
         # (the reference's async evaluator loads weights straight into agent.model, async_agent_evaluator.py:29)
         self.model.register_load_state_dict_post_hook(lambda module, incompatible: self._params_replaced())
@@ -769,15 +775,27 @@ class HipAgent:
         qb = torch.empty((dm.n_heads, n_pad, dm.n_actions), device=self.device) if self._act_q else None
         return z, qb, n_pad, T
 
-    def _act_launch(self, obs, n, T, tau, offset, z, qb, rng_counters, act_flags):
+    def _risk_buffer(self, n, T):
+        """Where ``prism_act_tau_distort`` leaves the distorted samples of an acting pass of ``n`` observations (None for
+        a neutral agent: no launch, no buffer).  A capture bakes its address: one per capturing slot, beside ``z``."""
+        return torch.empty(n * T, device=self.device) if self._risk_on and T > 0 else None
+
+    def _act_launch(self, obs, n, T, tau, offset, z, qb, rng_counters, act_flags, risk_tau=None):
         """The one ``prism_act_forward`` call, on the current stream.  The caller says who counts the draws, never the
         descriptor as the last learner step left it: a fused step leaves it pointing at the device counters (step_fused),
         and with them set ``prism_act_forward`` adds ``rng_counters[2]`` to ``offset`` and advances it.  That word belongs
         to the graph path (_forward_graph: ``rng_counters`` bound, offset 0), which seeds it from ``_act_draws`` whenever
         an eager call has moved the count on; the eager call (act_estimates) draws at the HOST's count (``rng_counters``
         None, offset ``_act_draws``) and has the packed weight copies rebuilt (``act_flags`` 0).  Both fields go back to
-        what they were.  A capture bakes every argument: ``obs``, ``z``, ``qb`` are the capturing slot's own buffers."""
+        what they were.  A capture bakes every argument: ``obs``, ``z``, ``qb`` are the capturing slot's own buffers.
+        With a risk policy one ``prism_act_tau_distort`` runs first: it draws the raw samples where the forward would have
+        (or takes ``tau`` as the raw ones), advances the device word when it is bound, and leaves beta of them in
+        ``risk_tau`` (_risk_buffer), which the forward then takes as explicit samples with the word unbound."""
         d = self._desc
+        if self._risk_on:
+            N.check(N.lib().prism_act_tau_distort(n, T, self.risk[0], self.risk[1], N.ptr(tau), self.seed, offset, rng_counters,
+                                                  N.ptr(risk_tau), None, N.current_stream_handle()), "prism_act_tau_distort")
+            tau, rng_counters = risk_tau, None
         keep = d.rng_counters, d.act_flags
         d.rng_counters, d.act_flags = rng_counters, act_flags
         try:
@@ -789,6 +807,12 @@ class HipAgent:
     _SCORED = ("ids", "ids_sampled", "min_regret", "simple_ids")          # selector kernels that leave (n, A) scores behind
 
     def _selector_key(self, sel):
+        """``_kernel_key`` of the selector, with ``("risk", policy id, eta)`` behind it for an agent that acts under a risk
+        policy: every graph keyed by it (the acting graphs, the captured iteration) bakes the policy's launch."""
+        key = self._kernel_key(sel)
+        return key if key is None or not self._risk_on else key + (("risk",) + self.risk,)
+
+    def _kernel_key(self, sel):
         """The selector's native kernel and constants: ``("ids", lmbda, epsilon, rho_lower_bound, unsquish id)``,
         ``("ids_sampled", ...)`` with the same constants for ``ids_use_random_samples`` (the action is a Philox draw of the
         agent's seed: only where the quantile draws are, ``tau_rng == "philox"``), ``("greedy",)``,
@@ -891,7 +915,8 @@ class HipAgent:
             taus = torch.rand([T * n, 1], device=self.device)
         tau = None if taus is None else taus.to(self.device, torch.float32).reshape(-1).contiguous()
         with torch.cuda.device(self.device):          # at the host's acting count, packed weight copies rebuilt
-            self._act_launch(obs, n, T, tau, self._act_draws, z, qb, rng_counters=None, act_flags=0)
+            self._act_launch(obs, n, T, tau, self._act_draws, z, qb, rng_counters=None, act_flags=0,
+                             risk_tau=self._risk_buffer(n, T))
         self._act_draws += T * n
         self._act_raw = (z, qb, n, n_pad, T)
         dist = z[:n * T].view(n, T, A).permute(1, 0, 2) if z is not None else None
@@ -984,7 +1009,7 @@ class HipAgent:
                 self._act_graphs.clear()
             z, qb, n_pad, T = self._act_buffers(n)
             dev = self.device
-            st = dict(T=T, n_pad=n_pad, z=z, qb=qb, calls=0, g=None,
+            st = dict(T=T, n_pad=n_pad, z=z, qb=qb, rtau=self._risk_buffer(n, T), calls=0, g=None,
                       pin_in=[torch.zeros(shape, dtype=torch.float32).pin_memory() for _ in range(4)] if on_host else None,
                       obs=obs_in if mode == "ptr" else (None if on_host else torch.empty(shape, dtype=torch.float32, device=dev)),
                       scores=torch.empty((n, dm.n_actions), device=dev) if skey[0] in self._SCORED else None,
@@ -1011,7 +1036,7 @@ class HipAgent:
             # host link cost less than a copy node in front of it; the selector writes the actions to device AND pinned host)
             self._act_launch(st["pin_in"][slot] if on_host else st["obs"], n, st["T"], None, 0, st["z"], st["qb"],
                              rng_counters=self.rng_counters.data_ptr(),
-                             act_flags=N.ACT_WEIGHTS_CURRENT if current else 0)
+                             act_flags=N.ACT_WEIGHTS_CURRENT if current else 0, risk_tau=st["rtau"])
             self._select_launch(skey, st["z"], st["qb"], n, st["n_pad"], st["T"], st["act"][slot], st["pin_out"][slot],
                                 st["scores"], rng_counters=self.rng_counters.data_ptr(),
                                 eg_word=self._eg_word.data_ptr())
@@ -1047,6 +1072,10 @@ class HipAgent:
         """Before a launch that binds the device words: ``rng_counters[2]`` follows ``_act_draws`` and the epsilon-greedy
         word the selector's ``current_step`` whenever an eager call, an explore branch, an evaluation or a loaded checkpoint
         has moved the host's count on (a store on the stream, only then)."""
+        if self._risk_on and (self._act_draws & (2 ** 62 - 1)) >= 2 ** N.RISK_COUNT_BITS - 2 ** 28:
+            # (prism_act_tau_distort keeps its tickets in bits 42 .. 61 of the word while it runs, include/prism_hip.h)
+            raise ValueError(f"acting under a risk policy counts draws as k * 2^62 + c with c < 2^42 - 2^28; the count is "
+                             f"{self._act_draws}")
         if self._act_dev_draws != self._act_draws:
             self.rng_counters[2] = self._act_draws
             self._act_dev_draws = self._act_draws
@@ -1061,7 +1090,7 @@ class HipAgent:
         if st is None:
             z, qb, n_pad, T = self._act_buffers(n)
             scores = torch.empty((n, self.dims.n_actions), device=self.device) if skey[0] in self._SCORED else None
-            st = slots[key] = dict(z=z, qb=qb, n_pad=n_pad, T=T, scores=scores)
+            st = slots[key] = dict(z=z, qb=qb, n_pad=n_pad, T=T, scores=scores, rtau=self._risk_buffer(n, T))
         return st
 
     def _enqueue_act(self, obs, act, skey, current):
@@ -1075,7 +1104,7 @@ class HipAgent:
         st = self._act_slot(n, skey)
         ptr = self.rng_counters.data_ptr()
         self._act_launch(obs, n, st["T"], None, 0, st["z"], st["qb"], rng_counters=ptr,
-                         act_flags=N.ACT_WEIGHTS_CURRENT if current else 0)
+                         act_flags=N.ACT_WEIGHTS_CURRENT if current else 0, risk_tau=st["rtau"])
         self._select_launch(skey, st["z"], st["qb"], n, st["n_pad"], st["T"], act, None, st["scores"], rng_counters=ptr,
                             eg_word=self._eg_word.data_ptr())
 
@@ -1243,9 +1272,13 @@ class HipAgent:
     # ------------------------------------------------------------------ exact resume (prism_amd/util/snapshot.py)
     def _compat_record(self):
         """What a snapshot must share with the agent it is loaded into: the ``prism_model_dims`` fields, the parameter
-        count, the optimizer kind and where the quantile draws come from."""
+        count, the optimizer kind, where the quantile draws come from and -- only when it is not neutral, so that a neutral
+        agent's record is what it always was -- the risk policy it acts under."""
         rec = {name: getattr(self.dims, name) for name, _ in N.ModelDims._fields_}
         rec.update(n_params=int(self.flat.numel()), optimizer_kind=int(self.optimizer.kind), tau_rng=str(self.tau_rng))
+        if self._risk_on:
+            from prism_amd.agents import risk_policies
+            rec["risk_policy"] = risk_policies.canonical_id(self.risk)
         return rec
 
     def _state_part(self):
@@ -1257,7 +1290,10 @@ class HipAgent:
 
     def _check_snapshot(self, manifest):
         from prism_amd.util import snapshot
-        snapshot.check_compat((manifest.get("compat") or {}).get("agent"), self._compat_record(), "HipAgent.load_state")
+        stored, mine = (manifest.get("compat") or {}).get("agent"), self._compat_record()
+        snapshot.check_compat(stored, mine, "HipAgent.load_state")
+        # (a neutral agent's record does not carry the field: a snapshot written under a policy is refused all the same)
+        snapshot.check_field("risk_policy", stored.get("risk_policy"), mine.get("risk_policy"), "HipAgent.load_state")
 
     def _restore_part(self, directory, part):
         self.load(directory)

@@ -68,6 +68,7 @@ class IQNHead(nn.Module):
         self.n_quantile_samples_per_action = n_tau_act
         self.huber_k, self.use_double_q_learning = huber_k, double_q
         self.distributional_loss_weight, self.propagate_grad = loss_weight, propagate_grad
+        self.risk_policy = None          # (PRISM_RISK_* id, eta) of a non-neutral config.iqn_risk_policy_id (model_factory)
         self.cos_basis_range = torch.arange(1, n_basis + 1, 1, device=device)
         self.phi = nn.Sequential(nn.Linear(n_basis, n_in), nn.ReLU()).to(device)
         self.model = None
@@ -90,7 +91,11 @@ class IQNHead(nn.Module):
         e = e.reshape(e.shape[0], -1)
         T = self.n_quantile_samples_per_action if for_action else n_quantile_samples
         taus = torch.rand([T * e.shape[0], 1], device=e.device)
-        c = torch.cos(torch.tile(taus, [1, self.n_basis]) * self.cos_basis_range.to(e.device) * np.pi)
+        embedded = taus
+        if for_action and self.risk_policy is not None:          # (acting only: the hook of iqn_model.py:73-78)
+            from prism_amd.agents import risk_policies
+            embedded = risk_policies.distort(taus, self.risk_policy)
+        c = torch.cos(torch.tile(embedded, [1, self.n_basis]) * self.cos_basis_range.to(e.device) * np.pi)
         h = self.phi(c) * torch.tile(e, [T, 1])
         if self.model is not None:
             h = self.model(h)

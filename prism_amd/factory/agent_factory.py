@@ -4,7 +4,7 @@
 with the online weights), action selectors, and the optimizer of the reference's three-way choice
 (agent_factory.py:40-58: ``use_adam`` wins, then ``use_rmsprop``, else SGD), which ``HipAgent`` builds over its
 flat parameter buffer (``hip_agent.build_optimizer``)."""
-from prism_amd.agents import action_selectors
+from prism_amd.agents import action_selectors, risk_policies
 from prism_amd.agents.hip_agent import HipAgent
 from prism_amd.factory import model_factory
 
@@ -25,6 +25,9 @@ def build_agent(config, obs_shape, n_actions, process_group=None):
     if ids_kind == "simple_ids" and config.ids_use_random_samples:
         raise ValueError("ids_action_selector = 'simple_ids' has no sampled form: ids_use_random_samples must be off "
                          "(the reference's SimpleIDSActionSelector raises on it)")
+    # (an id the acting path cannot honour -- unknown name, eta missing or out of range, Q heads -- is refused before a model
+    # is built)
+    risk_policies.for_config(config)
     model = model_factory.create_model(obs_shape, n_actions, config)
     target_model = None
     if config.use_target_network:

@@ -57,6 +57,9 @@ def create_model(env_state_shape, env_n_actions, config):
                       huber_k=config.iqn_huber_loss_kappa, double_q=config.use_double_q_learning,
                       loss_weight=config.distributional_loss_weight, propagate_grad=propagate,
                       device=dev)
+        from prism_amd.agents import risk_policies
+        risk = risk_policies.for_config(config)
+        iqn.risk_policy = None if risk == risk_policies.NEUTRAL else risk
     q = None
     if config.use_ids:
         q = QHeads(embed.output_dim, env_n_actions, config.ids_n_q_heads, config.use_layer_norm,

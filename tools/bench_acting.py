@@ -10,6 +10,9 @@ host -> actions on the host, per call, for the hipGraph form (default) and the e
 --rows eval     the ten-head IDS configuration in eval mode (agent.eval()), hipGraph form: the greedy evaluation selector,
                 the MinRegret one (eval_action_selector = "min_regret"; skipped with --no-min-regret, for a tree without it)
                 and greedy again -- the two greedy rows give the run-to-run spread of one visit
+--rows risk     the IQN configuration configs[2], hipGraph form: the greedy selector on the quantile mean, neutral, under each
+                risk policy (iqn_risk_policy_id: one prism_act_tau_distort in front of the forward) and neutral again -- the
+                two neutral rows give the run-to-run spread of one visit; --neutral-only for a tree without the knob
 --sizes 1,16    observation counts;  --reps 300   calls per median;  --tag NAME   prefix of every printed row (two trees
                 measured alternately in one visit)"""
 import argparse, contextlib, io, json, os, sys, time
@@ -53,7 +56,8 @@ def measure(cfg_i, graph, reps=400, sizes=(1, 4, 16), eval_mode=False, **over):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", default="all", choices=["all", "ids", "egreedy", "eval"])
+    ap.add_argument("--rows", default="all", choices=["all", "ids", "egreedy", "eval", "risk"])
+    ap.add_argument("--neutral-only", action="store_true")
     ap.add_argument("--no-min-regret", action="store_true")
     ap.add_argument("--sizes", default="1,4,16")
     ap.add_argument("--reps", type=int, default=400)
@@ -77,11 +81,15 @@ if __name__ == "__main__":
                 (3, "IDS + IQN, eval: greedy (again)", {})]
         if args.no_min_regret:
             del rows[1]
+    if args.rows == "risk":
+        policies = [] if args.neutral_only else ["cvar:0.25", "wang:-0.75", "cpw:0.71", "pow:-2"]
+        rows = [(2, "IQN, neutral", {})] + [(2, f"IQN, {p}", dict(iqn_risk_policy_id=p)) for p in policies] + \
+               [(2, "IQN, neutral (again)", {})]
     res = {}
     for cfg_i, name, over in rows:
         for graph in ((True,) if args.rows != "all" else (True, False)):
             r = measure(cfg_i, graph, args.reps, sizes, eval_mode=args.rows == "eval", **over)
-            what = f" {name}" if args.rows in ("egreedy", "eval") else " sampled" if over else ""
+            what = f" {name}" if args.rows in ("egreedy", "eval", "risk") else " sampled" if over else ""
             res[f"{args.tag}configs[{cfg_i}]{what} {'graph' if graph else 'eager'}"] = r
             for k, v in r.items():
                 print(f"{args.tag}{name:36s} {'hipGraph' if graph else 'eager   '} {k:18s}: {v:7.1f} us per Agent.forward (host -> actions on the host)",
