@@ -1,25 +1,22 @@
-// MinAtar Space Invaders (10 x 10 x 6 observations, 6 or 4 actions) for N lock-stepped environments: one launch per step, no
-// host value that changes between steps (the counters live in the state records), nothing read back.  The rules are the table
-// of DESIGN.md 7.6 -- a restatement of MinAtar v1, NOT checked against the `minatar` package.  A translation unit of its own, as
-// the other games' files are: their code objects and learner.hip's stay what they were.
+// MinAtar Space Invaders (10 x 10 x 6 observations, 6 or 4 actions) on the games' shared frame (env_frame.h).  The rules are the
+// table of DESIGN.md 7.6 -- a restatement of MinAtar v1, NOT checked against the `minatar` package.  A translation unit of its
+// own: learner.hip's code object stays what it was.
 //
-// One wave per environment, four environments per workgroup.  The game is wave-uniform: every lane computes it from the
-// environment's 32-byte state record (one broadcast load, scalar registers after readfirstlane), lane 0 writes the new
-// record.  MinAtar's three 10 x 10 maps are kept as what play can make of them: the aliens are a rigid 4 x 6 block (24
-// occupancy bits, an origin, a direction), a bullet map has at most one bullet per row (ten 4-bit fields x + 1, 0 = none).
-// Block and bullet rows stay PACKED in their words; every access is a shift of a scalar word, by a constant in the unrolled
-// loops and by a wave-uniform count where the origin decides the bit -- never an indexed array, which would go to the
-// private segment.  A board cell is six channels, which is no store unit: the image is 150 chunks of four consecutive HWC
-// elements (one 16-byte store in fp32, one 32-bit word in bytes), lane l owns chunks l, l + 64 and l + 128 (< 150) and looks
-// the at most two cells of a chunk up in the packed state from its side; a step whose episode goes on builds one image and
-// stores it twice.  No LDS, no private segment.
-#include "common.h"
+// The 32-byte state record comes in through one broadcast load, lane 0 writes the new one.  MinAtar's three 10 x 10 maps are
+// kept as what play can make of them: the aliens are a rigid 4 x 6 block (24 occupancy bits, an origin, a direction), a bullet
+// map has at most one bullet per row (ten 4-bit fields x + 1, 0 = none).  Block and bullet rows stay PACKED in their words;
+// every access is a shift of a scalar word, by a constant in the unrolled loops and by a wave-uniform count where the origin
+// decides the bit -- never an indexed array, which would go to the private segment.  A board cell is six channels, which is no
+// store unit: the image is 150 chunks, lane l owns chunks l, l + 64 and l + 128 (< 150) and looks the at most two cells of a
+// chunk up in the packed state from its side; a step whose episode goes on builds one image and stores it twice.  No LDS, no
+// private segment.
+#include "env_frame.h"
 
 namespace prism {
 
 // stream key, apart from "TAU0" + sid, "PERM", "UNIF", "IDSA", "EGRD", "ENVB", Freeway's five and Asterix's two
 constexpr uint64_t SI_KEY_COIN = 0x53504943ull;           // "SPIC": the sticky coin (the game draws nothing else)
-constexpr int SI_THREADS = 256, SI_PER_WG = SI_THREADS / WAVE, SI_CHANNELS = 6, SI_CELLS = 100;
+constexpr int SI_CHANNELS = 6, SI_CELLS = 100;
 constexpr int SI_CHUNKS = SI_CELLS * SI_CHANNELS / 4;     // 150 chunks of four elements
 // the block: 4 rows x 6 columns, first placed at rows 0..3, columns 2..7
 constexpr int SI_ROWS = 4, SI_COLS = 6, SI_FIRST_X = 2, SI_FIRST_Y = 0;
@@ -153,21 +150,6 @@ __host__ __device__ inline bool si_step(SiState &s, int a, float &reward) {
     return terminal;
 }
 
-struct SiArgs {
-    int n_envs, n_actions, step_limit, obs_kind;
-    double sticky_p;
-    uint64_t seed;
-    uint32_t *state, *status;
-    void *obs_next;          // the ping-pong buffer this launch writes the acting image into
-    void *next_obs;          // step only
-    float *reward;
-    uint8_t *done, *truncated;
-    const int64_t *actions;
-    const double *u_in;
-};
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-
 // The six channels of board cell `cell` = 10 y + x in bits 0..5, looked up from the lane's side; 0 for a cell off the board.
 __host__ __device__ inline uint32_t si_cell(const SiState &s, int cell) {
     const int y = (cell * 205) >> 11, x = cell - 10 * y;          // cell / 10 for cell < 1024
@@ -189,23 +171,6 @@ __host__ __device__ inline uint32_t si_image(const SiState &s, int lane) {
         img |= ((two >> ch) & 15u) << (4 * j);
     }
     return img;
-}
-__device__ __forceinline__ void si_store_chunk(void *base, int obs_kind, size_t at, uint32_t b) {
-    if (obs_kind == PRISM_OBS_U8) {
-        const uint32_t w = (b & 1u) | ((b & 2u) << 7) | ((b & 4u) << 14) | ((b & 8u) << 21);      // element j in byte j
-        __builtin_nontemporal_store(w, reinterpret_cast<uint32_t *>(base) + at);
-    } else {
-        stream_store4(reinterpret_cast<float4 *>(base) + at,
-                      make_float4((float)(b & 1u), (float)((b >> 1) & 1u), (float)((b >> 2) & 1u), (float)((b >> 3) & 1u)));
-    }
-}
-// One image of environment `env`: lane l writes chunks l, l + 64 and l + 128 (< 150).  Streaming stores: the next launch
-// reads them.
-__device__ __forceinline__ void si_store_image(void *base, int obs_kind, int env, int lane, uint32_t img) {
-    const size_t at = (size_t)env * SI_CHUNKS + lane;
-    si_store_chunk(base, obs_kind, at, img & 15u);
-    si_store_chunk(base, obs_kind, at + 64, (img >> 4) & 15u);
-    if (lane + 128 < SI_CHUNKS) si_store_chunk(base, obs_kind, at + 128, (img >> 8) & 15u);
 }
 __host__ __device__ inline void si_pack(const SiState &s, uint32_t (&w)[PRISM_ENV_STATE_WORDS]) {
     w[0] = s.block | ((uint32_t)(s.alien_x + 5) << 24) | ((uint32_t)s.alien_y << 28);
@@ -232,91 +197,47 @@ __device__ __forceinline__ void si_store_state(uint32_t *rec, const SiState &s) 
     p[1] = make_uint4(w[4], w[5], w[6], w[7]);
 }
 
-__global__ __launch_bounds__(SI_THREADS) void env_invaders_reset_kernel(SiArgs k) {
-    const int env = (int)uni(blockIdx.x * SI_PER_WG + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    if (env >= k.n_envs) return;
+__global__ __launch_bounds__(ENV_THREADS) void env_invaders_reset_kernel(EnvArgs k) {
+    int env, lane;
+    if (!env_of_wave(k, env, lane)) return;
     SiState s;
     s.last_action = 0;
     s.t = 0;
     si_reset(s);
-    si_store_image(k.obs_next, k.obs_kind, env, lane, si_image(s, lane));
+    env_store_image<SI_CHUNKS>(k.obs_next, k.obs_kind, env, lane, si_image(s, lane));
     if (lane == 0) si_store_state(k.state + (size_t)env * PRISM_ENV_STATE_WORDS, s);
 }
 
-__global__ __launch_bounds__(SI_THREADS) void env_invaders_step_kernel(SiArgs k) {
-    const int env = (int)uni(blockIdx.x * SI_PER_WG + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    if (env >= k.n_envs) return;
+__global__ __launch_bounds__(ENV_THREADS) void env_invaders_step_kernel(EnvArgs k) {
+    int env, lane;
+    if (!env_of_wave(k, env, lane)) return;
     uint32_t *rec = k.state + (size_t)env * PRISM_ENV_STATE_WORDS;
     const uint4 q0 = reinterpret_cast<const uint4 *>(rec)[0];
     const uint4 q1 = reinterpret_cast<const uint4 *>(rec)[1];
     const uint32_t w[PRISM_ENV_STATE_WORDS] = {uni(q0.x), uni(q0.y), uni(q0.z), uni(q0.w), uni(q1.x), uni(q1.y), uni(q1.z), uni(q1.w)};
     SiState s;
     si_unpack(w, s);
-    const uint64_t t0 = s.t;          // the counter of this step's draw
-    const int64_t raw = k.actions[env];
-    const uint32_t raw_lo = uni((uint32_t)raw), raw_hi = uni((uint32_t)((uint64_t)raw >> 32));
 
-    // the sticky coin
-    double u;
-    if (k.u_in) {
-        const uint64_t ub = __builtin_bit_cast(uint64_t, k.u_in[env]);
-        u = __builtin_bit_cast(double, (uint64_t)uni((uint32_t)ub) | ((uint64_t)uni((uint32_t)(ub >> 32)) << 32));
-    } else {
-        uint32_t r[4];
-        Philox(k.seed)(t0, ((uint64_t)env << 32) | SI_KEY_COIN, r);
-        u = u64_to_unit_double(uni(r[0]), uni(r[1]));
-    }
-
-    // the action: out of range acts as no-op and raises the sticky status bit; the 4-action set is n, l, r, f
-    const bool valid = raw_hi == 0u && raw_lo < (uint32_t)k.n_actions;
-    int a = valid ? (int)raw_lo : 0;
-    if (!valid && lane == 0) atomicOr(k.status, (uint32_t)PRISM_ENV_STATUS_BAD_ACTION);
+    // (the action's load is in flight while the coin is drawn)
+    int a = env_action(k.actions, env, k.n_actions, k.status, lane);
+    const double u = env_coin(k.u_in, k.seed, s.t, env, SI_KEY_COIN);
+    // the 4-action set is n, l, r, f
     if (k.n_actions == 4) a = a == 2 ? 3 : (a == 3 ? 5 : a);
-    if (u < k.sticky_p) a = s.last_action;
-    s.last_action = a;
+    a = env_sticky(a, u, k.sticky_p, s.last_action);
 
     float reward = 0.f;
     const bool terminal = si_step(s, a, reward);
-    // (10) counters and flags
-    s.ep_steps += 1u;
-    s.t += 1ull;
-    const bool truncated = k.step_limit > 0 && s.ep_steps >= (uint32_t)k.step_limit && !terminal;
+    const bool truncated = env_count_step(s.ep_steps, s.t, k.step_limit, terminal);          // (10) counters and flags
 
     uint32_t img = si_image(s, lane);
-    si_store_image(k.next_obs, k.obs_kind, env, lane, img);          // what the step returned, before any reset
-    if (terminal || truncated) {                                     // (wave-uniform) only then is the acting image another one
+    env_store_image<SI_CHUNKS>(k.next_obs, k.obs_kind, env, lane, img);          // what the step returned, before any reset
+    if (terminal || truncated) {                                                 // (wave-uniform) only then is the acting image another one
         si_reset(s);
         img = si_image(s, lane);
     }
-    si_store_image(k.obs_next, k.obs_kind, env, lane, img);          // what to act on next
-    if (lane == 0) {
-        si_store_state(rec, s);
-        k.reward[env] = reward;
-        k.done[env] = terminal ? 1 : 0;
-        k.truncated[env] = truncated ? 1 : 0;
-    }
-}
-
-// the checks and texts of env_breakout.hip's check_env but for the action counts: one descriptor, one contract
-static int check_env(const prism_env_desc *d) {
-    PRISM_CHECK_ARG(d, "null descriptor");
-    PRISM_CHECK_ARG(d->n_envs >= 1 && d->n_envs <= PRISM_ENV_MAX, "n_envs must be in [1, 65536]");
-    PRISM_CHECK_ARG(d->n_actions == 4 || d->n_actions == 6, "n_actions must be 4 or 6");
-    PRISM_CHECK_ARG(d->step_limit >= 0, "step_limit is negative");
-    // (written so that a NaN fails it)
-    PRISM_CHECK_ARG(d->sticky_p >= 0.0 && d->sticky_p <= 1.0, "sticky_p outside [0, 1]");
-    PRISM_CHECK_ARG(d->obs_kind == PRISM_OBS_F32 || d->obs_kind == PRISM_OBS_U8, "obs_kind must be PRISM_OBS_F32 or PRISM_OBS_U8");
-    PRISM_CHECK_ARG(d->state && d->status, "null state block / status word");
-    PRISM_CHECK_ARG(d->obs[0] && d->obs[1] && d->obs[0] != d->obs[1], "null or shared ping-pong observation buffers");
-    PRISM_CHECK_ARG(d->next_obs && d->reward && d->done && d->truncated, "null step outputs");
-    PRISM_CHECK_ARG(((uintptr_t)d->state | (uintptr_t)d->obs[0] | (uintptr_t)d->obs[1] | (uintptr_t)d->next_obs) % 16 == 0,
-                    "state block and observation buffers must be 16-byte aligned");
-    return PRISM_OK;
-}
-
-static SiArgs si_args(const prism_env_desc *d, int parity) {
-    return SiArgs{d->n_envs, d->n_actions, d->step_limit, d->obs_kind, d->sticky_p, d->seed, d->state, d->status,
-                  d->obs[parity], d->next_obs, d->reward, d->done, d->truncated, nullptr, nullptr};
+    env_store_image<SI_CHUNKS>(k.obs_next, k.obs_kind, env, lane, img);          // what to act on next
+    if (lane == 0) si_store_state(rec, s);
+    env_store_outcome(k, env, lane, reward, terminal, truncated);
 }
 
 }  // namespace prism
@@ -324,25 +245,16 @@ static SiArgs si_args(const prism_env_desc *d, int parity) {
 using namespace prism;
 
 extern "C" int prism_env_invaders_reset(const prism_env_desc *d, prism_stream_t stream_) {
-    const int rc = check_env(d);
+    const int rc = check_env(d, 4, "n_actions must be 4 or 6");
     if (rc != PRISM_OK) return rc;
-    SiArgs k = si_args(d, 0);
-    hipLaunchKernelGGL(env_invaders_reset_kernel, dim3((d->n_envs + SI_PER_WG - 1) / SI_PER_WG), dim3(SI_THREADS), 0,
-                       (hipStream_t)stream_, k);
-    PRISM_CHECK_LAUNCH();
-    return PRISM_OK;
+    return env_launch(env_invaders_reset_kernel, env_args(d, 0), stream_);
 }
 
 extern "C" int prism_env_invaders_step(const prism_env_desc *d, const int64_t *actions, const double *u_in, int32_t parity,
                                        prism_stream_t stream_) {
-    const int rc = check_env(d);
+    const int rc = check_env(d, 4, "n_actions must be 4 or 6");
     if (rc != PRISM_OK) return rc;
     PRISM_CHECK_ARG(actions, "actions is null");
     PRISM_CHECK_ARG(parity == 0 || parity == 1, "parity must be 0 or 1");
-    SiArgs k = si_args(d, parity ^ 1);
-    k.actions = actions, k.u_in = u_in;
-    hipLaunchKernelGGL(env_invaders_step_kernel, dim3((d->n_envs + SI_PER_WG - 1) / SI_PER_WG), dim3(SI_THREADS), 0,
-                       (hipStream_t)stream_, k);
-    PRISM_CHECK_LAUNCH();
-    return PRISM_OK;
+    return env_launch(env_invaders_step_kernel, env_args(d, parity ^ 1, actions, u_in), stream_);
 }

@@ -1,13 +1,11 @@
-// MinAtar Seaquest (10 x 10 x 10 observations, 6 actions) for N lock-stepped environments: one launch per step, no host value
-// that changes between steps (the counters live in the state records), nothing read back.  The rules are the table of
-// DESIGN.md 7.7 -- a restatement of MinAtar v1, NOT checked against the `minatar` package.  A translation unit of its own, as
-// the other games' files are: their code objects and learner.hip's stay what they were.
+// MinAtar Seaquest (10 x 10 x 10 observations, 6 actions) on the games' shared frame (env_frame.h).  The rules are the table of
+// DESIGN.md 7.7 -- a restatement of MinAtar v1, NOT checked against the `minatar` package.  A translation unit of its own:
+// learner.hip's code object stays what it was.
 //
-// One wave per environment, four environments per workgroup.  Unlike the four games of the 8-word record this one keeps
-// five ORDERED LISTS that grow and shrink (fish, enemy subs, enemy bullets, friendly bullets, divers); the record
-// (PRISM_ENV_SEAQUEST_STATE_WORDS words) holds them as fixed-capacity arrays in list order, one 32-bit word per entry, an
-// empty slot all zeros.  Lane i of the wave holds entry i of every list; the eight head words are wave-uniform (one
-// broadcast load, scalar registers after readfirstlane).
+// Unlike the four games of the 8-word record this one keeps five ORDERED LISTS that grow and shrink (fish, enemy subs, enemy
+// bullets, friendly bullets, divers); the record (PRISM_ENV_SEAQUEST_STATE_WORDS words) holds them as fixed-capacity arrays in
+// list order, one 32-bit word per entry, an empty slot all zeros.  Lane i of the wave holds entry i of every list; the eight
+// head words are wave-uniform (one broadcast load, scalar registers after readfirstlane).
 //   * a rule that visits a long list (enemy subs, fish, enemy bullets) runs on all of its entries at once; where the list
 //     order decides -- which of several enemies on a cell a bullet kills, which of several subs takes a bullet, the order of
 //     the bullets the subs fire -- it is a ballot and the lowest / highest set lane of it;
@@ -18,7 +16,7 @@
 // The image is built in 104 words of LDS per wave (one word per board cell, channel c in bit c: every entry ORs its own and
 // its trail cell), then lane l stores the four-element chunks l, l + 64, l + 128 and l + 192 (< 250).  No per-lane array is
 // indexed by a run-time value: no private segment.
-#include "common.h"
+#include "env_frame.h"
 
 namespace prism {
 
@@ -26,7 +24,7 @@ namespace prism {
 constexpr uint64_t SQ_KEY_COIN = 0x53515843ull;           // "SQXC": the sticky coin
 constexpr uint64_t SQ_KEY_ENEMY = 0x53515845ull;          // "SQXE": side, kind and row of an enemy spawn
 constexpr uint64_t SQ_KEY_DIVER = 0x53515844ull;          // "SQXD": side and row of a diver spawn
-constexpr int SQ_THREADS = 256, SQ_PER_WG = SQ_THREADS / WAVE, SQ_CHANNELS = 10, SQ_CELLS = 100;
+constexpr int SQ_CHANNELS = 10, SQ_CELLS = 100;
 constexpr int SQ_CHUNKS = SQ_CELLS * SQ_CHANNELS / 4;     // 250 chunks of four elements
 constexpr int SQ_CELL_WORDS = 104;                        // the board and a zero cell behind it (a chunk may end in cell 100)
 // capacities (DESIGN.md 7.7 derives them) and where the arrays start in the record
@@ -72,21 +70,6 @@ __device__ __forceinline__ void sq_reset(SqHead &h, SqLists &l) {
     l.fish = l.subs = l.ebullets = l.fbullets = l.divers = 0u;
 }
 
-struct SqArgs {
-    int n_envs, n_actions, step_limit, obs_kind;
-    double sticky_p;
-    uint64_t seed;
-    uint32_t *state, *status;
-    void *obs_next;          // the ping-pong buffer this launch writes the acting image into
-    void *next_obs;          // step only
-    float *reward;
-    uint8_t *done, *truncated;
-    const int64_t *actions;
-    const double *u_in;
-    const uint8_t *draws_in;
-};
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ uint64_t sq_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 // entry i of a list, wave-uniform (i is)
 __device__ __forceinline__ uint32_t sq_get(uint32_t v, int i) { return (uint32_t)__builtin_amdgcn_readlane((int)v, i); }
@@ -359,24 +342,6 @@ __device__ __forceinline__ uint32_t sq_image(uint32_t *cells, const SqHead &h, c
     }
     return img;
 }
-__device__ __forceinline__ void sq_store_chunk(void *base, int obs_kind, size_t at, uint32_t b) {
-    if (obs_kind == PRISM_OBS_U8) {
-        const uint32_t w = (b & 1u) | ((b & 2u) << 7) | ((b & 4u) << 14) | ((b & 8u) << 21);      // element j in byte j
-        __builtin_nontemporal_store(w, reinterpret_cast<uint32_t *>(base) + at);
-    } else {
-        stream_store4(reinterpret_cast<float4 *>(base) + at,
-                      make_float4((float)(b & 1u), (float)((b >> 1) & 1u), (float)((b >> 2) & 1u), (float)((b >> 3) & 1u)));
-    }
-}
-// One image of environment `env`: lane l writes chunks l, l + 64, l + 128 and l + 192 (< 250).  Streaming stores: the next
-// launch reads them.
-__device__ __forceinline__ void sq_store_image(void *base, int obs_kind, int env, int lane, uint32_t img) {
-    const size_t at = (size_t)env * SQ_CHUNKS + lane;
-    sq_store_chunk(base, obs_kind, at, img & 15u);
-    sq_store_chunk(base, obs_kind, at + 64, (img >> 4) & 15u);
-    sq_store_chunk(base, obs_kind, at + 128, (img >> 8) & 15u);
-    if (lane + 192 < SQ_CHUNKS) sq_store_chunk(base, obs_kind, at + 192, (img >> 12) & 15u);
-}
 // The record: lane 0 writes the head (two 16-byte stores), lane i entry i of every list: ordinary vector stores
 __device__ __forceinline__ void sq_store_state(uint32_t *rec, const SqHead &h, const SqLists &l, int lane) {
     if (lane == 0) {
@@ -411,54 +376,40 @@ __device__ __forceinline__ void sq_load_state(const uint32_t *rec, SqHead &h, Sq
     l.divers = lane < SQ_DIVERS ? rec[SQ_AT_DIVERS + lane] : 0u;
 }
 
-__global__ __launch_bounds__(SQ_THREADS) void env_seaquest_reset_kernel(SqArgs k) {
-    __shared__ uint32_t board[SQ_PER_WG][SQ_CELL_WORDS];
-    const int wave = (int)uni(threadIdx.x >> 6);
-    const int env = (int)uni(blockIdx.x * SQ_PER_WG + wave), lane = threadIdx.x & 63;
-    if (env >= k.n_envs) return;
+__global__ __launch_bounds__(ENV_THREADS) void env_seaquest_reset_kernel(EnvArgs k) {
+    __shared__ uint32_t board[ENV_PER_WG][SQ_CELL_WORDS];
+    int env, lane;
+    if (!env_of_wave(k, env, lane)) return;
+    uint32_t *cells = board[uni(threadIdx.x >> 6)];
     SqHead h;
     SqLists l;
     h.last_action = 0;
     h.t = 0;
     sq_reset(h, l);
-    sq_store_image(k.obs_next, k.obs_kind, env, lane, sq_image(board[wave], h, l, lane));
+    env_store_image<SQ_CHUNKS>(k.obs_next, k.obs_kind, env, lane, sq_image(cells, h, l, lane));
     sq_store_state(k.state + (size_t)env * PRISM_ENV_SEAQUEST_STATE_WORDS, h, l, lane);
 }
 
-__global__ __launch_bounds__(SQ_THREADS) void env_seaquest_step_kernel(SqArgs k) {
-    __shared__ uint32_t board[SQ_PER_WG][SQ_CELL_WORDS];
-    const int wave = (int)uni(threadIdx.x >> 6);
-    const int env = (int)uni(blockIdx.x * SQ_PER_WG + wave), lane = threadIdx.x & 63;
-    if (env >= k.n_envs) return;
+__global__ __launch_bounds__(ENV_THREADS) void env_seaquest_step_kernel(EnvArgs k) {
+    __shared__ uint32_t board[ENV_PER_WG][SQ_CELL_WORDS];
+    int env, lane;
+    if (!env_of_wave(k, env, lane)) return;
+    uint32_t *cells = board[uni(threadIdx.x >> 6)];
     uint32_t *rec = k.state + (size_t)env * PRISM_ENV_SEAQUEST_STATE_WORDS;
     SqHead h;
     SqLists l;
     sq_load_state(rec, h, l, lane);
     const uint64_t t0 = h.t;          // the counter of this step's draws
-    const int64_t raw = k.actions[env];
-    const uint32_t raw_lo = uni((uint32_t)raw), raw_hi = uni((uint32_t)((uint64_t)raw >> 32));
 
-    // the sticky coin
-    double u;
-    if (k.u_in) {
-        const uint64_t ub = __builtin_bit_cast(uint64_t, k.u_in[env]);
-        u = __builtin_bit_cast(double, (uint64_t)uni((uint32_t)ub) | ((uint64_t)uni((uint32_t)(ub >> 32)) << 32));
-    } else {
-        uint32_t r[4];
-        Philox(k.seed)(t0, ((uint64_t)env << 32) | SQ_KEY_COIN, r);
-        u = u64_to_unit_double(uni(r[0]), uni(r[1]));
-    }
-
-    // the action: out of range acts as no-op and raises the sticky status bit; the minimal set is the same six actions
-    const bool valid = raw_hi == 0u && raw_lo < (uint32_t)k.n_actions;
-    int a = valid ? (int)raw_lo : 0;
-    if (!valid && lane == 0) atomicOr(k.status, (uint32_t)PRISM_ENV_STATUS_BAD_ACTION);
-    if (u < k.sticky_p) a = h.last_action;
-    h.last_action = a;
+    // (the action's load is in flight while the coin is drawn)
+    int a = env_action(k.actions, env, k.n_actions, k.status, lane);
+    const double u = env_coin(k.u_in, k.seed, t0, env, SQ_KEY_COIN);
+    // the minimal set is the same six actions
+    a = env_sticky(a, u, k.sticky_p, h.last_action);
 
     float reward = 0.f;
     bool overflow = false;
-    const uint8_t *given = k.draws_in ? k.draws_in + (size_t)env * 5 : nullptr;
+    const uint8_t *given = k.draws_in ? static_cast<const uint8_t *>(k.draws_in) + (size_t)env * 5 : nullptr;
     // a given row outside 1..8 is taken into it (a guard: the host checks what it stages)
     auto enemy_draw = [&](uint32_t &side, uint32_t &is_sub, uint32_t &row) {
         if (given) {
@@ -483,46 +434,17 @@ __global__ __launch_bounds__(SQ_THREADS) void env_seaquest_step_kernel(SqArgs k)
     };
     const bool terminal = sq_step(h, l, a, lane, reward, overflow, enemy_draw, diver_draw);
     if (overflow && lane == 0) atomicOr(k.status, (uint32_t)PRISM_ENV_STATUS_OVERFLOW);
-    // (12) counters and flags
-    h.ep_steps += 1u;
-    h.t += 1ull;
-    const bool truncated = k.step_limit > 0 && h.ep_steps >= (uint32_t)k.step_limit && !terminal;
+    const bool truncated = env_count_step(h.ep_steps, h.t, k.step_limit, terminal);          // (12) counters and flags
 
-    uint32_t img = sq_image(board[wave], h, l, lane);
-    sq_store_image(k.next_obs, k.obs_kind, env, lane, img);          // what the step returned, before any reset
-    if (terminal || truncated) {                                     // (wave-uniform) only then is the acting image another one
+    uint32_t img = sq_image(cells, h, l, lane);
+    env_store_image<SQ_CHUNKS>(k.next_obs, k.obs_kind, env, lane, img);          // what the step returned, before any reset
+    if (terminal || truncated) {                                                 // (wave-uniform) only then is the acting image another one
         sq_reset(h, l);
-        img = sq_image(board[wave], h, l, lane);
+        img = sq_image(cells, h, l, lane);
     }
-    sq_store_image(k.obs_next, k.obs_kind, env, lane, img);          // what to act on next
+    env_store_image<SQ_CHUNKS>(k.obs_next, k.obs_kind, env, lane, img);          // what to act on next
     sq_store_state(rec, h, l, lane);
-    if (lane == 0) {
-        k.reward[env] = reward;
-        k.done[env] = terminal ? 1 : 0;
-        k.truncated[env] = truncated ? 1 : 0;
-    }
-}
-
-// the checks and texts of env_breakout.hip's check_env but for the action count: one descriptor, one contract
-static int check_env(const prism_env_desc *d) {
-    PRISM_CHECK_ARG(d, "null descriptor");
-    PRISM_CHECK_ARG(d->n_envs >= 1 && d->n_envs <= PRISM_ENV_MAX, "n_envs must be in [1, 65536]");
-    PRISM_CHECK_ARG(d->n_actions == 6, "n_actions must be 6");
-    PRISM_CHECK_ARG(d->step_limit >= 0, "step_limit is negative");
-    // (written so that a NaN fails it)
-    PRISM_CHECK_ARG(d->sticky_p >= 0.0 && d->sticky_p <= 1.0, "sticky_p outside [0, 1]");
-    PRISM_CHECK_ARG(d->obs_kind == PRISM_OBS_F32 || d->obs_kind == PRISM_OBS_U8, "obs_kind must be PRISM_OBS_F32 or PRISM_OBS_U8");
-    PRISM_CHECK_ARG(d->state && d->status, "null state block / status word");
-    PRISM_CHECK_ARG(d->obs[0] && d->obs[1] && d->obs[0] != d->obs[1], "null or shared ping-pong observation buffers");
-    PRISM_CHECK_ARG(d->next_obs && d->reward && d->done && d->truncated, "null step outputs");
-    PRISM_CHECK_ARG(((uintptr_t)d->state | (uintptr_t)d->obs[0] | (uintptr_t)d->obs[1] | (uintptr_t)d->next_obs) % 16 == 0,
-                    "state block and observation buffers must be 16-byte aligned");
-    return PRISM_OK;
-}
-
-static SqArgs sq_args(const prism_env_desc *d, int parity) {
-    return SqArgs{d->n_envs, d->n_actions, d->step_limit, d->obs_kind, d->sticky_p, d->seed, d->state, d->status,
-                  d->obs[parity], d->next_obs, d->reward, d->done, d->truncated, nullptr, nullptr, nullptr};
+    env_store_outcome(k, env, lane, reward, terminal, truncated);
 }
 
 }  // namespace prism
@@ -530,25 +452,16 @@ static SqArgs sq_args(const prism_env_desc *d, int parity) {
 using namespace prism;
 
 extern "C" int prism_env_seaquest_reset(const prism_env_desc *d, prism_stream_t stream_) {
-    const int rc = check_env(d);
+    const int rc = check_env(d, 6, "n_actions must be 6");
     if (rc != PRISM_OK) return rc;
-    SqArgs k = sq_args(d, 0);
-    hipLaunchKernelGGL(env_seaquest_reset_kernel, dim3((d->n_envs + SQ_PER_WG - 1) / SQ_PER_WG), dim3(SQ_THREADS), 0,
-                       (hipStream_t)stream_, k);
-    PRISM_CHECK_LAUNCH();
-    return PRISM_OK;
+    return env_launch(env_seaquest_reset_kernel, env_args(d, 0), stream_);
 }
 
 extern "C" int prism_env_seaquest_step(const prism_env_desc *d, const int64_t *actions, const double *u_in, const uint8_t *draws_in,
                                        int32_t parity, prism_stream_t stream_) {
-    const int rc = check_env(d);
+    const int rc = check_env(d, 6, "n_actions must be 6");
     if (rc != PRISM_OK) return rc;
     PRISM_CHECK_ARG(actions, "actions is null");
     PRISM_CHECK_ARG(parity == 0 || parity == 1, "parity must be 0 or 1");
-    SqArgs k = sq_args(d, parity ^ 1);
-    k.actions = actions, k.u_in = u_in, k.draws_in = draws_in;
-    hipLaunchKernelGGL(env_seaquest_step_kernel, dim3((d->n_envs + SQ_PER_WG - 1) / SQ_PER_WG), dim3(SQ_THREADS), 0,
-                       (hipStream_t)stream_, k);
-    PRISM_CHECK_LAUNCH();
-    return PRISM_OK;
+    return env_launch(env_seaquest_step_kernel, env_args(d, parity ^ 1, actions, u_in, draws_in), stream_);
 }

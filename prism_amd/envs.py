@@ -1,9 +1,8 @@
-"""The MinAtar games on the device: ``DeviceBreakout``, ``DeviceFreeway``, ``DeviceAsterix``, ``DeviceSpaceInvaders`` and
-``DeviceSeaquest`` -- N lock-stepped environments, stepped by one launch of ``prism_env_breakout_step`` /
-``prism_env_freeway_step`` / ``prism_env_asterix_step`` / ``prism_env_invaders_step`` / ``prism_env_seaquest_step``
-(include/prism_hip.h; the rules are DESIGN.md 7.3 to 7.7:
-restatements of MinAtar v1 that are NOT checked against the ``minatar`` package).  Each is the ``VectorCollector`` protocol (prism_amd/collectors.py), so acting, the environment step, the replay ingestion and the learner step sit on one
-stream and no host code reads an observation, a reward or an episode end.
+"""The five MinAtar games on the device (``Device<Game>``): N lock-stepped environments, stepped by one launch of the game's
+``prism_env_<game>_step`` (include/prism_hip.h; the rules are DESIGN.md 7.3 to 7.7: restatements of MinAtar v1 that are NOT
+checked against the ``minatar`` package).  Each is the ``VectorCollector`` protocol (prism_amd/collectors.py), so acting, the
+environment step, the replay ingestion and the learner step sit on one stream and no host code reads an observation, a
+reward or an episode end.
 
 What ``step`` returns are views of persistent device buffers; nothing synchronises.
 
@@ -17,6 +16,9 @@ points, its minimal action count, its state codec and the draws its parity path 
 ``pack_state``, ``unpack_state`` and ``render`` are Breakout's; Freeway's, Asterix's and Space Invaders' carry their names.
 Space Invaders draws nothing but the sticky coin, so its step passes no draw pointer (``_STEP_DRAWS``).  Seaquest keeps five
 ordered entity lists in a wider record (``_STATE_WORDS``); an append to a full one is dropped and ``check_status`` raises.
+
+The state codecs share what every record shares: the counters in words 2, 4, 5 (``_counters`` / ``_read_counters``), small
+fields laid out as ``{word: {name: (shift, mask)}}`` (``_put_fields`` / ``_get_fields``) and their range check (``_in_range``).
 """
 import ctypes
 
@@ -30,19 +32,18 @@ OBS_SHAPE = (10, 10, 4)
 FREEWAY_OBS_SHAPE = (10, 10, 7)
 FREEWAY_CARS = 8
 _OBS_DTYPES = {"float32": (N.OBS_F32, torch.float32), "uint8": (N.OBS_U8, torch.uint8)}
-_FIELDS = ("pos", "ball_x", "ball_y", "ball_dir", "last_x", "last_y", "strike", "last_action")
-_SHIFTS = dict(pos=(0, 15), ball_x=(4, 15), ball_y=(8, 15), ball_dir=(12, 3), last_x=(16, 15), last_y=(20, 15), strike=(24, 1),
-               last_action=(25, 7))
+# Breakout: word 1 of the record (include/prism_hip.h); a layout is {word: {name: (shift, mask)}}, a range (lo, hi)
+_SHIFTS = {1: dict(pos=(0, 15), ball_x=(4, 15), ball_y=(8, 15), ball_dir=(12, 3), last_x=(16, 15), last_y=(20, 15), strike=(24, 1),
+                   last_action=(25, 7))}
+_RANGES = dict(pos=(0, 9), ball_x=(0, 9), ball_y=(0, 9), ball_dir=(0, 3), last_x=(0, 9), last_y=(0, 9), strike=(0, 1), last_action=(0, 5))
 _NP = {torch.uint8: np.uint8, torch.int8: np.int8, torch.float64: np.float64}
-_LIMITS = dict(pos=9, ball_x=9, ball_y=9, ball_dir=3, last_x=9, last_y=9, strike=1, last_action=5)
 # Freeway: word 6 of the record, and the per-car words (include/prism_hip.h)
-_FW_FIELDS = ("pos", "move_timer", "terminate_timer", "last_action")
-_FW_SHIFTS = dict(pos=(0, 15), move_timer=(4, 3), terminate_timer=(6, 4095), last_action=(18, 7))
-_FW_LIMITS = dict(pos=9, move_timer=3, terminate_timer=2500, last_action=5)
+_FW_SHIFTS = {6: dict(pos=(0, 15), move_timer=(4, 3), terminate_timer=(6, 4095), last_action=(18, 7))}
+_FW_RANGES = dict(pos=(0, 9), move_timer=(0, 3), terminate_timer=(0, 2500), last_action=(0, 5))
 # Asterix: word 3 of the record (ramp_timer + 1 is word 6), and the per-slot words (include/prism_hip.h)
 ASTERIX_SLOTS = 8
-_AX_SHIFTS = dict(px=(0, 15), py=(4, 15), spawn_speed=(8, 15), spawn_timer=(12, 15), move_speed=(16, 7), move_timer=(19, 7),
-                  last_action=(22, 7), ramp_index=(25, 31))
+_AX_SHIFTS = {3: dict(px=(0, 15), py=(4, 15), spawn_speed=(8, 15), spawn_timer=(12, 15), move_speed=(16, 7), move_timer=(19, 7),
+                      last_action=(22, 7), ramp_index=(25, 31))}
 _AX_RANGES = dict(px=(0, 9), py=(1, 8), spawn_speed=(1, 10), spawn_timer=(0, 10), move_speed=(1, 5), move_timer=(0, 5),
                   last_action=(0, 5), ramp_index=(0, 15))
 # Space Invaders: the block of 4 x 6 aliens, and the small fields of words 6 and 7 of the record (include/prism_hip.h)
@@ -55,14 +56,44 @@ _SI_RANGES = dict(pos=(0, 9), shot_timer=(0, 5), last_action=(0, 5), alien_move_
 
 
 def _counters(words, fields, n):
-    """Words [2], [4], [5] of either game's record: ``ep_steps`` and the 64-bit ``t``."""
+    """Words [2], [4], [5] of every game's record: ``ep_steps`` and the 64-bit ``t``."""
     words[:, 2] = np.asarray(fields["ep_steps"]).astype(np.uint32)
     t = np.array([int(x) for x in fields["t"]], dtype=np.uint64).reshape(n)
     words[:, 4], words[:, 5] = (t & np.uint64(0xFFFFFFFF)).astype(np.uint32), (t >> np.uint64(32)).astype(np.uint32)
 
 
+def _read_counters(w, out):
+    """The inverse of ``_counters``: ``ep_steps`` as int64 and ``t`` as uint64 join ``out``."""
+    out["ep_steps"] = w[:, 2].astype(np.int64)
+    out["t"] = w[:, 4].astype(np.uint64) | (w[:, 5].astype(np.uint64) << np.uint64(32))
+    return out
+
+
+def _in_range(owner, name, v, lo, hi):
+    if v.min() < lo or v.max() > hi:
+        raise ValueError(f"{owner}.set_state: {name} outside [{lo}, {hi}]")
+
+
+def _scalars(owner, fields, ranges, n):
+    """The per-environment fields named by ``ranges`` as int64 [n], each checked against its (lo, hi)."""
+    out = {name: np.asarray(fields[name]).astype(np.int64).reshape(n) for name in ranges}
+    for name, (lo, hi) in ranges.items():
+        _in_range(owner, name, out[name], lo, hi)
+    return out
+
+
+def _put_fields(words, layout, values):
+    for word, names in layout.items():
+        for name, (sh, _) in names.items():
+            words[:, word] |= (values[name] << sh).astype(np.uint32)
+
+
+def _get_fields(w, layout):
+    return {name: ((w[:, word] >> sh) & mask).astype(np.int32) for word, names in layout.items() for name, (sh, mask) in names.items()}
+
+
 def pack_state(fields):
-    """The device's state block, int32 [N, 8], from a dict of host arrays: the small fields of ``_FIELDS`` [N], ``bricks``
+    """The device's state block, int32 [N, 8], from a dict of host arrays: the small fields of ``_RANGES`` [N], ``bricks``
     [N, 10, 10] (rows 1..3 only), ``ep_steps`` [N], ``t`` [N] (Python ints / uint64)."""
     n = len(fields["pos"])
     words = np.zeros((n, N.ENV_STATE_WORDS), np.uint32)
@@ -71,11 +102,7 @@ def pack_state(fields):
         raise ValueError("DeviceBreakout.set_state: bricks outside rows 1..3")
     bits = bricks[:, 1:4].reshape(n, 30).astype(np.uint64)
     words[:, 0] = (bits << np.arange(30, dtype=np.uint64)).sum(axis=1).astype(np.uint32)
-    for name in _FIELDS:
-        v = np.asarray(fields[name]).astype(np.int64).reshape(n)
-        if v.min() < 0 or v.max() > _LIMITS[name]:
-            raise ValueError(f"DeviceBreakout.set_state: {name} outside [0, {_LIMITS[name]}]")
-        words[:, 1] |= (v << _SHIFTS[name][0]).astype(np.uint32)
+    _put_fields(words, _SHIFTS, _scalars("DeviceBreakout", fields, _RANGES, n))
     _counters(words, fields, n)
     return words.view(np.int32)
 
@@ -84,13 +111,11 @@ def unpack_state(words):
     """The inverse of ``pack_state``: a dict of host arrays (``t`` as uint64)."""
     w = np.ascontiguousarray(words).view(np.uint32).reshape(-1, N.ENV_STATE_WORDS)
     n = w.shape[0]
-    out = {name: ((w[:, 1] >> sh) & mask).astype(np.int32) for name, (sh, mask) in _SHIFTS.items()}
+    out = _get_fields(w, _SHIFTS)
     bricks = np.zeros((n, 10, 10), np.uint8)
     bricks[:, 1:4] = ((w[:, 0:1] >> np.arange(30, dtype=np.uint32)) & 1).astype(np.uint8).reshape(n, 3, 10)
     out["bricks"] = bricks
-    out["ep_steps"] = w[:, 2].astype(np.int64)
-    out["t"] = w[:, 4].astype(np.uint64) | (w[:, 5].astype(np.uint64) << np.uint64(32))
-    return out
+    return _read_counters(w, out)
 
 
 def render(fields):
@@ -114,17 +139,12 @@ def pack_freeway_state(fields):
     words = np.zeros((n, N.ENV_STATE_WORDS), np.uint32)
     x, timer, speed = (np.asarray(fields[k]).astype(np.int64).reshape(n, FREEWAY_CARS) for k in ("car_x", "car_timer", "car_speed"))
     for name, v, lo, hi in (("car_x", x, 0, 9), ("car_timer", timer, 0, 5), ("|car_speed|", np.abs(speed), 1, 5)):
-        if v.min() < lo or v.max() > hi:
-            raise ValueError(f"DeviceFreeway.set_state: {name} outside [{lo}, {hi}]")
+        _in_range("DeviceFreeway", name, v, lo, hi)
     car = np.arange(FREEWAY_CARS, dtype=np.int64)
     words[:, 0] = (x << (4 * car)).sum(axis=1).astype(np.uint32)
     words[:, 1] = ((timer << (3 * car)).sum(axis=1) | ((speed > 0).astype(np.int64) << (24 + car)).sum(axis=1)).astype(np.uint32)
     words[:, 3] = (np.abs(speed) << (3 * car)).sum(axis=1).astype(np.uint32)
-    for name in _FW_FIELDS:
-        v = np.asarray(fields[name]).astype(np.int64).reshape(n)
-        if v.min() < 0 or v.max() > _FW_LIMITS[name]:
-            raise ValueError(f"DeviceFreeway.set_state: {name} outside [0, {_FW_LIMITS[name]}]")
-        words[:, 6] |= (v << _FW_SHIFTS[name][0]).astype(np.uint32)
+    _put_fields(words, _FW_SHIFTS, _scalars("DeviceFreeway", fields, _FW_RANGES, n))
     _counters(words, fields, n)
     return words.view(np.int32)
 
@@ -132,15 +152,13 @@ def pack_freeway_state(fields):
 def unpack_freeway_state(words):
     """The inverse of ``pack_freeway_state`` (``t`` as uint64)."""
     w = np.ascontiguousarray(words).view(np.uint32).reshape(-1, N.ENV_STATE_WORDS)
-    out = {name: ((w[:, 6] >> sh) & mask).astype(np.int32) for name, (sh, mask) in _FW_SHIFTS.items()}
+    out = _get_fields(w, _FW_SHIFTS)
     car = np.arange(FREEWAY_CARS, dtype=np.uint32)
     out["car_x"] = ((w[:, 0:1] >> (4 * car)) & 15).astype(np.int32)
     out["car_timer"] = ((w[:, 1:2] >> (3 * car)) & 7).astype(np.int32)
     mag = ((w[:, 3:4] >> (3 * car)) & 7).astype(np.int32)
     out["car_speed"] = np.where((w[:, 1:2] >> (24 + car)) & 1, mag, -mag).astype(np.int32)
-    out["ep_steps"] = w[:, 2].astype(np.int64)
-    out["t"] = w[:, 4].astype(np.uint64) | (w[:, 5].astype(np.uint64) << np.uint64(32))
-    return out
+    return _read_counters(w, out)
 
 
 def render_freeway(fields):
@@ -167,8 +185,7 @@ def pack_asterix_state(fields):
     active, x, direction, gold = (np.asarray(fields[k]).astype(np.int64).reshape(n, ASTERIX_SLOTS)
                                   for k in ("ent_active", "ent_x", "ent_dir", "ent_gold"))
     for name, v, lo, hi in (("ent_active", active, 0, 1), ("ent_x", x, 0, 9), ("ent_gold", gold, 0, 1)):
-        if v.min() < lo or v.max() > hi:
-            raise ValueError(f"DeviceAsterix.set_state: {name} outside [{lo}, {hi}]")
+        _in_range("DeviceAsterix", name, v, lo, hi)
     if (np.abs(direction) != active).any():
         raise ValueError("DeviceAsterix.set_state: ent_dir must be +1 or -1 in a slot that holds an entity, 0 in an empty one")
     if (x[active == 0] != 0).any() or (gold[active == 0] != 0).any():
@@ -176,15 +193,8 @@ def pack_asterix_state(fields):
     slot = np.arange(ASTERIX_SLOTS, dtype=np.int64)
     words[:, 0] = (x << (4 * slot)).sum(axis=1).astype(np.uint32)
     words[:, 1] = ((active << slot) | ((direction > 0).astype(np.int64) << (8 + slot)) | (gold << (16 + slot))).sum(axis=1).astype(np.uint32)
-    for name, (lo, hi) in _AX_RANGES.items():
-        v = np.asarray(fields[name]).astype(np.int64).reshape(n)
-        if v.min() < lo or v.max() > hi:
-            raise ValueError(f"DeviceAsterix.set_state: {name} outside [{lo}, {hi}]")
-        words[:, 3] |= (v << _AX_SHIFTS[name][0]).astype(np.uint32)
-    ramp = np.asarray(fields["ramp_timer"]).astype(np.int64).reshape(n)
-    if ramp.min() < -1 or ramp.max() > 100:
-        raise ValueError("DeviceAsterix.set_state: ramp_timer outside [-1, 100]")
-    words[:, 6] = (ramp + 1).astype(np.uint32)
+    _put_fields(words, _AX_SHIFTS, _scalars("DeviceAsterix", fields, _AX_RANGES, n))
+    words[:, 6] = (_scalars("DeviceAsterix", fields, dict(ramp_timer=(-1, 100)), n)["ramp_timer"] + 1).astype(np.uint32)
     _counters(words, fields, n)
     return words.view(np.int32)
 
@@ -192,16 +202,14 @@ def pack_asterix_state(fields):
 def unpack_asterix_state(words):
     """The inverse of ``pack_asterix_state`` (``t`` as uint64)."""
     w = np.ascontiguousarray(words).view(np.uint32).reshape(-1, N.ENV_STATE_WORDS)
-    out = {name: ((w[:, 3] >> sh) & mask).astype(np.int32) for name, (sh, mask) in _AX_SHIFTS.items()}
+    out = _get_fields(w, _AX_SHIFTS)
     out["ramp_timer"] = (w[:, 6] & 127).astype(np.int32) - 1
     slot = np.arange(ASTERIX_SLOTS, dtype=np.uint32)
     out["ent_active"] = ((w[:, 1:2] >> slot) & 1).astype(np.int32)
     out["ent_x"] = ((w[:, 0:1] >> (4 * slot)) & 15).astype(np.int32)
     out["ent_dir"] = np.where((w[:, 1:2] >> (8 + slot)) & 1, 1, -1).astype(np.int32) * out["ent_active"]
     out["ent_gold"] = ((w[:, 1:2] >> (16 + slot)) & 1).astype(np.int32)
-    out["ep_steps"] = w[:, 2].astype(np.int64)
-    out["t"] = w[:, 4].astype(np.uint64) | (w[:, 5].astype(np.uint64) << np.uint64(32))
-    return out
+    return _read_counters(w, out)
 
 
 def render_asterix(fields):
@@ -237,23 +245,18 @@ def pack_invaders_state(fields):
     none."""
     n, block, f, e = _invaders_fields(fields)
     words = np.zeros((n, N.ENV_STATE_WORDS), np.uint32)
-    scalars = {name: np.asarray(fields[name]).astype(np.int64).reshape(n) for name in _SI_RANGES}
-    for name, (lo, hi) in _SI_RANGES.items():
-        if scalars[name].min() < lo or scalars[name].max() > hi:
-            raise ValueError(f"DeviceSpaceInvaders.set_state: {name} outside [{lo}, {hi}]")
+    scalars = _scalars("DeviceSpaceInvaders", fields, _SI_RANGES, n)
     direction = np.asarray(fields["alien_dir"]).astype(np.int64).reshape(n)
     if (np.abs(direction) != 1).any():
         raise ValueError("DeviceSpaceInvaders.set_state: alien_dir must be +1 or -1")
-    if block.min() < 0 or block.max() > 1:
-        raise ValueError("DeviceSpaceInvaders.set_state: alien_block outside [0, 1]")
+    _in_range("DeviceSpaceInvaders", "alien_block", block, 0, 1)
     if not block.any(axis=(1, 2)).all():
         raise ValueError("DeviceSpaceInvaders.set_state: alien_block is empty (a cleared board is refilled on its step)")
     column = scalars["alien_x"][:, None] + np.arange(INVADERS_BLOCK[1])
     if (block.any(axis=1) & ((column < 0) | (column > 9))).any():
         raise ValueError("DeviceSpaceInvaders.set_state: alien_x puts a live alien of alien_block off the board")
     for name, v in (("f_bullet_x", f), ("e_bullet_x", e)):
-        if v.min() < -1 or v.max() > 9:
-            raise ValueError(f"DeviceSpaceInvaders.set_state: {name} outside [-1, 9]")
+        _in_range("DeviceSpaceInvaders", name, v, -1, 9)
     bit = np.arange(INVADERS_BLOCK[0] * INVADERS_BLOCK[1], dtype=np.int64)
     words[:, 0] = ((block.reshape(n, -1) << bit).sum(axis=1) | ((scalars["alien_x"] + 5) << 24) | (scalars["alien_y"] << 28)).astype(np.uint32)
     row = 4 * np.arange(8, dtype=np.int64)
@@ -261,9 +264,7 @@ def pack_invaders_state(fields):
     words[:, 3] = ((e[:, :8] + 1) << row).sum(axis=1).astype(np.uint32)
     words[:, 6] = ((f[:, 8] + 1) | ((f[:, 9] + 1) << 4) | ((e[:, 8] + 1) << 8) | ((e[:, 9] + 1) << 12) |
                    ((direction > 0).astype(np.int64) << 23)).astype(np.uint32)
-    for word, names in _SI_SHIFTS.items():
-        for name, (sh, _) in names.items():
-            words[:, word] |= (scalars[name] << sh).astype(np.uint32)
+    _put_fields(words, _SI_SHIFTS, scalars)
     _counters(words, fields, n)
     return words.view(np.int32)
 
@@ -272,7 +273,7 @@ def unpack_invaders_state(words):
     """The inverse of ``pack_invaders_state`` (``t`` as uint64)."""
     w = np.ascontiguousarray(words).view(np.uint32).reshape(-1, N.ENV_STATE_WORDS)
     n = w.shape[0]
-    out = {name: ((w[:, word] >> sh) & mask).astype(np.int32) for word, names in _SI_SHIFTS.items() for name, (sh, mask) in names.items()}
+    out = _get_fields(w, _SI_SHIFTS)
     bit = np.arange(INVADERS_BLOCK[0] * INVADERS_BLOCK[1], dtype=np.uint32)
     out["alien_block"] = ((w[:, 0:1] >> bit) & 1).astype(np.int32).reshape((n,) + INVADERS_BLOCK)
     out["alien_x"] = ((w[:, 0] >> 24) & 15).astype(np.int32) - 5
@@ -282,9 +283,7 @@ def unpack_invaders_state(words):
     for name, low, sh in (("f_bullet_x", 1, 0), ("e_bullet_x", 3, 8)):
         fields = np.concatenate([(w[:, low:low + 1] >> row) & 15, (w[:, 6:7] >> np.array([sh, sh + 4], np.uint32)) & 15], axis=1)
         out[name] = fields.astype(np.int32) - 1
-    out["ep_steps"] = w[:, 2].astype(np.int64)
-    out["t"] = w[:, 4].astype(np.uint64) | (w[:, 5].astype(np.uint64) << np.uint64(32))
-    return out
+    return _read_counters(w, out)
 
 
 def render_invaders(fields):
@@ -332,16 +331,11 @@ def pack_seaquest_state(fields):
     longer than its capacity, a field out of range, a sub whose rear cell is off the board, an enemy row outside 1..8."""
     n = len(fields["sub_x"])
     words = np.zeros((n, N.ENV_SEAQUEST_STATE_WORDS), np.uint32)
-    scalars = {name: np.asarray(fields[name]).astype(np.int64).reshape(n) for name in _SQ_RANGES}
-    for name, (lo, hi) in _SQ_RANGES.items():
-        if scalars[name].min() < lo or scalars[name].max() > hi:
-            raise ValueError(f"DeviceSeaquest.set_state: {name} outside [{lo}, {hi}]")
+    scalars = _scalars("DeviceSeaquest", fields, _SQ_RANGES, n)
     rear = np.where(scalars["sub_or"] != 0, scalars["sub_x"] - 1, scalars["sub_x"] + 1)
     if (rear < 0).any() or (rear > 9).any():
         raise ValueError("DeviceSeaquest.set_state: the cell behind the sub (sub_x - 1 facing +x, sub_x + 1 facing -x) is off the board")
-    for word, names in _SQ_SHIFTS.items():
-        for name, (sh, _) in names.items():
-            words[:, word] |= (scalars[name] << sh).astype(np.uint32)
+    _put_fields(words, _SQ_SHIFTS, scalars)
     words[:, 1] |= (scalars["oxygen"] + 1).astype(np.uint32)
     for name, (first, capacity, (y_lo, y_hi), width) in SEAQUEST_LISTS.items():
         per_env = fields[name]
@@ -370,7 +364,7 @@ def pack_seaquest_state(fields):
 def unpack_seaquest_state(words):
     """The inverse of ``pack_seaquest_state`` (``t`` as uint64; the lists as Python lists of tuples, one per environment)."""
     w = np.ascontiguousarray(words).view(np.uint32).reshape(-1, N.ENV_SEAQUEST_STATE_WORDS)
-    out = {name: ((w[:, word] >> sh) & mask).astype(np.int32) for word, names in _SQ_SHIFTS.items() for name, (sh, mask) in names.items()}
+    out = _get_fields(w, _SQ_SHIFTS)
     out["oxygen"] = (w[:, 1] & 255).astype(np.int32) - 1
     for name, (first, capacity, _, width) in SEAQUEST_LISTS.items():
         out[name] = []
@@ -380,9 +374,7 @@ def unpack_seaquest_state(words):
                 if e & _SQ_PRESENT:
                     entries.append((e & 15, (e >> 4) & 15, 1 if (e >> 8) & 1 else -1, (e >> 9) & 7, (e >> 12) & 15)[:width])
             out[name].append(entries)
-    out["ep_steps"] = w[:, 2].astype(np.int64)
-    out["t"] = w[:, 4].astype(np.uint64) | (w[:, 5].astype(np.uint64) << np.uint64(32))
-    return out
+    return _read_counters(w, out)
 
 
 def render_seaquest(fields):

@@ -1,0 +1,64 @@
+"""GPU: what the five device games take from their shared frame (csrc/env_frame.h) -- the wave-to-environment map and its
+exit, the Philox coin, the action check and its status bit, the sticky select, the chunk stores in both observation kinds, the
+counters, the truncation rule and the reset branch of the step's tail -- through every game at once, against the game's host
+restatement, exactly.  The games' own files hold the rules to their case tables; this one holds the frame to all five."""
+import copy
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from tests import env_frame_cases as FC
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    return "cuda:0"
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(game, n):
+    """The host restatement's run, computed once per (game, n) and shared by both observation kinds: the first observation,
+    then per step (next_obs, reward, done, truncated), the acting observation and the state."""
+    host, _ = FC.host(game, n)
+    first = host.reset().copy()
+    steps = []
+    for acts in FC.actions(game, n):
+        out = tuple(np.array(x) for x in host.step(acts))
+        steps.append((out, host.observe().copy(), copy.deepcopy(host.get_state())))
+    assert host.bad_action and sum(int(s[0][3].sum()) for s in steps) >= 1          # (tests/test_env_frame_host.py holds the run to more)
+    return first, steps
+
+
+@pytest.mark.parametrize("obs_dtype", ["float32", "uint8"])
+@pytest.mark.parametrize("n", FC.SIZES)
+@pytest.mark.parametrize("game", sorted(FC.GAMES))
+def test_every_game_on_the_frame_equals_its_host_restatement(dev, game, n, obs_dtype):
+    from prism_amd import _native as N
+    from prism_amd import envs
+    first, steps = _reference(game, n)
+    _, assert_same_state = FC.host(game, n)
+    env = getattr(envs, FC.GAMES[game][0])(n, FC.SEED, dev, obs_dtype=obs_dtype, **FC.KW)
+    assert env.n_actions == 6 and tuple(env.obs_shape) == FC.GAMES[game][3]
+    got = env.reset()
+    assert got.dtype == getattr(torch, obs_dtype)
+    np.testing.assert_array_equal(got.cpu().numpy().astype(np.float32), first, err_msg="reset")
+    for k, acts in enumerate(FC.actions(game, n)):
+        where = f"{game}, N = {n}, {obs_dtype}, step {k}"
+        next_obs, reward, done, trunc = env.step(torch.from_numpy(acts).to(dev))
+        (want_obs, want_reward, want_done, want_trunc), want_acting, want_state = steps[k]
+        np.testing.assert_array_equal(next_obs.cpu().numpy().astype(np.float32), want_obs, err_msg=f"{where}: next_obs")
+        np.testing.assert_array_equal(reward.cpu().numpy().view(np.uint32), want_reward.astype(np.float32).view(np.uint32), err_msg=f"{where}: reward")
+        np.testing.assert_array_equal(done.cpu().numpy(), want_done, err_msg=f"{where}: done")
+        np.testing.assert_array_equal(trunc.cpu().numpy(), want_trunc, err_msg=f"{where}: truncated")
+        np.testing.assert_array_equal(env.observe().cpu().numpy().astype(np.float32), want_acting, err_msg=f"{where}: acting observation")
+        assert_same_state(env.get_state(), want_state, where)
+    with pytest.raises(N.PrismError, match="outside"):
+        env.check_status()
+    env.check_status()          # raised once: the check cleared the status word
+    env.close()
