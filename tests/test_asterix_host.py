@@ -2,7 +2,6 @@
 invariants hold over seeded play, the draws sit where DESIGN.md 7.5 puts them -- and the host side of the device
 environment: the two entry points through the C ABI, their kernels' private segment, the state codec, the factory knob, the
 snapshot kinds.  Neither the restatement nor the kernel is checked against the ``minatar`` package."""
-import ctypes
 import os
 import re
 
@@ -10,20 +9,12 @@ import numpy as np
 import pytest
 
 from tests import asterix_cases as AC
+from tests import game_suite as GS
 from tests import helpers as H
-from tests.asterix_ref import (BRANCHES, KEY_COIN, KEY_SPAWN, HostAsterix, assert_same_state, coin, draw, draw_spawn, spawn_of_words,
-                               unit_double)
-from tests.test_env_host import ENV_REFUSALS, _edit, _fake_desc
+from tests.asterix_ref import BRANCHES, KEY_COIN, KEY_SPAWN, HostAsterix, assert_same_state, draw, draw_spawn, spawn_of_words
+from tests.env_frame_cases import GAMES
 
-# the Philox-path run of tests/test_gpu_asterix.py (kept here: this file needs no GPU)
-SEED = 0x5EEDFACE12345
-PHILOX_RUN = dict(n=5, steps=300, kw=dict(sticky_action_prob=0.25, episode_timestep_limit=60))
-
-
-def philox_actions():
-    """The run's actions: ``np.random.RandomState(7).randint(0, 5, size=5)`` per step."""
-    rng = np.random.RandomState(7)
-    return [rng.randint(0, 5, size=PHILOX_RUN["n"]).astype(np.int64) for _ in range(PHILOX_RUN["steps"])]
+GAME = GAMES["asterix"]          # its seed and Philox-path run are tests/test_gpu_asterix.py's: kept where no GPU is needed
 
 
 def run_case(name):
@@ -275,35 +266,13 @@ def test_spawn_map_edges_and_frequencies():
 
 
 def test_sticky_coin_counts_and_zero_never_repeats():
-    seed, n, steps = 99, 8, 200
-    host = HostAsterix(n, seed=seed, sticky_action_prob=0.25)
-    host.reset()
-    for _ in range(steps):
-        host.step(np.zeros(n, np.int64))
-    coins = np.array([coin(seed, e, t) for e in range(n) for t in range(steps)])
-    assert 0.0 <= coins.min() and coins.max() < 1.0
-    r = draw(seed, 3, 17, KEY_COIN)
-    assert coin(seed, 3, 17) == unit_double(r[0], r[1])
-    assert host.branches["sticky_repeat"] == int((coins < 0.25).sum())          # t runs on through the episode ends
-    host = HostAsterix(n, seed=seed, sticky_action_prob=0.0)
-    host.reset()
-    rng = np.random.default_rng(0)
-    for _ in range(100):
-        acts = rng.integers(0, 6, n)
-        host.step(acts)
-        assert [e["last_action"] for e in host.envs] == list(acts)
-    assert host.branches["sticky_repeat"] == 0
+    GS.sticky_coin_check(GAME, steps=200, free_steps=100)
 
 
 def test_the_philox_run_of_the_gpu_test_shows_a_gold_a_terminal_a_truncation_and_an_exit():
     """tests/test_gpu_asterix.py's Philox-path run (n = 5, 300 steps, limit 60, sticky_p = 0.25, actions of RandomState(7)) on
     ``HostAsterix`` alone.  This restatement gives 9 golds, 15 terminals, 11 truncations and 11 exits."""
-    host = HostAsterix(PHILOX_RUN["n"], SEED, **PHILOX_RUN["kw"])
-    host.reset()
-    golds = terminals = truncations = 0
-    for acts in philox_actions():
-        _, reward, done, trunc = host.step(acts)
-        golds, terminals, truncations = golds + int(reward.sum()), terminals + int(done.sum()), truncations + int(trunc.sum())
+    host, (golds, terminals, truncations) = GS.philox_host_run(GAME)
     exits = host.branches["exit_left"] + host.branches["exit_right"]
     print(f"golds {golds}, terminals {terminals}, truncations {truncations}, exits {exits}")
     assert golds >= 1 and terminals >= 1 and truncations >= 1 and exits >= 1
@@ -313,82 +282,31 @@ def test_the_philox_run_of_the_gpu_test_shows_a_gold_a_terminal_a_truncation_and
 # ---------------------------------------------------------------------- the host side of the device environment
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    from prism_amd import _native as N
-    if not os.path.exists(N.LIB_PATH):
-        g.build()
-    return N.lib()
+    return GS.native_lib()
 
 
 def test_symbols_exported_declared_and_mirrored(lib):
-    from prism_amd import _native as N
-    src = open(N.HEADER_PATH).read()
-    raw = ctypes.CDLL(N.LIB_PATH)
-    for name in ("prism_env_asterix_reset", "prism_env_asterix_step"):
-        assert hasattr(raw, name) and re.search(r"\bint " + name + r"\(const prism_env_desc \*d,", src)
-        assert N.SIGNATURES[name][1][0] == ctypes.POINTER(N.EnvDesc)
-    assert N.SIGNATURES["prism_env_asterix_step"] == N.SIGNATURES["prism_env_breakout_step"]
-    assert len(N.SIGNATURES["prism_env_asterix_reset"][1]) == 2          # a reset draws nothing: no draw pointer
+    src, signatures = GS.symbols_check(lib, GAME)
+    assert signatures["prism_env_asterix_step"] == signatures["prism_env_breakout_step"]
+    assert len(signatures["prism_env_asterix_reset"][1]) == 2          # a reset draws nothing: no draw pointer
     assert "int prism_env_asterix_reset(const prism_env_desc *d, prism_stream_t stream);" in src and "const uint8_t *spawn_in" in src
-    assert f"#define PRISM_ENV_STATE_WORDS {N.ENV_STATE_WORDS}" in src and N.ENV_STATE_WORDS == 8
-    makefile = open(os.path.join(H.ROOT, "prism_amd", "csrc", "Makefile")).read()
-    assert "env_asterix.hip" in re.search(r"^SRCS := (.*)$", makefile, re.M).group(1).split()
-
-
-# Breakout's table with this game's action counts: 5 or 6
-AX_REFUSALS = [(edit, text.replace(b"3 or 6", b"5 or 6")) for edit, text in ENV_REFUSALS] + [(_edit(n_actions=3), b"n_actions must be 5 or 6")]
-
-
-def _call(lib, entry, p, actions=0x40000000, parity=0):
-    if entry == "reset":
-        return lib.prism_env_asterix_reset(p, None)
-    return lib.prism_env_asterix_step(p, actions, None, None, parity, None)
 
 
 @pytest.mark.parametrize("entry", ["reset", "step"])
-@pytest.mark.parametrize("case", range(len(AX_REFUSALS)))
+@pytest.mark.parametrize("case", range(len(GS.refusals(GAME))))
 def test_env_refusals_without_device(lib, entry, case):
-    """Every refusal of Breakout's table, with the same text but for the action counts, through Asterix's entry points."""
-    edit, text = AX_REFUSALS[case]
-    d = _fake_desc()
-    if edit is not None:
-        edit(d)
-    rc = _call(lib, entry, None if edit is None else ctypes.byref(d))
-    assert rc == -1, (rc, lib.prism_last_error())
-    assert b"check_env: " in lib.prism_last_error() and text in lib.prism_last_error(), lib.prism_last_error()
+    """Every refusal of Breakout's table, with the same text but for the action counts (5 or 6), through Asterix's entry points."""
+    GS.refusal_check(lib, GAME, entry, case)
 
 
 def test_step_refuses_null_actions_and_bad_parity(lib):
-    d = _fake_desc()
-    assert _call(lib, "step", ctypes.byref(d), actions=None) == -1
-    assert b"prism_env_asterix_step: actions is null" in lib.prism_last_error()
-    for parity in (2, -1):
-        assert _call(lib, "step", ctypes.byref(d), parity=parity) == -1
-        assert b"parity must be 0 or 1" in lib.prism_last_error()
-    d.n_actions = 5          # the minimal set is accepted as far as the next check
-    assert _call(lib, "step", ctypes.byref(d), actions=None) == -1 and b"actions is null" in lib.prism_last_error()
+    GS.null_actions_and_parity_check(lib, GAME)
 
 
 def test_the_kernels_have_no_private_and_no_group_segment(tmp_path):
     """Read from the code object's metadata of env_asterix.hip (the slots are looked up by constant shifts: an array indexed
     by the chosen slot would land in the private segment)."""
-    import shutil
-    import subprocess
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(H.ROOT, "prism_amd", "csrc")
-    out = tmp_path / "env_asterix.s"
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-                    "-I" + os.path.join(H.ROOT, "include"), "-I" + csrc, "-S", "--cuda-device-only", "-o", str(out),
-                    os.path.join(csrc, "env_asterix.hip")], check=True, timeout=600, stdout=subprocess.DEVNULL,
-                   stderr=subprocess.DEVNULL)
-    kernels = dict(re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", out.read_text(), re.S))
-    names = [k for k in kernels if "env_asterix_" in k]
-    assert len(names) == 2 and sum("env_asterix_reset_kernel" in k for k in names) == sum("env_asterix_step_kernel" in k for k in names) == 1
-    for name in names:
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", kernels[name]).group(1)) == 0, name
-        assert int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", kernels[name]).group(1)) == 0, name
+    assert set(GS.kernel_segments(GAME, tmp_path).values()) == {(0, 0)}
 
 
 def test_state_codec_round_trips_and_refuses():
@@ -454,18 +372,7 @@ def test_factory_knob_off_on_and_bad(monkeypatch):
     from prism_amd.collectors import VectorCollector
     from prism_amd.config import baseline_config
     from prism_amd.factory import collector_factory, env_factory
-    made = []
-
-    def fake(kind):
-        class Fake:
-            obs_shape, n_actions = (10, 10, 4), 5
-
-            def __init__(self, *a, **kw):
-                made.append((kind, a, kw))
-        return Fake
-
-    for kind in ("Asterix", "Freeway", "Breakout"):
-        monkeypatch.setattr(envs, "Device" + kind, fake(kind))
+    made = GS.fake_device_classes(monkeypatch, GAME, ("Asterix", "Freeway", "Breakout"))
     assert env_factory.DEVICE_GAMES["Asterix"] == "DeviceAsterix" and env_factory.DEFAULT_DEVICE_GAMES == ("Breakout",)
     cfg = baseline_config(2, device="cuda:0", env_name="MinAtar/Asterix-v1", atari_sticky_actions_prob=0.1, num_processes=9,
                           seed=31, episode_timestep_limit=777)
@@ -528,15 +435,8 @@ def test_the_real_class_counts_five_minimal_actions_before_it_needs_a_device():
 
 
 def test_snapshot_kind_mismatch_is_refused():
-    import torch
-    from prism_amd.envs import DeviceAsterix, DeviceBreakout, DeviceFreeway
-    snap = lambda kind, a=6: dict(kind=kind, n_envs=4, n_actions=a, seed=9, started=False, state=torch.zeros((4, 8), dtype=torch.int32))
-
-    def bare(cls, n_actions=6):
-        env = cls.__new__(cls)
-        env.__dict__.update(dict(_name=cls.__name__, n_envs=4, n_actions=n_actions, seed=9, _started=False))
-        return env
-
+    from prism_amd.envs import DeviceAsterix, DeviceFreeway
+    bare, snap = GS.bare, GS.snap
     with pytest.raises(ValueError, match="kind = 'DeviceBreakout' in the snapshot, 'DeviceAsterix' here"):
         bare(DeviceAsterix).load_state_dict(snap("DeviceBreakout"))
     with pytest.raises(ValueError, match="kind = 'DeviceFreeway' in the snapshot, 'DeviceAsterix' here"):

@@ -9,8 +9,12 @@ import numpy as np
 import pytest
 
 from tests import env_cases as EC
+from tests import game_suite as GS
 from tests import helpers as H
+from tests.env_frame_cases import GAMES
 from tests.env_ref import BRANCHES, ENV_KEY, FIRST_COUNTER, HostBreakout, draw, unit_double
+
+GAME = GAMES["breakout"]
 
 
 def run_case(name):
@@ -160,86 +164,18 @@ def test_sticky_coin_frequency_and_zero_never_repeats():
 # ---------------------------------------------------------------------- the host side of the device environment
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    from prism_amd import _native as N
-    if not os.path.exists(N.LIB_PATH):
-        g.build()
-    return N.lib()
-
-
-def _fake_desc():
-    """A descriptor every check accepts, over buffers that do not exist: each case breaks ONE condition, so the call is
-    refused before anything touches a device."""
-    from prism_amd import _native as N
-    d = N.EnvDesc()
-    d.n_envs, d.n_actions, d.step_limit, d.obs_kind, d.sticky_p, d.seed = 5, 6, 0, N.OBS_F32, 0.25, 7
-    addr = 0x10000000
-    for f in ("state", "status", "next_obs", "reward", "done", "truncated"):
-        setattr(d, f, addr)
-        addr += 0x100000
-    d.obs[0], d.obs[1] = addr, addr + 0x100000
-    return d
-
-
-def _edit(**kw):
-    def f(d):
-        for k, v in kw.items():
-            setattr(d, k, v)
-    return f
-
-
-def _obs(i, v):
-    def f(d):
-        d.obs[i] = v
-    return f
-
-
-ENV_REFUSALS = [
-    (None, b"null descriptor"),
-    (_edit(n_envs=0), b"n_envs must be in [1, 65536]"),
-    (_edit(n_envs=65537), b"n_envs must be in [1, 65536]"),
-    (_edit(n_actions=4), b"n_actions must be 3 or 6"),
-    (_edit(n_actions=0), b"n_actions must be 3 or 6"),
-    (_edit(step_limit=-1), b"step_limit is negative"),
-    (_edit(sticky_p=-0.01), b"sticky_p outside [0, 1]"),
-    (_edit(sticky_p=1.5), b"sticky_p outside [0, 1]"),
-    (_edit(sticky_p=float("nan")), b"sticky_p outside [0, 1]"),
-    (_edit(obs_kind=2), b"obs_kind must be"),
-    (_edit(state=None), b"null state block / status word"),
-    (_edit(status=None), b"null state block / status word"),
-    (_obs(0, None), b"null or shared ping-pong observation buffers"),
-    (_obs(1, None), b"null or shared ping-pong observation buffers"),
-    (lambda d: _obs(1, d.obs[0])(d), b"null or shared ping-pong observation buffers"),
-    (_edit(next_obs=None), b"null step outputs"),
-    (_edit(reward=None), b"null step outputs"),
-    (_edit(done=None), b"null step outputs"),
-    (_edit(truncated=None), b"null step outputs"),
-    (lambda d: setattr(d, "state", d.state + 4), b"16-byte aligned"),
-    (lambda d: _obs(1, d.obs[1] + 8)(d), b"16-byte aligned"),
-]
+    return GS.native_lib()
 
 
 @pytest.mark.parametrize("entry", ["reset", "step"])
-@pytest.mark.parametrize("case", range(len(ENV_REFUSALS)))
+@pytest.mark.parametrize("case", range(len(GS.refusals(GAME))))
 def test_env_refusals_without_device(lib, entry, case):
-    edit, text = ENV_REFUSALS[case]
-    d = _fake_desc()
-    if edit is not None:
-        edit(d)
-    p = None if edit is None else ctypes.byref(d)
-    rc = lib.prism_env_breakout_reset(p, None, None) if entry == "reset" else \
-        lib.prism_env_breakout_step(p, 0x40000000, None, None, 0, None)
-    assert rc == -1, (rc, lib.prism_last_error())
-    assert b"check_env: " in lib.prism_last_error() and text in lib.prism_last_error(), lib.prism_last_error()
+    """Every refusal of the table (tests/game_suite.py ENV_REFUSALS: the other games derive theirs from it)."""
+    GS.refusal_check(lib, GAME, entry, case)
 
 
 def test_step_refuses_null_actions_and_bad_parity(lib):
-    d = _fake_desc()
-    assert lib.prism_env_breakout_step(ctypes.byref(d), None, None, None, 0, None) == -1
-    assert b"prism_env_breakout_step: actions is null" in lib.prism_last_error()
-    for parity in (2, -1):
-        assert lib.prism_env_breakout_step(ctypes.byref(d), 0x40000000, None, None, parity, None) == -1
-        assert b"parity must be 0 or 1" in lib.prism_last_error()
+    GS.null_actions_and_parity_check(lib, GAME)
 
 
 def test_descriptor_mirror_layout():

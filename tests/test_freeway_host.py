@@ -2,7 +2,6 @@
 invariants hold over seeded play, the draws sit where DESIGN.md 7.4 puts them -- and the host side of the device
 environment: the two entry points through the C ABI, their kernels' private segment, the state codec, the factory knob, the
 snapshot kinds."""
-import ctypes
 import os
 import re
 
@@ -10,10 +9,12 @@ import numpy as np
 import pytest
 
 from tests import freeway_cases as FC
+from tests import game_suite as GS
 from tests import helpers as H
-from tests.freeway_ref import (BRANCHES, FIRST_COUNTER, KEY_COIN, KEYS_RESET, KEYS_WIN, HostFreeway, coin, draw, draw_speeds,
-                               speed_of_word, unit_double)
-from tests.test_env_host import ENV_REFUSALS, _fake_desc
+from tests.env_frame_cases import GAMES
+from tests.freeway_ref import BRANCHES, FIRST_COUNTER, KEY_COIN, KEYS_RESET, KEYS_WIN, HostFreeway, draw, draw_speeds, speed_of_word
+
+GAME = GAMES["freeway"]          # its seed and Philox-path run are tests/test_gpu_freeway.py's: kept where no GPU is needed
 
 
 def run_case(name):
@@ -229,107 +230,44 @@ def test_speed_map_frequencies_and_edges():
 
 
 def test_sticky_coin_counts_and_zero_never_repeats():
-    seed, n, steps = 99, 8, 300
-    coins = np.array([coin(seed, e, t) for e in range(n) for t in range(steps)])
-    assert 0.0 <= coins.min() and coins.max() < 1.0
-    r = draw(seed, 3, 17, KEY_COIN)
-    assert coin(seed, 3, 17) == unit_double(r[0], r[1])
-    host = HostFreeway(n, seed=seed, sticky_action_prob=0.25)
-    host.reset()
-    for _ in range(steps):
-        host.step(np.zeros(n, np.int64))
-    assert host.branches["sticky_repeat"] == int((coins < 0.25).sum())
-    host = HostFreeway(n, seed=seed, sticky_action_prob=0.0)
-    host.reset()
-    rng = np.random.default_rng(0)
-    for _ in range(100):
-        acts = rng.integers(0, 6, n)
-        host.step(acts)
-        assert [e["last_action"] for e in host.envs] == list(acts)
-    assert host.branches["sticky_repeat"] == 0
+    GS.sticky_coin_check(GAME, steps=300, free_steps=100)
 
 
 def test_the_philox_script_of_the_gpu_test_shows_a_win():
     """tests/test_gpu_freeway.py's Philox-path run (its seed, hold u, 200 steps at N = 5, sticky_p = 0.25) has a win on
     ``HostFreeway`` alone."""
-    from tests.test_gpu_freeway import PHILOX_RUN, SEED
-    host = HostFreeway(PHILOX_RUN["n"], SEED, **PHILOX_RUN["kw"])
-    host.reset()
-    wins = 0
-    for _ in range(PHILOX_RUN["steps"]):
-        wins += int(host.step(np.full(PHILOX_RUN["n"], PHILOX_RUN["action"]))[1].sum())
+    host, (wins, _, _) = GS.philox_host_run(GAME)
     assert wins >= 1 and host.branches["sticky_repeat"] > 100 and host.branches["truncation"] >= 5
 
 
 # ---------------------------------------------------------------------- the host side of the device environment
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    from prism_amd import _native as N
-    if not os.path.exists(N.LIB_PATH):
-        g.build()
-    return N.lib()
+    return GS.native_lib()
 
 
 def test_symbols_exported_declared_and_mirrored(lib):
-    from prism_amd import _native as N
-    src = open(N.HEADER_PATH).read()
-    raw = ctypes.CDLL(N.LIB_PATH)
-    for name in ("prism_env_freeway_reset", "prism_env_freeway_step"):
-        assert hasattr(raw, name) and re.search(r"\bint " + name + r"\(const prism_env_desc \*d,", src)
-        assert N.SIGNATURES[name][1][0] == ctypes.POINTER(N.EnvDesc)
-    assert N.SIGNATURES["prism_env_freeway_reset"] == N.SIGNATURES["prism_env_breakout_reset"]
-    assert N.SIGNATURES["prism_env_freeway_step"] == N.SIGNATURES["prism_env_breakout_step"]
+    src, signatures = GS.symbols_check(lib, GAME)
+    assert signatures["prism_env_freeway_reset"] == signatures["prism_env_breakout_reset"]
+    assert signatures["prism_env_freeway_step"] == signatures["prism_env_breakout_step"]
     assert "const int8_t *first_speeds_in" in src and "const int8_t *speeds_in" in src
-    assert f"#define PRISM_ENV_STATE_WORDS {N.ENV_STATE_WORDS}" in src and N.ENV_STATE_WORDS == 8
-    makefile = open(os.path.join(H.ROOT, "prism_amd", "csrc", "Makefile")).read()
-    assert "env_freeway.hip" in re.search(r"^SRCS := (.*)$", makefile, re.M).group(1).split()
 
 
 @pytest.mark.parametrize("entry", ["reset", "step"])
-@pytest.mark.parametrize("case", range(len(ENV_REFUSALS)))
+@pytest.mark.parametrize("case", range(len(GS.refusals(GAME))))
 def test_env_refusals_without_device(lib, entry, case):
     """Every refusal of Breakout's table, with the same text, through Freeway's entry points."""
-    edit, text = ENV_REFUSALS[case]
-    d = _fake_desc()
-    if edit is not None:
-        edit(d)
-    p = None if edit is None else ctypes.byref(d)
-    rc = lib.prism_env_freeway_reset(p, None, None) if entry == "reset" else \
-        lib.prism_env_freeway_step(p, 0x40000000, None, None, 0, None)
-    assert rc == -1, (rc, lib.prism_last_error())
-    assert b"check_env: " in lib.prism_last_error() and text in lib.prism_last_error(), lib.prism_last_error()
+    GS.refusal_check(lib, GAME, entry, case)
 
 
 def test_step_refuses_null_actions_and_bad_parity(lib):
-    d = _fake_desc()
-    assert lib.prism_env_freeway_step(ctypes.byref(d), None, None, None, 0, None) == -1
-    assert b"prism_env_freeway_step: actions is null" in lib.prism_last_error()
-    for parity in (2, -1):
-        assert lib.prism_env_freeway_step(ctypes.byref(d), 0x40000000, None, None, parity, None) == -1
-        assert b"parity must be 0 or 1" in lib.prism_last_error()
+    GS.null_actions_and_parity_check(lib, GAME)
 
 
 def test_the_kernels_have_no_private_segment(tmp_path):
-    """Read from the code object's metadata of env_freeway.hip: the .amdhsa_private_segment_fixed_size values only (the
-    cars are looked up by a lane's row: an array would land there)."""
-    import shutil
-    import subprocess
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(H.ROOT, "prism_amd", "csrc")
-    out = tmp_path / "env_freeway.s"
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-                    "-I" + os.path.join(H.ROOT, "include"), "-I" + csrc, "-S", "--cuda-device-only", "-o", str(out),
-                    os.path.join(csrc, "env_freeway.hip")], check=True, timeout=600, stdout=subprocess.DEVNULL,
-                   stderr=subprocess.DEVNULL)
-    kernels = dict(re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", out.read_text(), re.S))
-    names = [k for k in kernels if "env_freeway_" in k]
-    assert len(names) == 2 and sum("env_freeway_reset_kernel" in k for k in names) == sum("env_freeway_step_kernel" in k for k in names) == 1
-    for name in names:
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", kernels[name]).group(1)) == 0, name
-        assert int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", kernels[name]).group(1)) == 0, name
+    """Read from the code object's metadata of env_freeway.hip (the cars are looked up by a lane's row: an array would land
+    in the private segment); no group segment either."""
+    assert set(GS.kernel_segments(GAME, tmp_path).values()) == {(0, 0)}
 
 
 def test_state_codec_round_trips_and_refuses():
@@ -382,18 +320,7 @@ def test_factory_knob_off_on_and_bad(monkeypatch):
     from prism_amd.collectors import VectorCollector
     from prism_amd.config import baseline_config
     from prism_amd.factory import collector_factory, env_factory
-    made = []
-
-    def fake(kind):
-        class Fake:
-            obs_shape, n_actions = (10, 10, 7), 3
-
-            def __init__(self, *a, **kw):
-                made.append((kind, a, kw))
-        return Fake
-
-    monkeypatch.setattr(envs, "DeviceFreeway", fake("freeway"))
-    monkeypatch.setattr(envs, "DeviceBreakout", fake("breakout"))
+    made = GS.fake_device_classes(monkeypatch, GAME, ("Freeway", "Breakout"))
     cfg = baseline_config(2, device="cuda:0", env_name="MinAtar/Freeway-v1", atari_sticky_actions_prob=0.1, num_processes=9,
                           seed=31, episode_timestep_limit=777)
     # the knob off: refused as before, and the text says how to enable the game
@@ -408,15 +335,15 @@ def test_factory_knob_off_on_and_bad(monkeypatch):
     # the knob on
     cfg.device_env_games = ("Breakout", "Freeway")
     assert isinstance(env_factory.build_environment(cfg, 5), envs.DeviceFreeway)
-    assert made == [("freeway", (5, 31, "cuda:0"), dict(sticky_action_prob=0.1, episode_timestep_limit=777, minimal_actions=True))]
+    assert made == [("Freeway", (5, 31, "cuda:0"), dict(sticky_action_prob=0.1, episode_timestep_limit=777, minimal_actions=True))]
     cfg.env_name = "MinAtar/Freeway-v0"
     env_factory.build_environment(cfg, 3, seed=8)
-    assert made[-1][:2] == ("freeway", (3, 8, "cuda:0")) and made[-1][2]["minimal_actions"] is False
+    assert made[-1][:2] == ("Freeway", (3, 8, "cuda:0")) and made[-1][2]["minimal_actions"] is False
     col = collector_factory.build_collector(cfg)
     assert isinstance(col, VectorCollector) and isinstance(col.envs, envs.DeviceFreeway) and made[-1][1][0] == 9
     cfg.env_name = "MinAtar/Breakout-v1"
     env_factory.build_environment(cfg, 4)
-    assert made[-1][0] == "breakout"
+    assert made[-1][0] == "Breakout"
     for game in ("Asterix", "Seaquest", "SpaceInvaders"):
         cfg.env_name = f"MinAtar/{game}-v1"
         with pytest.raises(NotImplementedError, match=game):
@@ -424,7 +351,7 @@ def test_factory_knob_off_on_and_bad(monkeypatch):
     cfg.device_env_games = ["Freeway"]                                         # any sequence; Breakout is then off
     cfg.env_name = "MinAtar/Freeway-v1"
     env_factory.build_environment(cfg, 2)
-    assert made[-1][0] == "freeway"
+    assert made[-1][0] == "Freeway"
     cfg.env_name = "MinAtar/Breakout-v1"
     with pytest.raises(NotImplementedError, match="Breakout"):
         env_factory.build_environment(cfg, 2)
@@ -443,19 +370,9 @@ def test_factory_knob_off_on_and_bad(monkeypatch):
     assert len(made) == n
 
 
-class _NoDevice:
-    """``load_state_dict`` of a device environment with everything a device would need taken away: the checks come first."""
-
-    def __init__(self, cls, **attrs):
-        self.env = cls.__new__(cls)
-        self.env.__dict__.update(dict(_name=cls.__name__, n_envs=4, n_actions=6, seed=9, _started=False), **attrs)
-
-
 def test_snapshot_kind_mismatch_is_refused():
-    import torch
     from prism_amd.envs import DeviceBreakout, DeviceFreeway
-    snap = lambda kind: dict(kind=kind, n_envs=4, n_actions=6, seed=9, started=False, state=torch.zeros((4, 8), dtype=torch.int32))
-    freeway, breakout = _NoDevice(DeviceFreeway).env, _NoDevice(DeviceBreakout).env
+    snap, freeway, breakout = GS.snap, GS.bare(DeviceFreeway), GS.bare(DeviceBreakout)
     with pytest.raises(ValueError, match="kind = 'DeviceBreakout' in the snapshot, 'DeviceFreeway' here"):
         freeway.load_state_dict(snap("DeviceBreakout"))
     with pytest.raises(ValueError, match="kind = 'DeviceFreeway' in the snapshot, 'DeviceBreakout' here"):

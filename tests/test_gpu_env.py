@@ -1,22 +1,18 @@
 """GPU: MinAtar Breakout on the device (``prism_env_breakout_reset`` / ``prism_env_breakout_step``, ``DeviceBreakout``)
 against ``HostBreakout`` (tests/env_ref.py), exactly: the case table with given coins and sides, the Philox path, the
 ping-pong observation buffers, a captured step, ``VectorCollector`` / ``learn()`` / ``VectorEvaluator`` over the device
-environments, and resume."""
-import contextlib
-import io
-
+environments, and resume.  The runs are tests/game_suite.py's; what is Breakout's own stands here: its learner plays the full
+action set through the configuration's own ``build_collector``."""
 import numpy as np
 import pytest
 import torch
 
 from tests import env_cases as EC
-from tests import eval_ref as ER
-from tests import resume_helpers as RH
-from tests.env_ref import HostBreakout, assert_same_state
+from tests import game_suite as GS
+from tests.env_frame_cases import GAMES
 
 pytestmark = pytest.mark.gpu
-
-SEED = 0x5EEDFACE12345
+GAME = GAMES["breakout"]
 
 
 @pytest.fixture(scope="module")
@@ -26,305 +22,48 @@ def dev():
     return "cuda:0"
 
 
-def _pair(dev, n, obs_dtype="float32", seed=SEED, **kw):
-    from prism_amd.envs import DeviceBreakout
-    return DeviceBreakout(n, seed, dev, obs_dtype=obs_dtype, **kw), HostBreakout(n, seed, **kw)
-
-
-def _np(x):
-    return x.cpu().numpy()
-
-
-def assert_step_equal(got, want, where):
-    """(next_obs, reward, done, truncated) of the device against the host's, exactly."""
-    next_obs, reward, done, trunc = got
-    assert reward.dtype == torch.float32 and done.dtype == torch.uint8 and trunc.dtype == torch.uint8
-    np.testing.assert_array_equal(_np(next_obs).astype(np.float32), want[0], err_msg=f"{where}: next_obs")
-    np.testing.assert_array_equal(_np(reward).view(np.uint32), want[1].view(np.uint32), err_msg=f"{where}: reward")
-    np.testing.assert_array_equal(_np(done), want[2], err_msg=f"{where}: done")
-    np.testing.assert_array_equal(_np(trunc), want[3], err_msg=f"{where}: truncated")
-
-
-def assert_env_equal(env, host, where):
-    assert_same_state(env.get_state(), host.get_state(), where)
-    np.testing.assert_array_equal(_np(env.observe()).astype(np.float32), host.observe(), err_msg=f"{where}: acting observation")
-
-
 # ---------------------------------------------------------------------------------------------------- the kernel
 @pytest.mark.parametrize("obs_dtype", ["float32", "uint8"])
 @pytest.mark.parametrize("n", [1, 3, 4, 5, 65])
 @pytest.mark.parametrize("group", sorted(EC.GROUPS))
 def test_kernel_equals_the_host_restatement_on_the_case_table(dev, group, n, obs_dtype):
-    """Every case of the group (offsets 0, n, 2n, ... lay all of them over the n environments), every state field, both
-    images, reward, done and truncated after every step; the observation the step acted on is left alone."""
-    from prism_amd import _native as N
-    n_cases = len(EC.group_cases(group))
-    for offset in range(0, n_cases, n):
-        env, host = _pair(dev, n, obs_dtype, **EC.GROUPS[group])
-        assert env.n_actions == host.n_actions and tuple(env.obs_shape) == (10, 10, 4)
-        state, actions, u, side = EC.vector(group, n, offset)
-        env.set_state(state)
-        host.set_state(state)
-        assert env.observe().dtype == getattr(torch, obs_dtype)
-        assert_env_equal(env, host, f"{group} + {offset}: installed")
-        for k in range(actions.shape[0]):
-            where = f"{group} + {offset}, step {k}"
-            acted_on = env.observe()
-            kept = acted_on.clone()
-            got = env.step(torch.from_numpy(actions[k]).to(dev), u=u[k], side=side[k])
-            assert_step_equal(got, host.step(actions[k], u=u[k], side=side[k]), where)
-            assert_env_equal(env, host, where)
-            assert env.observe().data_ptr() != acted_on.data_ptr() and torch.equal(acted_on, kept), where
-        bad = any(EC.CASES[name].get("bad_action") for name in EC.vector_names(group, n, offset))
-        assert host.bad_action == bad
-        if bad:
-            with pytest.raises(N.PrismError, match="outside"):
-                env.check_status()
-        env.close()          # (the status word is clean, or was cleared by the check above)
+    GS.case_table_run(GAME, dev, group, n, obs_dtype)
 
 
 def test_philox_path_200_steps_at_n_5(dev):
-    """The device's own draws (sticky coins, sides, the first side) against the host drawing through philox4x32; host actions
-    (the pinned rotation) and device actions by turns; one lifetime count about to carry into its high word."""
-    n = 5
-    env, host = _pair(dev, n, sticky_action_prob=0.25, episode_timestep_limit=30)
-    np.testing.assert_array_equal(_np(env.reset()), host.reset())
-    st = host.get_state()
-    st["t"][1] = 2 ** 32 - 3
-    env.set_state(st)
-    host.set_state(st)
-    rng = np.random.default_rng(3)
-    ends = 0
-    for k in range(200):
-        hs = host.get_state()
-        track = np.where(hs["ball_x"] < hs["pos"], 1, np.where(hs["ball_x"] > hs["pos"], 3, 0))
-        acts = np.where(rng.random(n) < 0.6, track, rng.integers(0, 6, n)).astype(np.int64)
-        got = env.step(acts if k % 2 else torch.from_numpy(acts).to(dev))
-        want = host.step(acts)
-        assert_step_equal(got, want, f"step {k}")
-        assert_env_equal(env, host, f"step {k}")
-        ends += int(want[2].sum() + want[3].sum())
-    assert ends >= 10 and host.branches["sticky_repeat"] > 100 and host.branches["reset_side_0"] and host.branches["reset_side_1"]
-    assert int(env.get_state()["t"][1]) == 2 ** 32 - 3 + 200
-    env.close()
+    """The device's own draws (sticky coins, sides, the first side) against the host drawing through philox4x32; the lifetime
+    count of environment 1 is about to carry from the first step on."""
+    host, (_, terminals, truncations) = GS.philox_run(GAME, dev)
+    assert terminals + truncations >= 10 and host.branches["sticky_repeat"] > 100
+    assert host.branches["reset_side_0"] and host.branches["reset_side_1"]
 
 
 def test_the_previous_acting_observation_survives_step(dev):
-    env, host = _pair(dev, 7)
-    first = env.reset()
-    host.reset()
-    seen = [first.data_ptr()]
-    for k in range(6):
-        acted_on, want = env.observe(), host.observe()
-        env.step(torch.full((7,), 3, dtype=torch.int64, device=dev))
-        host.step(np.full(7, 3))
-        np.testing.assert_array_equal(_np(acted_on), want)          # still what the step acted on
-        np.testing.assert_array_equal(_np(env.observe()), host.observe())
-        seen.append(env.observe().data_ptr())
-    assert seen[0::2] == [seen[0]] * 4 and seen[1::2] == [seen[1]] * 3 and seen[0] != seen[1]          # two addresses, by turns
-    with pytest.raises(RuntimeError, match="reset"):
-        _pair(dev, 2)[0].step(np.zeros(2, np.int64))
-    with pytest.raises(ValueError, match="actions"):
-        env.step(torch.zeros(6, dtype=torch.int64, device=dev))
+    GS.ping_pong_check(GAME, dev, lambda k: 3)
 
 
 def test_a_captured_step_replayed_50_times_equals_an_eager_twin(dev):
-    """The launch takes no host value that changes between steps: one captured ``step`` replayed 50 times (the actions
-    change in their buffer) is the eager twin's 50 steps, bit for bit."""
-    n = 9
-    kw = dict(sticky_action_prob=0.25, episode_timestep_limit=20)
-    graphed, eager = _pair(dev, n, **kw)[0], _pair(dev, n, **kw)[0]
-    rng = np.random.default_rng(8)
-    acts = torch.from_numpy(rng.integers(0, 6, (51, n))).to(dev)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    got, want = [], []
-    with torch.cuda.stream(side):
-        buf = acts[0].clone()
-        graphed.reset()
-        graphed.step(buf)                        # (eager once: the first launch of a kernel loads it)
-        side.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            out = graphed.step(buf)
-        written = graphed.observe()              # the ping-pong buffer the captured launch writes
-        for k in range(1, 51):
-            buf.copy_(acts[k])
-            g.replay()
-            got.append([t.clone() for t in out] + [written.clone()])
-        side.synchronize()
-    eager.reset()
-    eager.step(acts[0])
-    for k in range(1, 51):
-        out_e = eager.step(acts[k])
-        want.append([t.clone() for t in out_e] + [eager.observe().clone()])
-    torch.cuda.synchronize()
-    for k, (a, b) in enumerate(zip(got, want)):
-        for name, x, y in zip(("next_obs", "reward", "done", "truncated", "acting observation"), a, b):
-            assert torch.equal(x, y), f"replay {k}: {name}"
-    assert_same_state(graphed.get_state(), eager.get_state(), "after 50 replays")
-    assert int(eager.get_state()["t"].min()) == 51 and sum(int(w[2].sum() + w[3].sum()) for w in want) >= 5
+    GS.captured_step_run(GAME, dev, obs_dtype="float32")
 
 
 # ---------------------------------------------------------------------------------------------------- collector, learn, evaluator
-ENV_NAME = "MinAtar/Breakout-v0"
-
-
-def _learner(dev, ckpt_dir, envs=None, **over):
-    """A small learner (tests/resume_helpers.py case (a): IQN + PER + epsilon-greedy) over ``envs`` or, by default, over the
-    configuration's own device environments (``build_collector``)."""
-    from prism_amd.collectors import VectorCollector
-    from prism_amd.factory.collector_factory import build_collector
-    from prism_amd.learner import Learner
-    kw = dict(env_name=ENV_NAME, num_processes=RH.N_ENV, atari_sticky_actions_prob=0.1, episode_timestep_limit=25,
-              experience_replay_capacity=512)
-    kw.update(over)
-    cfg = RH.make_config("a_iqn_per_egreedy_adam", ckpt_dir, dev, **kw)
-    col = build_collector(cfg) if envs is None else VectorCollector(envs(cfg), cfg)
-    ln = Learner()
-    with contextlib.redirect_stdout(io.StringIO()):
-        ln.configure(cfg, collector=col)
-    return ln, col
-
-
-def _ring(buf):
-    buf.flush()
-    torch.cuda.synchronize()
-    return {name: getattr(buf, name).cpu().clone() for name in ("obs", "succ_obs", "reward", "action", "flags", "link", "back")
-            if getattr(buf, name) is not None}
-
-
 def test_vector_collector_rows_equal_a_twin_fed_by_the_host_restatement(dev, tmp_path):
-    from prism_amd.envs import DeviceBreakout
-    ln_d, col_d = _learner(dev, tmp_path / "d")
-    ln_h, col_h = _learner(dev, tmp_path / "h", envs=lambda cfg: HostBreakout(
-        RH.N_ENV, cfg.seed, sticky_action_prob=cfg.atari_sticky_actions_prob, episode_timestep_limit=cfg.episode_timestep_limit))
-    assert isinstance(col_d.envs, DeviceBreakout) and col_d.envs.seed == col_h.envs.seed == ln_d.agent.config.seed
-    assert col_d.get_env_info() == ((10, 10, 4), 6, 1)
-    for ln, col in ((ln_d, col_d), (ln_h, col_h)):
-        assert col.collect_timesteps(40, ln.agent, ln.experience_buffer, random=True) == 40
-        assert col.collect_timesteps(120, ln.agent, ln.experience_buffer) == 120
-    ring_d, ring_h = _ring(ln_d.experience_buffer), _ring(ln_h.experience_buffer)
-    RH.assert_same(ring_d, ring_h, "ring")
-    assert ln_d.experience_buffer.episode_stats() == ln_h.experience_buffer.episode_stats()
-    assert ln_d.experience_buffer.episode_stats()["episodes"] >= 5
-    assert_env_equal(col_d.envs, col_h.envs, "after 160 rows")
-    assert len(ring_d["action"][:160].unique()) > 1
-    col_d.close()
-
-
-def _learn(dev, ckpt_dir):
-    ln, col = _learner(dev, ckpt_dir, num_initial_random_timesteps=40, timestep_limit=40 + RH.N_ENV * 60,
-                       timesteps_per_report=100, timesteps_between_evaluations=10 ** 6)
-    buf = ln.experience_buffer
-    with contextlib.redirect_stdout(io.StringIO()):
-        real_empty, buf.empty = buf.empty, lambda: None          # learn() empties the buffer on exit: keep it for the checks
-        ln.learn()
-        buf.empty = real_empty
-    return ln, col
+    GS.collector_twin_run(GAME, dev, tmp_path)[2].close()
 
 
 def test_learn_twice_from_one_seed_is_bit_identical(dev, tmp_path):
-    a, col_a = _learn(dev, tmp_path / "a")
-    b, col_b = _learn(dev, tmp_path / "b")
-    assert a.cumulative_timesteps == b.cumulative_timesteps == 40 + RH.N_ENV * 60 and a.cumulative_model_updates == 60
-    assert col_a.envs.closed and col_a.rows == 340
-    RH.assert_same(RH.full_state(a), RH.full_state(b), "learn")
-    RH.assert_same(_ring(a.experience_buffer), _ring(b.experience_buffer), "ring")
-    assert_same_state(col_a.envs.get_state(), col_b.envs.get_state(), "environments")
-    assert int(col_a.envs.get_state()["t"].min()) == 340 // RH.N_ENV
-    assert a.experience_buffer.episode_stats() == b.experience_buffer.episode_stats()
-    assert a.experience_buffer.episode_stats()["episodes"] >= 5
+    GS.learn_twice_check(GAME, dev, tmp_path, updates=60)
 
 
 def test_vector_evaluator_over_the_device_equals_eval_host_on_the_restatement(dev):
-    from prism_amd.evals import EVAL_DRAW_BASE, VectorEvaluator
     from tests.test_gpu_eval import _agent
-    n, horizon = 5, 203
-    kw = dict(sticky_action_prob=0.1, episode_timestep_limit=30)
-    env, host = _pair(dev, n, **kw)
-    _, agent = _agent(dev)
-    ev = VectorEvaluator(agent, env, 0, horizon)
-    returns = ev.evaluate_agent()
-    _, twin = _agent(dev)
-    want = ER.EvalHost(n, horizon)
-    twin.eval()
-    with twin.acting_stream(EVAL_DRAW_BASE):
-        obs, steps = host.reset(), 0
-        while True:
-            _, reward, done, trunc = host.step(twin.forward(obs))
-            want.track(reward, done, trunc)
-            obs = host.observe()
-            steps += 1
-            if steps * n >= horizon and want.closed():
-                break
-    twin.train()
-    np.testing.assert_array_equal(ER.bits64(returns), ER.bits64(want.returns()))
-    assert ev.last == want.result() and ev.last["timesteps"] == steps * n and ev.last["episodes"] >= 3
-    assert_env_equal(env, host, "after the evaluation")
-    # a second evaluation starts the environments afresh: same episodes unless the agent's draws differ
-    assert len(ev.evaluate_agent()) >= 3
-    env.close()
+    GS.evaluator_run(GAME, dev, make_agent=lambda: _agent(dev)[1])
 
 
 # ---------------------------------------------------------------------------------------------------- resume
 def test_state_dict_into_a_fresh_object_continues_bit_identically(dev):
-    from prism_amd.util import snapshot
-    n = 6
-    kw = dict(sticky_action_prob=0.25, episode_timestep_limit=20, minimal_actions=True)
-    a, host = _pair(dev, n, "uint8", **kw)
-    a.reset()
-    host.reset()
-    rng = np.random.default_rng(4)
-    acts = rng.integers(0, 3, (60, n))
-    for k in range(30):
-        a.step(acts[k])
-        host.step(acts[k])
-    sd = a.state_dict()
-    snapshot.check_plain(sd)
-    b = _pair(dev, n, "uint8", **kw)[0]
-    b.load_state_dict(sd)
-    np.testing.assert_array_equal(_np(b.observe()), _np(a.observe()))
-    for k in range(30, 60):
-        out_a, out_b = a.step(acts[k]), b.step(acts[k])
-        want = host.step(acts[k])
-        assert_step_equal(out_b, want, f"step {k}")
-        for x, y in zip(out_a, out_b):
-            assert torch.equal(x, y)
-        assert torch.equal(a.observe(), b.observe())
-    assert_env_equal(b, host, "continued")
-    fresh = _pair(dev, n, "uint8", **kw)[0]
-    fresh.load_state_dict(fresh.state_dict())          # never started: stays so
-    with pytest.raises(RuntimeError, match="reset"):
-        fresh.observe()
-    with pytest.raises(ValueError, match="n_envs"):
-        _pair(dev, n + 1, "uint8", **kw)[0].load_state_dict(sd)
-    with pytest.raises(ValueError, match="seed"):
-        _pair(dev, n, "uint8", seed=1, **kw)[0].load_state_dict(sd)
-
-
-def _iterate(ln, col):
-    col.collect_timesteps(RH.N_ENV, ln.agent, ln.experience_buffer)
-    ln.cumulative_timesteps += RH.N_ENV
-    td = ln.step(RH.N_ENV)
-    return td.cpu().clone(), col.envs.get_state()
+    GS.state_dict_run(GAME, dev, np.random.default_rng(4).integers(0, 3, (60, 6)), other="freeway")
 
 
 def test_learner_save_state_carries_the_environments_through_the_collector_key(dev, tmp_path):
-    ln, col = _learner(dev, tmp_path / "a")
-    col.collect_timesteps(40, ln.agent, ln.experience_buffer, random=True)
-    ln.cumulative_timesteps += 40
-    for _ in range(6):
-        _iterate(ln, col)
-    ln.save_state(tmp_path / "snap")
-    assert "envs" in ln._state_part()["collector"]
-    want = [_iterate(ln, col) for _ in range(8)]
-    ln2, col2 = _learner(dev, tmp_path / "b")
-    ln2.load_state(tmp_path / "snap")
-    got = [_iterate(ln2, col2) for _ in range(8)]
-    for k, ((td_a, st_a), (td_b, st_b)) in enumerate(zip(want, got)):
-        assert torch.equal(td_a.view(torch.int32), td_b.view(torch.int32)), f"iteration {k}: TD errors"
-        assert_same_state(st_b, st_a, f"iteration {k}")
-    RH.assert_same(RH.full_state(ln2), RH.full_state(ln), "resumed")
-    RH.assert_same(_ring(ln2.experience_buffer), _ring(ln.experience_buffer), "ring")
-    assert int(col2.envs.get_state()["t"].min()) == (40 + 14 * RH.N_ENV) // RH.N_ENV
+    GS.save_state_check(GAME, dev, tmp_path)

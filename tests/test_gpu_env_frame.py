@@ -43,8 +43,8 @@ def test_every_game_on_the_frame_equals_its_host_restatement(dev, game, n, obs_d
     from prism_amd import envs
     first, steps = _reference(game, n)
     _, assert_same_state = FC.host(game, n)
-    env = getattr(envs, FC.GAMES[game][0])(n, FC.SEED, dev, obs_dtype=obs_dtype, **FC.KW)
-    assert env.n_actions == 6 and tuple(env.obs_shape) == FC.GAMES[game][3]
+    env = getattr(envs, FC.GAMES[game].device)(n, FC.SEED, dev, obs_dtype=obs_dtype, **FC.KW)
+    assert env.n_actions == 6 and tuple(env.obs_shape) == FC.GAMES[game].obs_shape
     got = env.reset()
     assert got.dtype == getattr(torch, obs_dtype)
     np.testing.assert_array_equal(got.cpu().numpy().astype(np.float32), first, err_msg="reset")

@@ -1,24 +1,18 @@
 """GPU: MinAtar Freeway on the device (``prism_env_freeway_reset`` / ``prism_env_freeway_step``, ``DeviceFreeway``) against
 ``HostFreeway`` (tests/freeway_ref.py), exactly: the case table with given coins and speeds, the Philox path, the ping-pong
 observation buffers, a captured step, ``VectorCollector`` / ``learn()`` / ``VectorEvaluator`` over the device environments
-(C = 7, A = 3; the first 700-byte observation rows to reach ingestion from a device buffer), and resume."""
-import contextlib
-import io
-
+(C = 7, A = 3; the first 700-byte observation rows to reach ingestion from a device buffer), and resume.  The runs are
+tests/game_suite.py's; what is Freeway's own stands here."""
 import numpy as np
 import pytest
 import torch
 
-from tests import eval_ref as ER
 from tests import freeway_cases as FC
-from tests import resume_helpers as RH
-from tests.freeway_ref import HostFreeway, assert_same_state
+from tests import game_suite as GS
+from tests.env_frame_cases import GAMES
 
 pytestmark = pytest.mark.gpu
-
-SEED = 0x5EEDFACE12345
-# the Philox-path run; tests/test_freeway_host.py shows on HostFreeway alone that it has a win
-PHILOX_RUN = dict(n=5, steps=200, action=2, kw=dict(sticky_action_prob=0.25, episode_timestep_limit=60))
+GAME = GAMES["freeway"]
 
 
 @pytest.fixture(scope="module")
@@ -28,95 +22,26 @@ def dev():
     return "cuda:0"
 
 
-def _pair(dev, n, obs_dtype="float32", seed=SEED, **kw):
-    from prism_amd.envs import DeviceFreeway
-    return DeviceFreeway(n, seed, dev, obs_dtype=obs_dtype, **kw), HostFreeway(n, seed, **kw)
-
-
-def _np(x):
-    return x.cpu().numpy()
-
-
-def assert_step_equal(got, want, where):
-    """(next_obs, reward, done, truncated) of the device against the host's, exactly."""
-    next_obs, reward, done, trunc = got
-    assert reward.dtype == torch.float32 and done.dtype == torch.uint8 and trunc.dtype == torch.uint8
-    np.testing.assert_array_equal(_np(next_obs).astype(np.float32), want[0], err_msg=f"{where}: next_obs")
-    np.testing.assert_array_equal(_np(reward).view(np.uint32), want[1].view(np.uint32), err_msg=f"{where}: reward")
-    np.testing.assert_array_equal(_np(done), want[2], err_msg=f"{where}: done")
-    np.testing.assert_array_equal(_np(trunc), want[3], err_msg=f"{where}: truncated")
-
-
-def assert_env_equal(env, host, where):
-    assert_same_state(env.get_state(), host.get_state(), where)
-    np.testing.assert_array_equal(_np(env.observe()).astype(np.float32), host.observe(), err_msg=f"{where}: acting observation")
-
-
 # ---------------------------------------------------------------------------------------------------- the kernel
 @pytest.mark.parametrize("obs_dtype", ["float32", "uint8"])
 @pytest.mark.parametrize("n", [1, 3, 4, 5, 65])
 @pytest.mark.parametrize("group", sorted(FC.GROUPS))
 def test_kernel_equals_the_host_restatement_on_the_case_table(dev, group, n, obs_dtype):
-    """Every case of the group (offsets 0, n, 2n, ... lay all of them over the n environments), every state field, both
-    images, reward, done and truncated after every step; the observation the step acted on is left alone."""
-    from prism_amd import _native as N
-    n_cases = len(FC.group_cases(group))
-    for offset in range(0, n_cases, n):
-        env, host = _pair(dev, n, obs_dtype, **FC.GROUPS[group])
-        assert env.n_actions == host.n_actions and tuple(env.obs_shape) == (10, 10, 7)
-        state, actions, u, speeds = FC.vector(group, n, offset)
-        env.set_state(state)
-        host.set_state(state)
-        assert env.observe().dtype == getattr(torch, obs_dtype) and env.observe().shape == (n, 10, 10, 7)
-        assert_env_equal(env, host, f"{group} + {offset}: installed")
-        for k in range(actions.shape[0]):
-            where = f"{group} + {offset}, step {k}"
-            acted_on = env.observe()
-            kept = acted_on.clone()
-            got = env.step(torch.from_numpy(actions[k]).to(dev), u=u[k], speeds=speeds[k])
-            assert_step_equal(got, host.step(actions[k], u=u[k], speeds=speeds[k]), where)
-            assert_env_equal(env, host, where)
-            assert env.observe().data_ptr() != acted_on.data_ptr() and torch.equal(acted_on, kept), where
-        bad = any(FC.CASES[name].get("bad_action") for name in FC.vector_names(group, n, offset))
-        assert host.bad_action == bad
-        if bad:
-            with pytest.raises(N.PrismError, match="outside"):
-                env.check_status()
-        env.close()          # (the status word is clean, or was cleared by the check above)
+    GS.case_table_run(GAME, dev, group, n, obs_dtype)
 
 
 def test_philox_path_200_steps_at_n_5(dev):
     """The device's own draws (sticky coins, the first speeds, win and reset speeds) against the host drawing through
-    philox4x32; host actions (the pinned rotation) and device actions by turns; one lifetime count about to carry into its
-    high word.  Hold u: the run must win at least once."""
-    n, steps = PHILOX_RUN["n"], PHILOX_RUN["steps"]
-    env, host = _pair(dev, n, **PHILOX_RUN["kw"])
-    np.testing.assert_array_equal(_np(env.reset()), host.reset())
-    assert_env_equal(env, host, "reset")
-    acts = np.full(n, PHILOX_RUN["action"], dtype=np.int64)
-    wins = ends = 0
-    for k in range(steps):
-        if k == 100:          # from here on environment 1 draws beyond a 32-bit counter
-            st = host.get_state()
-            st["t"][1] = 2 ** 32 - 3
-            env.set_state(st)
-            host.set_state(st)
-        got = env.step(acts if k % 2 else torch.from_numpy(acts).to(dev))
-        want = host.step(acts)
-        assert_step_equal(got, want, f"step {k}")
-        assert_env_equal(env, host, f"step {k}")
-        wins += int(want[1].sum())
-        ends += int(want[3].sum())
+    philox4x32.  Hold u: the run must win at least once."""
+    host, (wins, _, ends) = GS.philox_run(GAME, dev)
     assert wins >= 1 and ends >= 5 and host.branches["sticky_repeat"] > 100 and host.branches["win"] == wins
-    assert int(env.get_state()["t"][1]) == 2 ** 32 - 3 + 100
-    env.close()
 
 
 def test_given_first_speeds_and_argument_checks(dev):
-    env, host = _pair(dev, 3, "uint8")
+    env, host = GS.pair(GAME, dev, 3, "uint8")
     first = np.array([FC.SLOW, FC.FAST, FC.SPEEDS], dtype=np.int8)
-    np.testing.assert_array_equal(_np(env.reset(first_speeds=first)).astype(np.float32), host.reset(first_speeds=first))
-    assert_env_equal(env, host, "reset with given speeds")
+    np.testing.assert_array_equal(env.reset(first_speeds=first).cpu().numpy().astype(np.float32), host.reset(first_speeds=first))
+    GS.assert_env_equal(GAME, env, host, "reset with given speeds")
     np.testing.assert_array_equal(env.get_state()["car_speed"], first)
     with pytest.raises(ValueError, match="8 values per environment"):
         env.reset(first_speeds=first[:2])
@@ -127,261 +52,41 @@ def test_given_first_speeds_and_argument_checks(dev):
 
 
 def test_the_previous_acting_observation_survives_step(dev):
-    env, host = _pair(dev, 7)
-    first = env.reset()
-    host.reset()
-    seen = [first.data_ptr()]
-    for k in range(6):
-        acted_on, want = env.observe(), host.observe()
-        env.step(torch.full((7,), 2, dtype=torch.int64, device=dev))
-        host.step(np.full(7, 2))
-        np.testing.assert_array_equal(_np(acted_on), want)          # still what the step acted on
-        np.testing.assert_array_equal(_np(env.observe()), host.observe())
-        seen.append(env.observe().data_ptr())
-    assert seen[0::2] == [seen[0]] * 4 and seen[1::2] == [seen[1]] * 3 and seen[0] != seen[1]          # two addresses, by turns
-    with pytest.raises(RuntimeError, match="reset"):
-        _pair(dev, 2)[0].step(np.zeros(2, np.int64))
-    with pytest.raises(ValueError, match="actions"):
-        env.step(torch.zeros(6, dtype=torch.int64, device=dev))
+    GS.ping_pong_check(GAME, dev, lambda k: 2)
 
 
 def test_a_captured_step_replayed_50_times_equals_an_eager_twin(dev):
-    """The launch takes no host value that changes between steps: one captured ``step`` replayed 50 times (the actions
-    change in their buffer) is the eager twin's 50 steps, bit for bit."""
-    n = 9
-    kw = dict(sticky_action_prob=0.25, episode_timestep_limit=20)
-    graphed, eager = _pair(dev, n, "uint8", **kw)[0], _pair(dev, n, "uint8", **kw)[0]
     rng = np.random.default_rng(8)
-    acts = torch.from_numpy(np.where(rng.random((51, n)) < 0.7, 2, rng.integers(0, 6, (51, n)))).to(dev)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    got, want = [], []
-    with torch.cuda.stream(side):
-        buf = acts[0].clone()
-        graphed.reset()
-        graphed.step(buf)                        # (eager once: the first launch of a kernel loads it)
-        side.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            out = graphed.step(buf)
-        written = graphed.observe()              # the ping-pong buffer the captured launch writes
-        for k in range(1, 51):
-            buf.copy_(acts[k])
-            g.replay()
-            got.append([t.clone() for t in out] + [written.clone()])
-        side.synchronize()
-    eager.reset()
-    eager.step(acts[0])
-    for k in range(1, 51):
-        out_e = eager.step(acts[k])
-        want.append([t.clone() for t in out_e] + [eager.observe().clone()])
-    torch.cuda.synchronize()
-    for k, (a, b) in enumerate(zip(got, want)):
-        for name, x, y in zip(("next_obs", "reward", "done", "truncated", "acting observation"), a, b):
-            assert torch.equal(x, y), f"replay {k}: {name}"
-    assert_same_state(graphed.get_state(), eager.get_state(), "after 50 replays")
-    assert int(eager.get_state()["t"].min()) == 51 and sum(int(w[2].sum() + w[3].sum()) for w in want) >= 5
+    GS.captured_step_run(GAME, dev, acts=np.where(rng.random((51, 9)) < 0.7, 2, rng.integers(0, 6, (51, 9))))
 
 
 # ---------------------------------------------------------------------------------------------------- collector, learn, evaluator
-ENV_NAME = "MinAtar/Freeway-v1"
-
-
-def _learner(dev, ckpt_dir, envs=None, obs_storage="float32", **over):
-    """A small learner (tests/resume_helpers.py case (a): IQN + PER + epsilon-greedy) over ``envs`` or, by default, over the
-    configuration's own device environments (``build_collector`` with the Freeway knob on): C = 7, A = 3."""
-    from prism_amd.collectors import VectorCollector
-    from prism_amd.factory.collector_factory import build_collector
-    from prism_amd.learner import Learner
-    kw = dict(env_name=ENV_NAME, num_processes=RH.N_ENV, atari_sticky_actions_prob=0.1, episode_timestep_limit=25,
-              experience_replay_capacity=512)
-    kw.update(over)
-    cfg = RH.make_config("a_iqn_per_egreedy_adam", ckpt_dir, dev, **kw)
-    cfg.device_env_games = ("Breakout", "Freeway")
-    cfg.replay_obs_storage = obs_storage
-    col = build_collector(cfg) if envs is None else VectorCollector(envs(cfg), cfg)
-    ln = Learner()
-    with contextlib.redirect_stdout(io.StringIO()):
-        ln.configure(cfg, collector=col)
-    return ln, col
-
-
-def _ring(buf):
-    buf.flush()
-    torch.cuda.synchronize()
-    return {name: getattr(buf, name).cpu().clone() for name in ("obs", "succ_obs", "reward", "action", "flags", "link", "back")
-            if getattr(buf, name) is not None}
-
-
 @pytest.mark.parametrize("obs_storage", ["float32", "uint8"])
 def test_vector_collector_rows_equal_a_twin_fed_by_the_host_restatement(dev, tmp_path, obs_storage):
     """Into an fp32 ring and into a byte ring; the device side hands ingestion uint8 observation rows of 700 bytes (4-byte
     aligned only) in the byte case, fp32 rows of 2800 bytes otherwise."""
-    from prism_amd.envs import DeviceFreeway
-    obs_dtype = obs_storage
-    ln_d, col_d = _learner(dev, tmp_path / "d", obs_storage=obs_storage, envs=lambda cfg: DeviceFreeway(
-        RH.N_ENV, cfg.seed, dev, sticky_action_prob=cfg.atari_sticky_actions_prob, episode_timestep_limit=cfg.episode_timestep_limit,
-        minimal_actions=True, obs_dtype=obs_dtype))
-    ln_h, col_h = _learner(dev, tmp_path / "h", obs_storage=obs_storage, envs=lambda cfg: HostFreeway(
-        RH.N_ENV, cfg.seed, sticky_action_prob=cfg.atari_sticky_actions_prob, episode_timestep_limit=cfg.episode_timestep_limit,
-        minimal_actions=True))
-    assert col_d.envs.seed == col_h.envs.seed == ln_d.agent.config.seed
-    assert col_d.get_env_info() == ((10, 10, 7), 3, 1)
-    for ln, col in ((ln_d, col_d), (ln_h, col_h)):
-        assert col.collect_timesteps(40, ln.agent, ln.experience_buffer, random=True) == 40
-        assert col.collect_timesteps(120, ln.agent, ln.experience_buffer) == 120
-    ring_d, ring_h = _ring(ln_d.experience_buffer), _ring(ln_h.experience_buffer)
-    assert col_d.envs.observe().dtype == ring_d["obs"].dtype == getattr(torch, obs_storage)
-    RH.assert_same(ring_d, ring_h, "ring")
-    ln_d.experience_buffer.check_status()
+    ring_d, _, col_d, _ = GS.collector_twin_run(GAME, dev, tmp_path, obs_storage)
     assert ring_d["obs"][:160].reshape(160, -1).float().sum(dim=1).eq(17).all()          # a chicken, eight cars, eight trails a row
-    assert ln_d.experience_buffer.episode_stats() == ln_h.experience_buffer.episode_stats()
-    assert ln_d.experience_buffer.episode_stats()["episodes"] >= 5
-    assert_env_equal(col_d.envs, col_h.envs, "after 160 rows")
-    assert len(ring_d["action"][:160].unique()) > 1
     col_d.close()
 
 
 def test_build_collector_with_the_knob_builds_device_freeway(dev, tmp_path):
-    from prism_amd.envs import DeviceFreeway
-    ln, col = _learner(dev, tmp_path / "k")
-    assert isinstance(col.envs, DeviceFreeway) and col.envs.minimal_actions and col.envs.n_envs == RH.N_ENV
-    assert col.envs.seed == ln.agent.config.seed and col.get_env_info() == ((10, 10, 7), 3, 1)
-    col.close()
-
-
-def _learn(dev, ckpt_dir):
-    ln, col = _learner(dev, ckpt_dir, num_initial_random_timesteps=40, timestep_limit=40 + RH.N_ENV * 40,
-                       timesteps_per_report=100, timesteps_between_evaluations=10 ** 6)
-    buf = ln.experience_buffer
-    with contextlib.redirect_stdout(io.StringIO()):
-        real_empty, buf.empty = buf.empty, lambda: None          # learn() empties the buffer on exit: keep it for the checks
-        ln.learn()
-        buf.empty = real_empty
-    return ln, col
+    GS.knob_collector_check(GAME, dev, tmp_path).close()
 
 
 def test_learn_twice_from_one_seed_is_bit_identical(dev, tmp_path):
-    a, col_a = _learn(dev, tmp_path / "a")
-    b, col_b = _learn(dev, tmp_path / "b")
-    assert a.cumulative_timesteps == b.cumulative_timesteps == 40 + RH.N_ENV * 40 and a.cumulative_model_updates == 40
-    assert col_a.envs.closed and col_a.rows == 240 and col_a.get_env_info() == ((10, 10, 7), 3, 1)
-    RH.assert_same(RH.full_state(a), RH.full_state(b), "learn")
-    RH.assert_same(_ring(a.experience_buffer), _ring(b.experience_buffer), "ring")
-    assert_same_state(col_a.envs.get_state(), col_b.envs.get_state(), "environments")
-    assert int(col_a.envs.get_state()["t"].min()) == 240 // RH.N_ENV
-    assert a.experience_buffer.episode_stats() == b.experience_buffer.episode_stats()
-    assert a.experience_buffer.episode_stats()["episodes"] >= 5
-
-
-def _agent(dev):
-    from prism_amd.config import baseline_config
-    from prism_amd.factory import agent_factory
-    cfg = baseline_config(2, device=dev, batch_size=16, log_to_wandb=False, seed=SEED & 0xFFFF)
-    torch.manual_seed(11)
-    with contextlib.redirect_stdout(io.StringIO()):
-        agent = agent_factory.build_agent(cfg, (10, 10, 7), 3)
-    gen = torch.Generator().manual_seed(5)          # away from the initialisation: actions that depend on the draws
-    agent.model.load_state_dict({k: v.cpu() + 0.05 * torch.randn(v.shape, generator=gen)
-                                 for k, v in agent.model.state_dict().items()})
-    agent._params_replaced()
-    return agent
+    GS.learn_twice_check(GAME, dev, tmp_path)
 
 
 def test_vector_evaluator_over_the_device_equals_eval_host_on_the_restatement(dev):
-    from prism_amd.evals import EVAL_DRAW_BASE, VectorEvaluator
-    n, horizon = 5, 203
-    kw = dict(sticky_action_prob=0.1, episode_timestep_limit=30, minimal_actions=True)
-    env, host = _pair(dev, n, **kw)
-    agent = _agent(dev)
-    ev = VectorEvaluator(agent, env, 0, horizon)
-    returns = ev.evaluate_agent()
-    twin = _agent(dev)
-    want = ER.EvalHost(n, horizon)
-    twin.eval()
-    with twin.acting_stream(EVAL_DRAW_BASE):
-        obs, steps = host.reset(), 0
-        while True:
-            _, reward, done, trunc = host.step(twin.forward(obs))
-            want.track(reward, done, trunc)
-            obs = host.observe()
-            steps += 1
-            if steps * n >= horizon and want.closed():
-                break
-    twin.train()
-    np.testing.assert_array_equal(ER.bits64(returns), ER.bits64(want.returns()))
-    assert ev.last == want.result() and ev.last["timesteps"] == steps * n and ev.last["episodes"] >= 3
-    assert_env_equal(env, host, "after the evaluation")
-    assert len(ev.evaluate_agent()) >= 3
-    env.close()
+    GS.evaluator_run(GAME, dev, minimal_actions=True)
 
 
 # ---------------------------------------------------------------------------------------------------- resume
 def test_state_dict_into_a_fresh_object_continues_bit_identically(dev):
-    from prism_amd.envs import DeviceBreakout
-    from prism_amd.util import snapshot
-    n = 6
-    kw = dict(sticky_action_prob=0.25, episode_timestep_limit=20, minimal_actions=True)
-    a, host = _pair(dev, n, "uint8", **kw)
-    a.reset()
-    host.reset()
     rng = np.random.default_rng(4)
-    acts = np.where(rng.random((60, n)) < 0.7, 1, rng.integers(0, 3, (60, n)))
-    for k in range(30):
-        a.step(acts[k])
-        host.step(acts[k])
-    sd = a.state_dict()
-    snapshot.check_plain(sd)
-    assert sd["kind"] == "DeviceFreeway"
-    b = _pair(dev, n, "uint8", **kw)[0]
-    b.load_state_dict(sd)
-    np.testing.assert_array_equal(_np(b.observe()), _np(a.observe()))
-    for k in range(30, 60):
-        out_a, out_b = a.step(acts[k]), b.step(acts[k])
-        want = host.step(acts[k])
-        assert_step_equal(out_b, want, f"step {k}")
-        for x, y in zip(out_a, out_b):
-            assert torch.equal(x, y)
-        assert torch.equal(a.observe(), b.observe())
-    assert_env_equal(b, host, "continued")
-    fresh = _pair(dev, n, "uint8", **kw)[0]
-    fresh.load_state_dict(fresh.state_dict())          # never started: stays so
-    with pytest.raises(RuntimeError, match="reset"):
-        fresh.observe()
-    with pytest.raises(ValueError, match="n_envs"):
-        _pair(dev, n + 1, "uint8", **kw)[0].load_state_dict(sd)
-    with pytest.raises(ValueError, match="seed"):
-        _pair(dev, n, "uint8", seed=1, **kw)[0].load_state_dict(sd)
-    # the other game's snapshot is refused, either way round
-    other = DeviceBreakout(n, SEED, dev, obs_dtype="uint8", **kw)
-    with pytest.raises(ValueError, match="kind"):
-        other.load_state_dict(sd)
-    with pytest.raises(ValueError, match="kind"):
-        b.load_state_dict(other.state_dict())
-
-
-def _iterate(ln, col):
-    col.collect_timesteps(RH.N_ENV, ln.agent, ln.experience_buffer)
-    ln.cumulative_timesteps += RH.N_ENV
-    td = ln.step(RH.N_ENV)
-    return td.cpu().clone(), col.envs.get_state()
+    GS.state_dict_run(GAME, dev, np.where(rng.random((60, 6)) < 0.7, 1, rng.integers(0, 3, (60, 6))), other="breakout")
 
 
 def test_learner_save_state_carries_the_environments_through_the_collector_key(dev, tmp_path):
-    ln, col = _learner(dev, tmp_path / "a")
-    col.collect_timesteps(40, ln.agent, ln.experience_buffer, random=True)
-    ln.cumulative_timesteps += 40
-    for _ in range(6):
-        _iterate(ln, col)
-    ln.save_state(tmp_path / "snap")
-    assert ln._state_part()["collector"]["envs"]["kind"] == "DeviceFreeway"
-    want = [_iterate(ln, col) for _ in range(8)]
-    ln2, col2 = _learner(dev, tmp_path / "b")
-    ln2.load_state(tmp_path / "snap")
-    got = [_iterate(ln2, col2) for _ in range(8)]
-    for k, ((td_a, st_a), (td_b, st_b)) in enumerate(zip(want, got)):
-        assert torch.equal(td_a.view(torch.int32), td_b.view(torch.int32)), f"iteration {k}: TD errors"
-        assert_same_state(st_b, st_a, f"iteration {k}")
-    RH.assert_same(RH.full_state(ln2), RH.full_state(ln), "resumed")
-    RH.assert_same(_ring(ln2.experience_buffer), _ring(ln.experience_buffer), "ring")
-    assert int(col2.envs.get_state()["t"].min()) == (40 + 14 * RH.N_ENV) // RH.N_ENV
+    GS.save_state_check(GAME, dev, tmp_path)

@@ -3,27 +3,19 @@ table reaches every branch, invariants hold over seeded play under three policie
 it -- and the host side of the device environment: the two entry points through the C ABI, their kernels' private and group
 segments, the compact state codec, the factory knob, the snapshot kinds.  Neither the restatement nor the kernel is checked
 against the ``minatar`` package."""
-import ctypes
 import os
 import re
 
 import numpy as np
 import pytest
 
+from tests import game_suite as GS
 from tests import helpers as H
 from tests import invaders_cases as IC
-from tests.invaders_ref import BRANCHES, KEY_COIN, HostSpaceInvaders, assert_same_state, coin, draw, unit_double
-from tests.test_env_host import ENV_REFUSALS, _edit, _fake_desc
+from tests.env_frame_cases import GAMES
+from tests.invaders_ref import BRANCHES, KEY_COIN, HostSpaceInvaders, assert_same_state, draw
 
-# the Philox-path run of tests/test_gpu_invaders.py (kept here: this file needs no GPU)
-SEED = 0x5EEDFACE12345
-PHILOX_RUN = dict(n=5, steps=300, kw=dict(sticky_action_prob=0.25, episode_timestep_limit=60))
-
-
-def philox_actions():
-    """The run's actions: ``np.random.RandomState(7).randint(0, 6, size=5)`` per step."""
-    rng = np.random.RandomState(7)
-    return [rng.randint(0, 6, size=PHILOX_RUN["n"]).astype(np.int64) for _ in range(PHILOX_RUN["steps"])]
+GAME = GAMES["invaders"]          # its seed and Philox-path run are tests/test_gpu_invaders.py's: kept where no GPU is needed
 
 
 def run_case(name):
@@ -229,35 +221,13 @@ def test_draw_stream_key_and_counter():
 
 
 def test_sticky_coin_counts_and_zero_never_repeats():
-    seed, n, steps = 99, 8, 200
-    host = HostSpaceInvaders(n, seed=seed, sticky_action_prob=0.25)
-    host.reset()
-    for _ in range(steps):
-        host.step(np.zeros(n, np.int64))
-    coins = np.array([coin(seed, e, t) for e in range(n) for t in range(steps)])
-    assert 0.0 <= coins.min() and coins.max() < 1.0
-    r = H.philox4x32(seed, np.array([17], np.uint64), (3 << 32) | KEY_COIN)[0]
-    assert coin(seed, 3, 17) == unit_double(r[0], r[1])
-    assert host.branches["sticky_repeat"] == int((coins < 0.25).sum())          # t runs on through the episode ends
-    host = HostSpaceInvaders(n, seed=seed, sticky_action_prob=0.0)
-    host.reset()
-    rng = np.random.default_rng(0)
-    for _ in range(100):
-        acts = rng.integers(0, 6, n)
-        host.step(acts)
-        assert [e["last_action"] for e in host.envs] == list(acts)
-    assert host.branches["sticky_repeat"] == 0
+    GS.sticky_coin_check(GAME, steps=200, free_steps=100)
 
 
 def test_the_philox_run_of_the_gpu_test_shows_a_kill_a_terminal_a_truncation_and_a_turn():
     """tests/test_gpu_invaders.py's Philox-path run (n = 5, 300 steps, limit 60, sticky_p = 0.25, actions of RandomState(7)) on
     ``HostSpaceInvaders`` alone."""
-    host = HostSpaceInvaders(PHILOX_RUN["n"], SEED, **PHILOX_RUN["kw"])
-    host.reset()
-    kills = terminals = truncations = 0
-    for acts in philox_actions():
-        _, reward, done, trunc = host.step(acts)
-        kills, terminals, truncations = kills + int(reward.sum()), terminals + int(done.sum()), truncations + int(trunc.sum())
+    host, (kills, terminals, truncations) = GS.philox_host_run(GAME)
     turns = host.branches["turn_at_column_0"] + host.branches["turn_at_column_9"]
     print(f"kills {kills}, terminals {terminals}, truncations {truncations}, turns {turns}")
     assert kills >= 1 and terminals >= 1 and truncations >= 1 and turns >= 1 and host.branches["alien_shot"] >= 1
@@ -267,88 +237,38 @@ def test_the_philox_run_of_the_gpu_test_shows_a_kill_a_terminal_a_truncation_and
 # ---------------------------------------------------------------------- the host side of the device environment
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    from prism_amd import _native as N
-    if not os.path.exists(N.LIB_PATH):
-        g.build()
-    return N.lib()
+    return GS.native_lib()
 
 
 def test_symbols_exported_declared_and_mirrored(lib):
-    from prism_amd import _native as N
-    src = open(N.HEADER_PATH).read()
-    raw = ctypes.CDLL(N.LIB_PATH)
-    for name in ("prism_env_invaders_reset", "prism_env_invaders_step"):
-        assert hasattr(raw, name) and re.search(r"\bint " + name + r"\(const prism_env_desc \*d,", src)
-        assert N.SIGNATURES[name][1][0] == ctypes.POINTER(N.EnvDesc)
+    src, signatures = GS.symbols_check(lib, GAME)
     # no draw pointer at either entry point: the step is Breakout's signature without its draw array
-    breakout = N.SIGNATURES["prism_env_breakout_step"]
-    assert N.SIGNATURES["prism_env_invaders_step"] == (breakout[0], breakout[1][:3] + breakout[1][4:])
-    assert N.SIGNATURES["prism_env_invaders_reset"] == N.SIGNATURES["prism_env_asterix_reset"] and len(N.SIGNATURES["prism_env_invaders_reset"][1]) == 2
+    breakout = signatures["prism_env_breakout_step"]
+    assert signatures["prism_env_invaders_step"] == (breakout[0], breakout[1][:3] + breakout[1][4:])
+    assert signatures["prism_env_invaders_reset"] == signatures["prism_env_asterix_reset"] and len(signatures["prism_env_invaders_reset"][1]) == 2
     assert "int prism_env_invaders_reset(const prism_env_desc *d, prism_stream_t stream);" in src
     assert re.search(r"int prism_env_invaders_step\(const prism_env_desc \*d, const int64_t \*actions, const double \*u_in, int32_t parity,\s+"
                      r"prism_stream_t stream\);", src)
-    assert f"#define PRISM_ENV_STATE_WORDS {N.ENV_STATE_WORDS}" in src and N.ENV_STATE_WORDS == 8
-    makefile = open(os.path.join(H.ROOT, "prism_amd", "csrc", "Makefile")).read()
-    assert "env_invaders.hip" in re.search(r"^SRCS := (.*)$", makefile, re.M).group(1).split()
 
 
-# Breakout's table with this game's action counts: 4 or 6 (4 is among the counts Breakout's table refuses)
-SI_REFUSALS = [(edit, text) for edit, text in ENV_REFUSALS if b"n_actions" not in text] + \
-    [(_edit(n_actions=k), b"n_actions must be 4 or 6") for k in (0, 3, 5, 7)]
-assert len(SI_REFUSALS) == len(ENV_REFUSALS) + 2
-
-
-def _call(lib, entry, p, actions=0x40000000, parity=0):
-    if entry == "reset":
-        return lib.prism_env_invaders_reset(p, None)
-    return lib.prism_env_invaders_step(p, actions, None, parity, None)
+assert len(GS.refusals(GAME)) == len(GS.ENV_REFUSALS) + 2          # 4 or 6 (4 is among the counts Breakout's table refuses)
 
 
 @pytest.mark.parametrize("entry", ["reset", "step"])
-@pytest.mark.parametrize("case", range(len(SI_REFUSALS)))
+@pytest.mark.parametrize("case", range(len(GS.refusals(GAME))))
 def test_env_refusals_without_device(lib, entry, case):
     """Every refusal of Breakout's table, with the same text but for the action counts, through this game's entry points."""
-    edit, text = SI_REFUSALS[case]
-    d = _fake_desc()
-    if edit is not None:
-        edit(d)
-    rc = _call(lib, entry, None if edit is None else ctypes.byref(d))
-    assert rc == -1, (rc, lib.prism_last_error())
-    assert b"check_env: " in lib.prism_last_error() and text in lib.prism_last_error(), lib.prism_last_error()
+    GS.refusal_check(lib, GAME, entry, case)
 
 
 def test_step_refuses_null_actions_and_bad_parity(lib):
-    d = _fake_desc()
-    assert _call(lib, "step", ctypes.byref(d), actions=None) == -1
-    assert b"prism_env_invaders_step: actions is null" in lib.prism_last_error()
-    for parity in (2, -1):
-        assert _call(lib, "step", ctypes.byref(d), parity=parity) == -1
-        assert b"parity must be 0 or 1" in lib.prism_last_error()
-    d.n_actions = 4          # the minimal set is accepted as far as the next check
-    assert _call(lib, "step", ctypes.byref(d), actions=None) == -1 and b"actions is null" in lib.prism_last_error()
+    GS.null_actions_and_parity_check(lib, GAME)
 
 
 def test_the_kernels_have_no_private_and_no_group_segment(tmp_path):
     """Read from the code object's metadata of env_invaders.hip (block and bullet rows are reached by shifts of scalar words:
     an array indexed by a row or a column would land in the private segment)."""
-    import shutil
-    import subprocess
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(H.ROOT, "prism_amd", "csrc")
-    out = tmp_path / "env_invaders.s"
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-                    "-I" + os.path.join(H.ROOT, "include"), "-I" + csrc, "-S", "--cuda-device-only", "-o", str(out),
-                    os.path.join(csrc, "env_invaders.hip")], check=True, timeout=600, stdout=subprocess.DEVNULL,
-                   stderr=subprocess.DEVNULL)
-    kernels = dict(re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", out.read_text(), re.S))
-    names = [k for k in kernels if "env_invaders_" in k]
-    assert len(names) == 2 and sum("env_invaders_reset_kernel" in k for k in names) == sum("env_invaders_step_kernel" in k for k in names) == 1
-    for name in names:
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", kernels[name]).group(1)) == 0, name
-        assert int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", kernels[name]).group(1)) == 0, name
+    assert set(GS.kernel_segments(GAME, tmp_path).values()) == {(0, 0)}
 
 
 def test_named_constants_stand_once_on_each_side():
@@ -443,18 +363,7 @@ def test_factory_knob_off_on_and_bad(monkeypatch):
     from prism_amd.collectors import VectorCollector
     from prism_amd.config import baseline_config
     from prism_amd.factory import collector_factory, env_factory
-    made = []
-
-    def fake(kind):
-        class Fake:
-            obs_shape, n_actions = (10, 10, 6), 4
-
-            def __init__(self, *a, **kw):
-                made.append((kind, a, kw))
-        return Fake
-
-    for kind in ("SpaceInvaders", "Asterix", "Freeway", "Breakout"):
-        monkeypatch.setattr(envs, "Device" + kind, fake(kind))
+    made = GS.fake_device_classes(monkeypatch, GAME, ("SpaceInvaders", "Asterix", "Freeway", "Breakout"))
     assert env_factory.DEVICE_GAMES["SpaceInvaders"] == "DeviceSpaceInvaders" and env_factory.DEFAULT_DEVICE_GAMES == ("Breakout",)
     assert sorted(set(env_factory.MINATAR_GAMES) - set(env_factory.DEVICE_GAMES)) == ["Seaquest"]
     cfg = baseline_config(2, device="cuda:0", env_name="MinAtar/SpaceInvaders-v1", atari_sticky_actions_prob=0.1, num_processes=9,
@@ -519,15 +428,8 @@ def test_the_real_class_counts_four_minimal_actions_before_it_needs_a_device():
 
 
 def test_snapshot_kind_mismatch_is_refused():
-    import torch
-    from prism_amd.envs import DeviceAsterix, DeviceBreakout, DeviceSpaceInvaders
-    snap = lambda kind, a=6: dict(kind=kind, n_envs=4, n_actions=a, seed=9, started=False, state=torch.zeros((4, 8), dtype=torch.int32))
-
-    def bare(cls, n_actions=6):
-        env = cls.__new__(cls)
-        env.__dict__.update(dict(_name=cls.__name__, n_envs=4, n_actions=n_actions, seed=9, _started=False))
-        return env
-
+    from prism_amd.envs import DeviceAsterix, DeviceSpaceInvaders
+    bare, snap = GS.bare, GS.snap
     with pytest.raises(ValueError, match="kind = 'DeviceBreakout' in the snapshot, 'DeviceSpaceInvaders' here"):
         bare(DeviceSpaceInvaders).load_state_dict(snap("DeviceBreakout"))
     with pytest.raises(ValueError, match="kind = 'DeviceAsterix' in the snapshot, 'DeviceSpaceInvaders' here"):

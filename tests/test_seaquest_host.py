@@ -3,28 +3,20 @@ every branch, invariants hold over seeded play under three policies (the conditi
 overflow), the draws sit where DESIGN.md 7.7 puts them -- and the host side of the device environment: the two entry points
 through the C ABI, their kernels' private segment, the state codec, the two factory knobs, the snapshot kinds.  Neither the
 restatement nor the kernel is checked against the ``minatar`` package."""
-import ctypes
 import os
 import re
 
 import numpy as np
 import pytest
 
+from tests import game_suite as GS
 from tests import helpers as H
 from tests import seaquest_cases as SC
+from tests.env_frame_cases import GAMES
 from tests.seaquest_ref import (BRANCHES, CAPACITY, KEY_COIN, KEY_DIVER, KEY_ENEMY, LISTS, HostSeaquest, assert_same_state, coin,
                                 diver_map, draw, enemy_map, unit_double)
-from tests.test_env_host import ENV_REFUSALS, _edit, _fake_desc
 
-# the Philox-path run of tests/test_gpu_seaquest.py (kept here: this file needs no GPU)
-SEED = 0x5EA0E57C0FFEE
-PHILOX_RUN = dict(n=5, steps=300, kw=dict(sticky_action_prob=0.25, episode_timestep_limit=60))
-
-
-def philox_actions():
-    """The run's actions: ``np.random.RandomState(7).randint(0, 6, size=5)`` per step."""
-    rng = np.random.RandomState(7)
-    return [rng.randint(0, 6, size=PHILOX_RUN["n"]).astype(np.int64) for _ in range(PHILOX_RUN["steps"])]
+GAME = GAMES["seaquest"]          # its seed and Philox-path run are tests/test_gpu_seaquest.py's: kept where no GPU is needed
 
 
 def run_case(name):
@@ -288,30 +280,11 @@ def test_draw_map_edges_and_frequencies():
 
 
 def test_sticky_coin_counts_and_zero_never_repeats():
-    seed, n, steps = 99, 8, 120
-    host = HostSeaquest(n, seed=seed, sticky_action_prob=0.25)
-    host.reset()
-    for _ in range(steps):
-        host.step(np.zeros(n, np.int64))
-    coins = np.array([coin(seed, e, t) for e in range(n) for t in range(steps)])
-    assert host.branches["sticky_repeat"] == int((coins < 0.25).sum())          # t runs on through the episode ends
-    host = HostSeaquest(n, seed=seed, sticky_action_prob=0.0)
-    host.reset()
-    rng = np.random.default_rng(0)
-    for _ in range(60):
-        acts = rng.integers(0, 6, n)
-        host.step(acts)
-        assert [e["last_action"] for e in host.envs] == list(acts)
-    assert host.branches["sticky_repeat"] == 0
+    GS.sticky_coin_check(GAME, steps=120, free_steps=60)
 
 
 def test_the_philox_run_of_the_gpu_test_shows_spawns_a_terminal_and_a_truncation():
-    host = HostSeaquest(PHILOX_RUN["n"], SEED, **PHILOX_RUN["kw"])
-    host.reset()
-    terminals = truncations = 0
-    for acts in philox_actions():
-        _, reward, done, trunc = host.step(acts)
-        terminals, truncations = terminals + int(done.sum()), truncations + int(trunc.sum())
+    host, (_, terminals, truncations) = GS.philox_host_run(GAME)
     br = host.branches
     print(f"terminals {terminals}, truncations {truncations}, fish {br['spawn_fish']}, subs {br['spawn_sub']}, divers {br['spawn_diver']}, "
           f"blocked {br['spawn_blocked']}, fired {br['fire']}")
@@ -322,87 +295,38 @@ def test_the_philox_run_of_the_gpu_test_shows_spawns_a_terminal_and_a_truncation
 # ---------------------------------------------------------------------- the host side of the device environment
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    from prism_amd import _native as N
-    if not os.path.exists(N.LIB_PATH):
-        g.build()
-    return N.lib()
+    return GS.native_lib()
 
 
 def test_symbols_exported_declared_and_mirrored(lib):
     from prism_amd import _native as N
-    src = open(N.HEADER_PATH).read()
-    raw = ctypes.CDLL(N.LIB_PATH)
-    for name in ("prism_env_seaquest_reset", "prism_env_seaquest_step"):
-        assert hasattr(raw, name) and re.search(r"\bint " + name + r"\(const prism_env_desc \*d,", src)
-        assert N.SIGNATURES[name][1][0] == ctypes.POINTER(N.EnvDesc)
-    assert N.SIGNATURES["prism_env_seaquest_step"] == N.SIGNATURES["prism_env_asterix_step"]          # one draw array
-    assert N.SIGNATURES["prism_env_seaquest_reset"] == N.SIGNATURES["prism_env_asterix_reset"]        # a reset draws nothing
+    src, signatures = GS.symbols_check(lib, GAME)
+    assert signatures["prism_env_seaquest_step"] == signatures["prism_env_asterix_step"]          # one draw array
+    assert signatures["prism_env_seaquest_reset"] == signatures["prism_env_asterix_reset"]        # a reset draws nothing
     assert "int prism_env_seaquest_reset(const prism_env_desc *d, prism_stream_t stream);" in src
     assert re.search(r"int prism_env_seaquest_step\(const prism_env_desc \*d, const int64_t \*actions, const double \*u_in, "
                      r"const uint8_t \*draws_in,\s+int32_t parity, prism_stream_t stream\);", src)
     # a record width and a status bit of its own; the 8-word record and the descriptor are what they were
     assert f"#define PRISM_ENV_SEAQUEST_STATE_WORDS {N.ENV_SEAQUEST_STATE_WORDS}" in src and N.ENV_SEAQUEST_STATE_WORDS == 112
     assert f"#define PRISM_ENV_STATUS_OVERFLOW {N.ENV_STATUS_OVERFLOW}u" in src and N.ENV_STATUS_OVERFLOW == 2 != N.ENV_STATUS_BAD_ACTION
-    assert f"#define PRISM_ENV_STATE_WORDS {N.ENV_STATE_WORDS}" in src and N.ENV_STATE_WORDS == 8
     assert 8 + sum(CAPACITY.values()) == N.ENV_SEAQUEST_STATE_WORDS
-    makefile = open(os.path.join(H.ROOT, "prism_amd", "csrc", "Makefile")).read()
-    assert "env_seaquest.hip" in re.search(r"^SRCS := (.*)$", makefile, re.M).group(1).split()
-
-
-# Breakout's table with this game's action count: 6 only
-SQ_REFUSALS = [(edit, text) for edit, text in ENV_REFUSALS if b"n_actions" not in text] + \
-    [(_edit(n_actions=k), b"n_actions must be 6") for k in (0, 3, 4, 5, 7)]
-
-
-def _call(lib, entry, p, actions=0x40000000, parity=0):
-    if entry == "reset":
-        return lib.prism_env_seaquest_reset(p, None)
-    return lib.prism_env_seaquest_step(p, actions, None, None, parity, None)
 
 
 @pytest.mark.parametrize("entry", ["reset", "step"])
-@pytest.mark.parametrize("case", range(len(SQ_REFUSALS)))
+@pytest.mark.parametrize("case", range(len(GS.refusals(GAME))))
 def test_env_refusals_without_device(lib, entry, case):
-    """Every refusal of Breakout's table, with the same text but for the action count, through this game's entry points."""
-    edit, text = SQ_REFUSALS[case]
-    d = _fake_desc()
-    if edit is not None:
-        edit(d)
-    rc = _call(lib, entry, None if edit is None else ctypes.byref(d))
-    assert rc == -1, (rc, lib.prism_last_error())
-    assert b"check_env: " in lib.prism_last_error() and text in lib.prism_last_error(), lib.prism_last_error()
+    """Every refusal of Breakout's table, with the same text but for the action count (6 only), through this game's entry points."""
+    GS.refusal_check(lib, GAME, entry, case)
 
 
 def test_step_refuses_null_actions_and_bad_parity(lib):
-    d = _fake_desc()
-    assert _call(lib, "step", ctypes.byref(d), actions=None) == -1
-    assert b"prism_env_seaquest_step: actions is null" in lib.prism_last_error()
-    for parity in (2, -1):
-        assert _call(lib, "step", ctypes.byref(d), parity=parity) == -1
-        assert b"parity must be 0 or 1" in lib.prism_last_error()
+    GS.null_actions_and_parity_check(lib, GAME)
 
 
 def test_the_kernels_have_no_private_segment(tmp_path):
     """Read from the code object's metadata of env_seaquest.hip: lane i holds entry i of every list, so no per-lane array is
     indexed by a run-time value.  The group segment is the four waves' boards of 104 words."""
-    import shutil
-    import subprocess
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(H.ROOT, "prism_amd", "csrc")
-    out = tmp_path / "env_seaquest.s"
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-                    "-I" + os.path.join(H.ROOT, "include"), "-I" + csrc, "-S", "--cuda-device-only", "-o", str(out),
-                    os.path.join(csrc, "env_seaquest.hip")], check=True, timeout=600, stdout=subprocess.DEVNULL,
-                   stderr=subprocess.DEVNULL)
-    kernels = dict(re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", out.read_text(), re.S))
-    names = [k for k in kernels if "env_seaquest_" in k]
-    assert len(names) == 2 and sum("env_seaquest_reset_kernel" in k for k in names) == sum("env_seaquest_step_kernel" in k for k in names) == 1
-    for name in names:
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", kernels[name]).group(1)) == 0, name
-        assert int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", kernels[name]).group(1)) == 4 * 104 * 4, name
+    assert set(GS.kernel_segments(GAME, tmp_path).values()) == {(0, 4 * 104 * 4)}
 
 
 def test_named_constants_stand_once_on_each_side():
@@ -510,18 +434,7 @@ def test_both_factory_knobs(monkeypatch):
     from prism_amd.collectors import VectorCollector
     from prism_amd.config import baseline_config
     from prism_amd.factory import collector_factory, env_factory
-    made = []
-
-    def fake(kind):
-        class Fake:
-            obs_shape, n_actions = (10, 10, 10), 6
-
-            def __init__(self, *a, **kw):
-                made.append((kind, a, kw))
-        return Fake
-
-    for kind in ("Seaquest", "SpaceInvaders", "Asterix", "Freeway", "Breakout"):
-        monkeypatch.setattr(envs, "Device" + kind, fake(kind))
+    made = GS.fake_device_classes(monkeypatch, GAME, ("Seaquest", "SpaceInvaders", "Asterix", "Freeway", "Breakout"))
     assert env_factory.WIDE_DEVICE_GAMES == {"Seaquest": "DeviceSeaquest"} and env_factory.DEFAULT_WIDE_DEVICE_GAMES == ()
     assert "Seaquest" not in env_factory.DEVICE_GAMES and env_factory.DEFAULT_DEVICE_GAMES == ("Breakout",)
     assert sorted(set(env_factory.MINATAR_GAMES) - set(env_factory.DEVICE_GAMES) - set(env_factory.WIDE_DEVICE_GAMES)) == []
@@ -590,15 +503,8 @@ def test_the_real_class_checks_before_it_needs_a_device():
 
 
 def test_snapshot_kind_mismatch_is_refused():
-    import torch
-    from prism_amd.envs import DeviceAsterix, DeviceSeaquest, DeviceSpaceInvaders
-    snap = lambda kind, words=8: dict(kind=kind, n_envs=4, n_actions=6, seed=9, started=False, state=torch.zeros((4, words), dtype=torch.int32))
-
-    def bare(cls):
-        env = cls.__new__(cls)
-        env.__dict__.update(dict(_name=cls.__name__, n_envs=4, n_actions=6, seed=9, _started=False))
-        return env
-
+    from prism_amd.envs import DeviceAsterix, DeviceSeaquest
+    bare, snap = GS.bare, lambda kind, words=8: GS.snap(kind, words=words)
     with pytest.raises(ValueError, match="kind = 'DeviceSpaceInvaders' in the snapshot, 'DeviceSeaquest' here"):
         bare(DeviceSeaquest).load_state_dict(snap("DeviceSpaceInvaders"))
     with pytest.raises(ValueError, match="kind = 'DeviceAsterix' in the snapshot, 'DeviceSeaquest' here"):
